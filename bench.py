@@ -318,6 +318,29 @@ def sample_track_lengths(rng, size):
 
 
 _REALISTIC_CACHE = {}
+_REALISTIC_PENDING = {}                              # (B, seed) -> future of _realistic_job, taken by the first VisualEkfBench of that key
+
+
+def _realistic_job(B, seed):
+    """What the first VisualEkfBench(B, seed=seed, realistic=True) draws: the frame, and its generator's state after the draws."""
+    rng = np.random.default_rng(300 + seed)
+    return make_visual_frame_realistic(rng, B), rng.bit_generator.state
+
+
+def prefetch_realistic(B, seeds):
+    """Draws the realistic frames of several engines at once in fresh worker processes (numpy only, no GPU): ~6 s of numpy per 1024
+    filters and engine, which the lanes would otherwise draw one after the other. The arrays and the generator states that follow
+    are bit-identical to drawing them in this process."""
+    import concurrent.futures
+    import multiprocessing
+    seeds = [s for s in dict.fromkeys(seeds) if (B, s) not in _REALISTIC_CACHE and (B, s) not in _REALISTIC_PENDING]
+    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    if len(seeds) < 2 or cpus < 2:
+        return
+    pool = concurrent.futures.ProcessPoolExecutor(max_workers=min(len(seeds), cpus), mp_context=multiprocessing.get_context("spawn"))
+    for s in seeds:
+        _REALISTIC_PENDING[(B, s)] = pool.submit(_realistic_job, B, s)
+    pool.shutdown(wait=False)
 
 
 def make_visual_frame_realistic(rng, B, distinct=None, p_inlier=0.25):
@@ -370,6 +393,9 @@ class VisualEkfBench:
         self.realistic, self.lens, self.chained = realistic, None, chained
         if realistic:
             key = (B, seed)
+            if key in _REALISTIC_PENDING and key not in _REALISTIC_CACHE:        # drawn ahead by prefetch_realistic
+                _REALISTIC_CACHE[key], state = _REALISTIC_PENDING.pop(key).result()
+                rng.bit_generator.state = state
             if key not in _REALISTIC_CACHE:                     # (7 s of numpy per 1024 distinct filters: legs with the same seed share them)
                 _REALISTIC_CACHE[key] = make_visual_frame_realistic(rng, B)
             T1, T2, means, lens, idx, feat, vel, y = _REALISTIC_CACHE[key]
@@ -1209,6 +1235,43 @@ def emit_record(out):
     sys.stdout.flush()
 
 
+DUMP_SEQUENCES = 2048          # --dump-outputs: sequences written over all engines (a seeded sample of each engine's B)
+DUMP_COV_FILTERS = 4           # full covariances written per engine (the diagonal is written for every sampled sequence)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, engines):
+    """--dump-outputs: what the headline's last timed step handed to its caller, per engine i as out_dir/lane<i>_<name>.npy (float32 /
+    float64): both LK calls (positions, statuses), the rotation RANSAC (statuses, R), the GFTT key points, and the filters (mean, the
+    covariance's diagonal, a few full covariances, visit / gate statuses, updates applied) of a fixed seeded sample of the sequences.
+    engines: [(TrackerBench, VisualEkfBench, device pointer of the covariance buffer the last timed step left current)]."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    per = max(1, DUMP_SEQUENCES // len(engines))
+    total = 0
+    for i, (tb, eb, p_ptr) in enumerate(engines):
+        B, n, dev = tb.B, eb.ekf.n, tb.grid.device
+        rng = np.random.default_rng(4242 + i)
+        sel = np.arange(B) if B <= per else np.sort(rng.choice(B, per, replace=False))
+        cov = np.sort(rng.choice(sel, min(DUMP_COV_FILTERS, len(sel)), replace=False))
+        ix, cx = torch.from_numpy(sel).to(dev), torch.from_numpy(cov).to(dev)
+        m = torch.as_tensor(_DevView(eb.ekf.device_pointers()[0], (B, n)), device=dev)
+        P = torch.as_tensor(_DevView(p_ptr, (B, n, n)), device=dev)          # column-major per filter: P[b].T[i, j] = P_ij
+        out = {"sequences": torch.from_numpy(sel.astype(np.float64)), "cov_sequences": torch.from_numpy(cov.astype(np.float64)),
+               "lk_temporal_xy": tb.cur_left.reshape(B, -1, 2)[ix], "lk_temporal_status": tb.st1.reshape(B, -1)[ix].float(),
+               "lk_stereo_xy": tb.cur_right.reshape(B, -1, 2)[ix], "lk_stereo_status": tb.st2.reshape(B, -1)[ix].float(),
+               "ekf_mean": m[ix], "ekf_cov_diag": P[ix].diagonal(dim1=1, dim2=2), "ekf_cov": P[cx].transpose(1, 2),
+               "visit_status": eb.st[:, ix].float(), "gate_status": eb.gs[:, ix].float(), "updates_applied": eb.counter[ix].float()}
+        if tb.chain:
+            out.update(ransac_status=tb.rst[ix].float(), ransac_R=tb.rR[ix], gftt_keypoints=tb.kp[ix])
+        for name, a in out.items():
+            a = a.detach().cpu().numpy()
+            assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+            total += a.nbytes
+            np.save(os.path.join(out_dir, f"lane{i}_{name}.npy"), np.ascontiguousarray(a))
+    assert total <= DUMP_LIMIT_BYTES, total
+
+
 class BenchRun:
     """One bench.py run: the shared state of the legs (arguments, the distributed timing contract, the lanes, the tracker and EKF
     bench objects) and one method per leg. r04 / r05 had all of this as one 700-line main()."""
@@ -1263,17 +1326,19 @@ class BenchRun:
                     gl_, fr_ = [], []
                     for _ in range(N_CYCLE):
                         g_ = torch.cuda.CUDAGraph()
-                        fr_.append((tbi_.k, ebi_.k))                 # the frame this graph replays (verify_c3 checks the last one replayed)
+                        k_ = (tbi_.k, ebi_.k)                        # the frame this graph replays (verify_c3 checks the last one replayed)
                         with torch.cuda.graph(g_, stream=si_):
                             tbi_.step(); ebi_.step()
+                        fr_.append(k_ + (ebi_.ekf.device_pointers()[1],))    # + the covariance buffer the replay leaves current
                         gl_.append(g_)
                     si_.synchronize()
                 self.pre_engines.append((si_, tbi_, ebi_, gl_, fr_))
             torch.cuda.synchronize()
 
-    def c3_leg(self, realistic, repeats, graph, chained=False, verify_n=0):
+    def c3_leg(self, realistic, repeats, graph, chained=False, verify_n=0, profile=True, dump=False):
         """One single-engine C3 leg under the timing contract: `repeats` timed regions of exactly args.steps steps each (barrier + sync on
         both sides, MAX over ranks), eager first (per-kernel hipEvent times), then -- graph -- the same steps as HIP-graph replay.
+        profile=False (graph): no eager region, the graph replay is the only timed region. dump: --dump-outputs of the last timed step.
         Returns a dict: eb (the EKF bench object, still open), tb, times (graph replay if it ran, else eager), kern, applied, launch,
         eager, nsteps, verify."""
         tb = self.tb_c2
@@ -1283,14 +1348,17 @@ class BenchRun:
         for _ in range(self.args.warmup):
             tb.step(); eb_.step()
         eb_.applied.zero_()
-        tb.ctx.profile_enable(True)
-        tb.ctx.profile_reset()
-        eager = [self.env.timed(lambda: (tb.step(), eb_.step()), self.args.steps) for _ in range(1 if graph else max(1, repeats))]
-        prof = {name: tb.ctx.profile_read(kid) for name, kid in self.names}
+        if profile:
+            tb.ctx.profile_enable(True)
+            tb.ctx.profile_reset()
+        eager = [self.env.timed(lambda: (tb.step(), eb_.step()), self.args.steps) for _ in range(int(profile) if graph else max(1, repeats))]
+        prof = {name: tb.ctx.profile_read(kid) for name, kid in self.names} if profile else {}
         tb.ctx.profile_enable(False)
         nsteps = self.args.steps * len(eager)
         kern = {k: {"avg_ms": ms / n, "launches": n, "total_ms": ms, "ms_per_step": ms / nsteps} for k, (ms, n) in prof.items() if n}
-        applied_ = float(eb_.applied.item()) / (self.B * nsteps)
+        applied_ = float(eb_.applied.item()) / (self.B * nsteps) if nsteps else None
+        if dump and not graph:
+            self.dump_outputs([(tb, eb_, eb_.ekf.device_pointers()[1])])
         times, launch, last_frame = None, "eager", None
         if graph:
             # The step is a fixed launch sequence with period N_CYCLE (camera path, RANSAC draws, GFTT every 2nd frame, the augmentation's
@@ -1311,9 +1379,10 @@ class BenchRun:
                     side.synchronize()
                     for _ in range(N_CYCLE):
                         g_ = torch.cuda.CUDAGraph()
-                        fr_.append((tb.k, eb_.k))
+                        k_ = (tb.k, eb_.k)
                         with torch.cuda.graph(g_, stream=side):
                             tb.step(); eb_.step()
+                        fr_.append(k_ + (eb_.ekf.device_pointers()[1],))
                         gl_.append(g_)
                     side.synchronize()
                 torch.cuda.synchronize()
@@ -1327,6 +1396,8 @@ class BenchRun:
                     replay()
                 torch.cuda.synchronize()
                 times = [self.env.timed(replay, self.args.steps) for _ in range(max(1, repeats))]
+                if dump:
+                    self.dump_outputs([(tb, eb_, fr_[(cnt[0] - 1) % N_CYCLE][2])])
                 while cnt[0] % N_CYCLE:                          # back to a cycle boundary: the host-side counters (frame number, discard
                     replay()                                     # pattern) match the device state again for the eager steps that follow
                 torch.cuda.synchronize()
@@ -1336,6 +1407,8 @@ class BenchRun:
                 launch = "hipGraph replay"
                 self.keep_graphs.append(gl_)                          # (destroyed with the process: the captured kernels hold the library's buffers)
             except Exception as ex:                              # pragma: no cover
+                if not eager or dump:                            # (profile=False: no eager region to report instead; dump: nor its outputs)
+                    raise
                 tb.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
                 launch = "eager (graph capture failed: " + repr(ex)[:120] + ")"
                 times = None
@@ -1345,13 +1418,14 @@ class BenchRun:
         return {"eb": eb_, "tb": tb, "times": times if times is not None else eager, "kern": kern, "applied": applied_, "launch": launch,
                 "eager": eager, "nsteps": nsteps, "verify": ver}
 
-    def c3_lanes(self, repeats, verify_n):
+    def c3_lanes(self, repeats, verify_n, full=True):
         """The realistic C3 step on every lane of the hv_lanes set at once: a step replays one captured graph of EACH lane on the lane's
         own stream, i.e. is a step of lanes x B frames. The visit loop of one lane is a chain of dependent launches of which several
         fill a fraction of the chip (the long class's launch, the second update launch); the other lanes' chains run in those gaps (the
         lanes' VALU-bound tracker halves gain nothing from each other: rocprofv3 timeline in profiles/r04). Timed twice: the first two
         lanes alone (`lanes_2`: r03's configuration of 2 x B resident sequences) and all of them (the headline). After the timed regions
-        EVERY lane is verified against the oracle from the state its last replay left (the lanes' last replays ran beside each other)."""
+        EVERY lane is verified against the oracle from the state its last replay left (the lanes' last replays ran beside each other).
+        full=False: the headline region alone (no `lanes_2`, no verification); returns times and launch only."""
         cnt = [0] * len(self.pre_engines)
 
         def replay_on(sel):
@@ -1367,12 +1441,16 @@ class BenchRun:
             replay_on(every)()
         torch.cuda.synchronize()
         two = None
-        if len(self.pre_engines) > 2:
+        if full and len(self.pre_engines) > 2:
             t2 = sorted(self.env.timed(replay_on([0, 1]), self.args.steps) for _ in range(3))[1]
             two = {"sequences_per_gpu": 2 * self.B, "value": aggregate_value(2 * self.B, self.world, self.args.steps, t2), "unit": "frames/s",
                    "ms_per_step": t2 / self.args.steps * 1e3, "r03_value": 129538.0,
                    "note": "two lanes of the same set replaying alone: r03's headline configuration (2 engines x 1024 sequences)"}
         times = [self.env.timed(replay_on(every), self.args.steps) for _ in range(max(1, repeats))]
+        self.dump_outputs([(t_, e_, fr_[(cnt[i_] - 1) % N_CYCLE][2]) for i_, (_, t_, e_, _, fr_) in enumerate(self.pre_engines)])
+        launch = f"hipGraph replay, {len(self.pre_engines)} lanes (hv_lanes) x {self.B} sequences, one captured graph per lane and step"
+        if not full:
+            return {"times": times, "launch": launch}
         for i_ in every:
             while cnt[i_] % N_CYCLE:
                 replay_on([i_])()
@@ -1385,8 +1463,7 @@ class BenchRun:
             for i_, (_, t_, e_, _, fr_) in enumerate(self.pre_engines):
                 vers.append(verify_c3(t_, e_, verify_n, seed=self.rank + 17 * i_, frame=fr_[-1]))
         gate_hist = [int((self.pre_engines[0][2].gs[k] == 0).sum().item()) for k in range(VISITS)]
-        return {"times": times, "verify": vers, "gate_hist": gate_hist, "lanes_2": two,
-                "launch": f"hipGraph replay, {len(self.pre_engines)} lanes (hv_lanes) x {self.B} sequences, one captured graph per lane and step"}
+        return {"times": times, "verify": vers, "gate_hist": gate_hist, "lanes_2": two, "launch": launch}
 
     def leg_headline_lanes(self):
         global W, H, NPTS
@@ -1455,7 +1532,8 @@ class BenchRun:
         global W, H, NPTS
         # ---- the realistic C3 step with ONE engine (one context on a torch stream): the per-kernel hipEvent profile of the headline
         # workload comes from its eager region; with lanes it is also the `one_engine` comparison figure (r03's first-half configuration) ----
-        self.one = self.c3_leg(True, self.args.repeats if self.head_lanes is None else 1, not self.args.no_graph, verify_n=self.args.verify if self.head_lanes is None else min(self.args.verify, 2))
+        self.one = self.c3_leg(True, self.args.repeats if self.head_lanes is None else 1, not self.args.no_graph, verify_n=self.args.verify if self.head_lanes is None else min(self.args.verify, 2),
+                               dump=self.head_lanes is None)
         eb, self.k3, self.applied, self.eager3, self.nprof3, self.tb = self.one["eb"], self.one["kern"], self.one["applied"], self.one["eager"], self.one["nsteps"], self.one["tb"]
         t_one = sorted(self.one["times"])[len(self.one["times"]) // 2]
         self.one_engine = {"sequences_per_gpu": self.B, "value": aggregate_value(self.B, self.world, self.args.steps, t_one), "unit": "frames/s",
@@ -1488,6 +1566,28 @@ class BenchRun:
         self.long_class_share = float((eb.lens_host > 12).mean())      # (split form, late r06: the short class ends at 12 poses = 48 rows)
         eb.ekf.close()
         del eb
+
+    def headline_record(self):
+        """The record's headline keys (rank 0): the realistic C3 step timed on self.times3 (plain and --full runs alike)."""
+        return {
+            "metric": "VIO frames/sec at 752x480 stereo, 200 KLT features; pyramid+KLT HBM GB/s",
+            "value": aggregate_value(self.ENG * self.B, self.world, self.args.steps, self.el3), "unit": "frames/s", "n_gpus": self.world, "steps": self.args.steps, "warmup": self.args.warmup,
+            "ms_per_step": self.el3 / self.args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u8/int16 pixels, int32/int64 sums, f32 solve (tracker); f64 (EKF)", "data": "synthetic",
+            "smoke_all_ranks_on_one_device": self.forced_dev is not None or None,
+            "repeats_ms_per_step": [t_ / self.args.steps * 1e3 for t_ in self.times3], "value_is": "median of the repeats (each an exact K-step timed region)",
+            "launch": self.launch3,
+            "config": {"workload": "C3: 752x480 stereo, 200 pts -- the whole frame chained on one stream per sequence: 2 pyramid builds, temporal LK from "
+                                   "predicted positions, 2-point rotation RANSAC on its output, stereo LK, GFTT key points every 2nd frame (HIP tracker), "
+                                   "then the HIP EKF from the device mean: 20 track visits (triangulation + prepareVisualUpdate + chi2 gate; track lengths "
+                                   "5 + Geometric(0.2) <= 21 stereo poses = 20 .. 84 rows, per-filter independent inliers p = 0.25 drawn independently of the track length, quota 5 updates), "
+                                   "symmetrise, 1 Joseph-form augmentation, 10 predicts in one launch; state dim 160",
+                       "sequences_per_gpu": self.ENG * self.B, "engines_per_gpu": self.ENG, "sequences_per_engine": self.B, "frames_per_step": self.world * self.ENG * self.B,
+                       "engines": "the lanes of one hv_lanes set (include/hybvio_hip.h): independent batched contexts whose streams the LIBRARY creates "
+                                  "from the device's high-priority queue pool; a step replays one captured graph of each, their launch chains fill each "
+                                  "other's idle CUs; `one_engine` = the same leg with one context on a torch stream",
+                       "parallelism": f"replicas x{self.world} (no collective)",
+                       "timing_process_group": self.args.dist_backend if self.world > 1 else None, "host_cores_per_rank": self.env.cores}}
 
     def assemble_headline(self):
         global W, H, NPTS
@@ -1568,37 +1668,23 @@ class BenchRun:
                    "ekf_update_gate": "f64 MFMA + per-workgroup latency: one 512-thread workgroup per CU keeps P in registers (read once, written once); "
                                       "MFMA busy ~35 %"}.get(dom)
         if self.rank == 0:
-            head = {
-                "metric": "VIO frames/sec at 752x480 stereo, 200 KLT features; pyramid+KLT HBM GB/s",
-                "value": aggregate_value(self.ENG * self.B, self.world, self.args.steps, self.el3), "unit": "frames/s", "n_gpus": self.world, "steps": self.args.steps, "warmup": self.args.warmup,
-                "ms_per_step": self.el3 / self.args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": "u8/int16 pixels, int32/int64 sums, f32 solve (tracker); f64 (EKF)", "data": "synthetic",
-                "smoke_all_ranks_on_one_device": self.forced_dev is not None or None,
-                "repeats_ms_per_step": [t_ / self.args.steps * 1e3 for t_ in self.times3], "value_is": "median of the repeats (each an exact K-step timed region)",
-                "launch": self.launch3, "eager_ms_per_step": self.eager3[0] / self.args.steps * 1e3,
+            head = self.headline_record()
+            head.update({
+                "eager_ms_per_step": self.eager3[0] / self.args.steps * 1e3,
                 "eager_ms_per_step_is": f"ONE engine ({self.B} sequences) with eager launches: the region the per-kernel hipEvent profile (`kernels`, `roofline`) comes from",
                 "r03": {"value": 129538.0, "one_engine": 107100.0, "c3_uniform": 124600.0},
                 "one_engine": self.one_engine, "lanes_2": self.head_lanes["lanes_2"] if self.head_lanes else None,
                 "stage_pyramid_klt_frac_of_8TBs": stage["frac_of_8TBs"], "stage_pyramid_klt_frac_actual": stage["frac_actual"],
-                "parity_checked_sequences": self.verify["parity_checked_sequences"] if self.verify else 0, "parity_ok": self.verify["ok"] if self.verify else None,
-                "config": {"workload": "C3: 752x480 stereo, 200 pts -- the whole frame chained on one stream per sequence: 2 pyramid builds, temporal LK from "
-                                       "predicted positions, 2-point rotation RANSAC on its output, stereo LK, GFTT key points every 2nd frame (HIP tracker), "
-                                       "then the HIP EKF from the device mean: 20 track visits (triangulation + prepareVisualUpdate + chi2 gate; track lengths "
-                                       "5 + Geometric(0.2) <= 21 stereo poses = 20 .. 84 rows, per-filter independent inliers p = 0.25 drawn independently of the track length, quota 5 updates), "
-                                       "symmetrise, 1 Joseph-form augmentation, 10 predicts in one launch; state dim 160",
-                           "sequences_per_gpu": self.ENG * self.B, "engines_per_gpu": self.ENG, "sequences_per_engine": self.B, "frames_per_step": self.world * self.ENG * self.B,
-                           "engines": "the lanes of one hv_lanes set (include/hybvio_hip.h): independent batched contexts whose streams the LIBRARY creates "
-                                      "from the device's high-priority queue pool; a step replays one captured graph of each, their launch chains fill each "
-                                      "other's idle CUs; `one_engine` = the same leg with one context on a torch stream",
-                           "parallelism": f"replicas x{self.world} (no collective)",
+                "parity_checked_sequences": self.verify["parity_checked_sequences"] if self.verify else 0, "parity_ok": self.verify["ok"] if self.verify else None})
+            head["config"].update({
                            "track_poses_mean": self.lens_mean, "tracks_longer_than_11_poses": self.long_share, "tracks_in_the_long_class": self.long_class_share, "distinct_filters_per_engine": self.B,
                            "parity_ok": self.verify["ok"] if self.verify else None, "parity_checked_sequences": self.verify["parity_checked_sequences"] if self.verify else 0,
                            "parity_engines_checked": self.verify["engines_checked"] if self.verify else 0,
                            "stage_frac_agreed": stage["frac_of_8TBs"], "stage_frac_actual": stage["frac_actual"],
                            "one_engine_value": self.one_engine["value"], "one_engine_ms_per_step": self.one_engine["ms_per_step"],
                            "lanes_2_value": (self.head_lanes["lanes_2"] or {}).get("value") if self.head_lanes else None,
-                           "comparable_to_r03": "lanes_2_value (or value when 2 lanes run): r03 headline 129.5 k (2 engines x 1024 on torch streams created first); one_engine_value: r03 one_engine 107.1 k; value with 4 lanes has no r03 counterpart (r03 probe of 4 engines: 130 k)",
-                           "timing_process_group": self.args.dist_backend if self.world > 1 else None, "host_cores_per_rank": self.env.cores},
+                           "comparable_to_r03": "lanes_2_value (or value when 2 lanes run): r03 headline 129.5 k (2 engines x 1024 on torch streams created first); one_engine_value: r03 one_engine 107.1 k; value with 4 lanes has no r03 counterpart (r03 probe of 4 engines: 130 k)"})
+            head.update({
                 # the dominant kernel, labelled for what bounds it: klt_kernel issues integer VALU instructions > 90 % of the time. achieved /
                 # peak / frac stay in the contract's units on the AGREED bytes of SURVEY 8(d) (windows read once, every gradient plane counted);
                 # frac_pmc_bytes prices the bytes the kernel really moves (PMC); frac_valu_issue = instructions issued per second / the MEASURED
@@ -1652,7 +1738,7 @@ class BenchRun:
                 "tracked_fraction": self.tracked3,
                 "verify": self.verify,
                 "c2": self.c2,
-            }
+            })
             head.update(self.out)
             self.out = head
 
@@ -1922,7 +2008,31 @@ class BenchRun:
             emit_record(self.out)
         self.env.close()
 
+    def leg_headline_only(self):
+        """A plain run (no --full): the headline's timed region and nothing else -- the lanes replaying their captured steps (one engine
+        or --no-graph: the one-context leg without its eager profiling region), then its outputs if --dump-outputs is given."""
+        self.build_lanes()
+        if self.pre_engines:
+            h = self.c3_lanes(self.args.repeats, 0, full=False)
+            self.times3, self.launch3, self.ENG = h["times"], h["launch"], len(self.pre_engines)
+        else:
+            self.tb_c2 = TrackerBench(self.B, self.local_rank, seed=self.rank)
+            one = self.c3_leg(True, self.args.repeats, not self.args.no_graph, profile=False, dump=True)
+            self.times3, self.launch3, self.ENG = one["times"], one["launch"], 1
+            one["eb"].ekf.close()
+        self.el3 = sorted(self.times3)[len(self.times3) // 2]
+        if self.rank == 0:
+            self.out = self.headline_record()
+
+    def dump_outputs(self, engines):
+        if self.args.dump_outputs and self.rank == 0:
+            write_outputs(self.args.dump_outputs, engines)
+
     def run(self):
+        if not self.args.full:
+            self.leg_headline_only()
+            self.emit()
+            return
         self.build_lanes()
         self.leg_headline_lanes()
         self.leg_c2()
@@ -1957,9 +2067,14 @@ def main():
     ap.add_argument("--no-visual-track", action="store_true", help="skip the f3 (device triangulation + prepareVisualUpdate) measurement")
     ap.add_argument("--no-ransac", action="store_true", help="skip the f4 (2-point rotation RANSAC kernel) measurement")
     ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive measurement (frames handed over as host buffers)")
-    ap.add_argument("--only-headline", action="store_true", help="C2 + C3 legs only (what the rocprofv3 collection runs)")
-    ap.add_argument("--verify", type=int, default=16, help="sequences of the C3 batch re-computed by the CPU oracle after the timed region (0 = off)")
-    ap.add_argument("--repeats", type=int, default=5, help="repeats of the K-step timed region of the headline; `value` is the median repeat")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg and check (C2, f1-f4, one engine, c3_uniform, c3_chained, c3_dense_h, PCIe, C4, latency, CPU "
+                         "baselines, lanes_2, the oracle parity check, per-kernel and roofline figures); default: the headline region only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed to DIR/<name>.npy (rank 0; a seeded sample of the sequences)")
+    ap.add_argument("--only-headline", action="store_true", help="with --full: C2 + C3 legs only (what the rocprofv3 collection runs)")
+    ap.add_argument("--verify", type=int, default=16, help="with --full: sequences of the C3 batch re-computed by the CPU oracle after the timed region (0 = off)")
+    ap.add_argument("--repeats", type=int, default=None, help="repeats of the K-step timed region of the headline; `value` is the median repeat (default 1, 5 with --full)")
     ap.add_argument("--no-graph", action="store_true", help="time the headline with eager launches instead of HIP-graph replay of the captured steps")
     ap.add_argument("--engines", type=int, default=4,
                     help="lanes of the hv_lanes set of the realistic headline leg: each a batched context on library-owned streams with its own HIP "
@@ -1976,6 +2091,10 @@ def main():
         out["ekf_only_frames_per_s"], out["ekf_sample"], out["ekf_timers_ms_per_frame"] = fps_ekf, sample, tm
         print(json.dumps(out))
         return
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.engines > 1 and not args.no_graph:              # the lanes' inputs, drawn while this process sets up the device
+        prefetch_realistic(args.sequences, [int(os.environ.get("RANK", "0")) + 1000 * i for i in range(args.engines)])
     if args.only_headline:
         args.no_c4 = args.no_gftt = args.no_ingest = args.no_visual_track = args.no_ransac = args.no_pcie = True
         args.no_latency_mode = args.no_cpu_baseline = True

@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/${PROF_DIR:-trace_visit}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/tv
-rocprofv3 --kernel-trace --output-format csv -d /tmp/tv -o t -- python $R/bench.py --only-headline --steps 2 --warmup 1 --repeats 1 --verify 0 > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$TMPDIR/tv" -o t -- python $R/bench.py --full --only-headline --steps 2 --warmup 1 --repeats 1 --verify 0 > $OUT/log.txt 2>&1
 F=$(find /tmp/tv -name "*kernel_trace.csv" | head -1)
 python - "$F" "$OUT/timeline.txt" <<'PY'
 import csv, sys

@@ -94,12 +94,9 @@ def test_quat2rmat_goldens(oracle, fx):
 
 
 def test_chi2_table_matches_reference_constants():
-    """The generated chi2inv95 table equals the reference's (src/odometry/util.hpp:23) where the
-    reference tree is available (it is not on the GPU box)."""
-    ref = "/root/reference/src/odometry/util.hpp"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present")
-    vals = [float(x) for x in re.search(r"chi2inv95 = \{([^}]*)\}", open(ref).read()).group(1).split(",")]
+    """The generated chi2inv95 table equals the reference's (src/odometry/util.hpp:23), stored as
+    tests/golden/chi2inv95_reference.npy by tests/golden/make_chi2_fixture.py."""
+    vals = np.load(os.path.join(os.path.dirname(__file__), "golden", "chi2inv95_reference.npy")).tolist()
     here = open(os.path.join(os.path.dirname(__file__), "..", "oracle", "chi2inv95.h")).read()
     body = re.search(r"#define HV_CHI2INV95_VALUES(.*?)\nstatic", here, re.S).group(1).replace("\\", " ")
     mine = [float(x) for x in body.split(",")]
