@@ -29,7 +29,9 @@ f32p = C.POINTER(C.c_float)
 f64p = C.POINTER(C.c_double)
 
 HV_MAX_LEVELS = 6
-K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI = range(12)
+(K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI,
+ K_SUBPIX) = range(13)
+SUBPIX_MAX_WIN = 16
 
 # tracker::Feature::Status (src/tracker/track.hpp:9-21)
 ST_TRACKED, ST_NEW, ST_FAILED_FLOW, ST_RANSAC_OUTLIER, ST_FLOW_OUT_OF_RANGE = 0, 1, 2, 3, 4
@@ -54,6 +56,10 @@ class EkfParams(C.Structure):
 class GfttParams(C.Structure):
     _fields_ = [("gfttBlockSize", C.c_int), ("gfttMinDistance", C.c_double), ("gfttMinResponse", C.c_float),
                 ("maxTracks", C.c_int)]
+
+
+class SubpixParams(C.Structure):
+    _fields_ = [("subPixWindowSize", C.c_int), ("subPixMaxIter", C.c_int), ("subPixEpsilon", C.c_double)]
 
 
 class HvError(RuntimeError):
@@ -151,6 +157,10 @@ PROTOTYPES = {
                                  C.POINTER(C.c_int)]),
     "hv_gftt_keypoints_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(GfttParams), C.c_int, C.c_void_p, C.c_void_p]),
     "hv_apply_min_distance": (None, [f32p, C.POINTER(C.c_int), f32p, C.c_int, C.c_int, C.c_int]),
+    "hv_subpix_default_params": (None, [C.POINTER(SubpixParams)]),
+    "hv_corner_subpix": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_int, f32p, i32p]),
+    "hv_corner_subpix_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -395,6 +405,22 @@ class Context:
         self._chk(lib().hv_gftt_keypoints_batch_dev(self._h, C.byref(gp), n_images, C.c_void_p(slots_dev),
                                                     C.c_void_p(kp_dev)), "hv_gftt_keypoints_batch_dev")
 
+    # -- sub-pixel corner refinement --
+    def corner_subpix(self, slot: int, xy, params: "SubpixParams" = None):
+        """SubPixelAdjuster::adjust on the level-0 image of a built pyramid slot -> (refined xy [n, 2], position updates [n])."""
+        sp = params if params is not None else subpix_default_params()
+        out = np.ascontiguousarray(xy, np.float32).reshape(-1, 2).copy()
+        it = np.zeros(len(out), np.int32)
+        self._chk(lib().hv_corner_subpix(self._h, C.byref(sp), slot, len(out), _p(out, f32p), _p(it, i32p)), "hv_corner_subpix")
+        return out, it
+
+    def corner_subpix_batch_dev(self, n_sets: int, slots_dev: int, max_points: int, n_points_dev: int, xy_dev: int,
+                                iters_dev: int = 0, params: "SubpixParams" = None):
+        sp = params if params is not None else subpix_default_params()
+        self._chk(lib().hv_corner_subpix_batch_dev(self._h, C.byref(sp), n_sets, C.c_void_p(slots_dev), max_points,
+                                                   C.c_void_p(n_points_dev), C.c_void_p(xy_dev), C.c_void_p(iters_dev or None)),
+                  "hv_corner_subpix_batch_dev")
+
     # -- timers --
     def profile_enable(self, on=True):
         self._chk(lib().hv_profile_enable(self._h, int(on)), "hv_profile_enable")
@@ -411,6 +437,14 @@ class Context:
 def gftt_default_params(**over) -> GfttParams:
     p = GfttParams()
     lib().hv_gftt_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def subpix_default_params(**over) -> SubpixParams:
+    p = SubpixParams()
+    lib().hv_subpix_default_params(C.byref(p))
     for k, v in over.items():
         setattr(p, k, v)
     return p

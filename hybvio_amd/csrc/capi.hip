@@ -399,6 +399,7 @@ void hv_destroy(hv_ctx *h)
     if (c->d_ingest_stage) (void)hipFree(c->d_ingest_stage);
     if (c->d_ransac_stage) (void)hipFree(c->d_ransac_stage);
     if (c->d_ransac_split) (void)hipFree(c->d_ransac_split);
+    if (c->d_subpix_stage) (void)hipFree(c->d_subpix_stage);
     for (int k = 0; k < HV_INGEST_CAMERAS; ++k)
         if (c->d_tile_box[k]) (void)hipFree(c->d_tile_box[k]);
     for (int k = 0; k < HV_INGEST_CAMERAS; ++k)

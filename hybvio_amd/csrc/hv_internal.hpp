@@ -116,6 +116,8 @@ struct Ctx {
     size_t ingest_stage_bytes = 0;
     unsigned char *d_ransac_stage = nullptr;   // staging of the host-pointer rotation-RANSAC entry (f4)
     size_t ransac_stage_bytes = 0;
+    unsigned char *d_subpix_stage = nullptr;   // points + update counts of the host-pointer sub-pixel entry (subpix.hip)
+    size_t subpix_stage_bytes = 0;
     unsigned char *d_ransac_split = nullptr;   // records of the split rotation-RANSAC launches (rot_ransac.hip), ransac_split_sets of them
     int ransac_split_sets = 0;
     std::string last_error;

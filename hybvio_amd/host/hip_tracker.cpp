@@ -44,6 +44,7 @@ ImagePyramid::~ImagePyramid() = default;
 ImagePyramid::Factory::~Factory() = default;
 OpticalFlow::~OpticalFlow() = default;
 FeatureDetector::~FeatureDetector() = default;
+SubPixelAdjuster::~SubPixelAdjuster() = default;
 Undistorter::~Undistorter() = default;
 rot_ransac::RotRansac::~RotRansac() = default;
 
@@ -195,6 +196,21 @@ public:
     }
 };
 
+// Counterpart of SubPixelAdjusterImplementation (src/tracker/subpixel_adjuster.cpp:9-42): cornerSubPix and the revert of
+// points outside the image both run inside hv_corner_subpix, on level 0 of the frame's pyramid.
+class HipSubPixelAdjuster : public SubPixelAdjuster {
+    Session &session;
+    const hv_subpix_params parameters;
+public:
+    HipSubPixelAdjuster(Session &s, const hv_subpix_params &p) : session(s), parameters(p) {}
+    void adjust(ImagePyramid &imagePyramid, std::vector<Feature::Point> &corners) final {
+        if (corners.empty()) return;                                       // subpixel_adjuster.cpp:21-23
+        static_assert(sizeof(Feature::Point) == 2 * sizeof(float), "Point must be two packed floats");
+        session.check(hv_corner_subpix(session.ctx(), &parameters, imagePyramid.deviceSlot(), (int)corners.size(),
+                                        reinterpret_cast<float *>(corners.data()), nullptr), "hv_corner_subpix");
+    }
+};
+
 }  // namespace
 
 namespace {
@@ -245,6 +261,11 @@ std::unique_ptr<Undistorter> Undistorter::buildRectifiedHip(Session &s, int came
 std::unique_ptr<FeatureDetector> FeatureDetector::buildHip(Session &s, const hv_gftt_params &p)
 {
     return std::unique_ptr<FeatureDetector>(new HipFeatureDetector(s, p));
+}
+
+std::unique_ptr<SubPixelAdjuster> SubPixelAdjuster::buildHip(Session &s, const hv_subpix_params &p)
+{
+    return std::unique_ptr<SubPixelAdjuster>(new HipSubPixelAdjuster(s, p));
 }
 
 std::unique_ptr<ImagePyramid::Factory> ImagePyramid::Factory::buildHip(Session &s)

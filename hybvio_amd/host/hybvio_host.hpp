@@ -4,6 +4,7 @@
 //   tracker::ImagePyramid / ImagePyramid::Factory   src/tracker/image_pyramid.hpp:18-43
 //   tracker::OpticalFlow                            src/tracker/optical_flow.hpp:20-40
 //   tracker::Feature::{Point,Status}                src/tracker/track.hpp:8-32
+//   tracker::SubPixelAdjuster                       src/tracker/subpixel_adjuster.hpp:10-15
 //   odometry::EKF                                   src/odometry/ekf.hpp:62-174
 //
 // Same class and method names, argument order and meaning, ownership (factories return unique_ptr,
@@ -193,6 +194,16 @@ public:
 protected:
     explicit FeatureDetector(const hv_gftt_params &parameters) : parameters(parameters) {}
     const hv_gftt_params parameters;
+};
+
+// tracker::SubPixelAdjuster (src/tracker/subpixel_adjuster.hpp:10-15): cv::cornerSubPix on the detected corners, refined
+// points outside the image reverted to their input (subpixel_adjuster.cpp:18-42). Like the HIP detector it takes the frame's
+// device pyramid instead of the CPU image, so findKeypoints never brings the frame back to the host.
+class SubPixelAdjuster {
+public:
+    static std::unique_ptr<SubPixelAdjuster> buildHip(Session &session, const hv_subpix_params &parameters);   // sibling of build()
+    virtual ~SubPixelAdjuster();
+    virtual void adjust(ImagePyramid &imagePyramid, std::vector<Feature::Point> &corners) = 0;
 };
 
 // tracker::rot_ransac::RotRansac (src/tracker/rot_ransac.hpp:14-41), SURVEY.md 8(f) row f4. Same members and call:

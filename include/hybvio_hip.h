@@ -1,7 +1,7 @@
 /*
  * hybvio_hip.h -- C ABI of libhybvio_hip.so: the MI355X (gfx950) implementation of HybVIO's
  * per-frame hot path (image pyramid + pyramidal Lucas-Kanade tracker + EKF covariance algebra) and of
- * its GFTT feature detector.
+ * its GFTT feature detector with the detector's sub-pixel corner refinement.
  *
  * Plain pointers and sizes only; no C++/torch types cross this boundary. Every entry point
  * returns HV_OK (0) or a negative hv_status; nothing throws. All device work of one hv_ctx is
@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HV_ABI_VERSION 4   /* 4 (r05): host-pointer forms of the r04 frame entries (hv_ekf_visual_frame_batch, hv_ekf_visual_track_hybrid, hv_ekf_symmetrize_augment), hv_ekf_insert_map_point / hv_ekf_get_map_point; 3 (r04): hv_lanes_*, hv_get_stream; 2 (r03): hv_debug_*_knob, hv_ekf_frame_error, HV_ERR_TIMEOUT; maxSuccessfulVisualUpdates <= 0 = no limit */
+#define HV_ABI_VERSION 4   /* 4 (r05; later additions within 4: hv_subpix_default_params, hv_corner_subpix, hv_corner_subpix_batch_dev, HV_K_SUBPIX): host-pointer forms of the r04 frame entries (hv_ekf_visual_frame_batch, hv_ekf_visual_track_hybrid, hv_ekf_symmetrize_augment), hv_ekf_insert_map_point / hv_ekf_get_map_point; 3 (r04): hv_lanes_*, hv_get_stream; 2 (r03): hv_debug_*_knob, hv_ekf_frame_error, HV_ERR_TIMEOUT; maxSuccessfulVisualUpdates <= 0 = no limit */
 #define HV_MAX_LEVELS 6
 
 typedef enum hv_status {
@@ -423,6 +423,29 @@ int hv_gftt_keypoints_batch_dev(hv_ctx *ctx, const hv_gftt_params *p, int n_imag
 void hv_apply_min_distance(float *corners_xy, int *n_inout, const float *prev_xy, int n_prev, int r,
                            int max_tracks);
 
+/* ---- sub-pixel corner refinement (added within ABI 4) ----------------------------------------
+ * Replaces tracker::SubPixelAdjuster::adjust (src/tracker/subpixel_adjuster.cpp:18-42): cv::cornerSubPix(image, corners,
+ * Size(win, win), Size(-1, -1), TermCriteria(COUNT | EPS, maxIter, epsilon)) on the level-0 image of a pyramid slot, then
+ * every refined point outside the image goes back to its input value. Bit-identical to OpenCV 4.x's float / double
+ * evaluation order (restated in tests/subpix_restatement.py). Field names are the reference's parameters
+ * (codegen/parameter_definitions.c:328-332). The reference builds no adjuster when subPixMaxIter <= 0 (image.cpp:54);
+ * these entries clamp it to one iteration, as cornerSubPix does, and leave that choice to the caller.
+ * HV_ERR_INVALID: window < 1, or the image is smaller than 2 * win + 5 in either dimension (where OpenCV asserts);
+ * HV_ERR_UNSUPPORTED: window > HV_SUBPIX_MAX_WIN (the kernel keeps the (2 win + 1)^2 gradient terms of a corner in LDS).
+ * An input point outside [0, w) x [0, h) (OpenCV asserts on it) is returned unchanged with 0 updates. */
+#define HV_SUBPIX_MAX_WIN 16
+typedef struct hv_subpix_params { int subPixWindowSize; int subPixMaxIter; double subPixEpsilon; } hv_subpix_params;
+void hv_subpix_default_params(hv_subpix_params *p);            /* 10, 20, 0.03 (parameter_definitions.c:328-332) */
+/* SubPixelAdjuster::adjust on level 0 of `slot`: xy [n][2] in/out; iters [n] (NULL ok) = position updates applied (0 after an
+ * immediate det break). n == 0 returns HV_OK after the argument checks. Synchronous. */
+int hv_corner_subpix(hv_ctx *ctx, const hv_subpix_params *p, int slot, int n, float *xy, int *iters);
+/* n_sets independent point lists, xy_dev [n_sets][max_points][2] in place, n_points_dev [n_sets] (<= max_points; larger values
+ * are clamped), slots_dev [n_sets], iters_dev [n_sets][max_points] or NULL; asynchronous on the context stream, no allocation or
+ * synchronisation inside (capturable in a HIP graph). A set whose slot is not a valid slot index is left untouched.
+ * n_sets <= 65535 (HV_ERR_UNSUPPORTED beyond). */
+int hv_corner_subpix_batch_dev(hv_ctx *ctx, const hv_subpix_params *p, int n_sets, const int *slots_dev, int max_points,
+                               const int *n_points_dev, float *xy_dev, int *iters_dev);
+
 /* ---- image ingest --------------------------------------------------
  * Replaces the per-frame work of tracker::Image::Factory::build / buildStereo (src/tracker/image.cpp:272-306):
  * the colour -> gray copy (image.cpp:351-367, coefficients 0.299 / 0.587 / 0.114 on channels 0, 1, 2) and
@@ -495,7 +518,8 @@ int hv_rot_ransac_lk_batch_dev(hv_ctx *ctx, int n_sets, int max_points, const in
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
        HV_K_VU_TRI = 11 /* r06: the triangulation front of the split form (vu_tri_kernel); HV_K_VU_PREPARE then times the record-fed gates */,
-       HV_K_COUNT = 12 };
+       HV_K_SUBPIX = 12 /* added within ABI 4: hv_corner_subpix* */,
+       HV_K_COUNT = 13 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
 /* Synchronizes, then returns accumulated device milliseconds and launch count of a kernel class. */
