@@ -30,7 +30,10 @@ f64p = C.POINTER(C.c_double)
 
 HV_MAX_LEVELS = 6
 (K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI,
- K_SUBPIX) = range(13)
+ K_SUBPIX, K_RANSAC5) = range(14)
+RANSAC5_MAX_ITERS = 75
+# RansacResult::Type as reported by hv_hybrid_ransac_lk_batch_dev
+R5_TYPE_SKIPPED, R5_TYPE_R2, R5_TYPE_R5 = 0, 1, 3
 SUBPIX_MAX_WIN = 16
 
 # tracker::Feature::Status (src/tracker/track.hpp:9-21)
@@ -60,6 +63,12 @@ class GfttParams(C.Structure):
 
 class SubpixParams(C.Structure):
     _fields_ = [("subPixWindowSize", C.c_int), ("subPixMaxIter", C.c_int), ("subPixEpsilon", C.c_double)]
+
+
+class Ransac5Params(C.Structure):
+    _fields_ = [("ransac5Prob", C.c_double), ("ransac5Threshold", C.c_double), ("ransacMaxIters", C.c_int),
+                ("ransac2InliersToSkipRansac5", C.c_double), ("ransacMinInlierFraction", C.c_double),
+                ("ransac2InliersOverRansac5Needed", C.c_double)]
 
 
 class HvError(RuntimeError):
@@ -161,6 +170,10 @@ PROTOTYPES = {
     "hv_corner_subpix": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_int, f32p, i32p]),
     "hv_corner_subpix_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "hv_ransac5_default_params": (None, [C.POINTER(Ransac5Params)]),
+    "hv_ransac5": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int] + [C.c_void_p] * 7),
+    "hv_ransac5_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "hv_hybrid_ransac_lk_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int, C.c_int] + [C.c_void_p] * 12),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -311,6 +324,35 @@ class Context:
                                                    float(threshold_pow2), p(status_dev), p(R_dev), p(summary_dev)),
                   "hv_rot_ransac_lk_batch_dev")
 
+    # ---- five-point RANSAC and the hybrid RANSAC2 / RANSAC5 filter ----
+    def ransac5(self, c1, c2, cam1: "CameraModel", cam2: "CameraModel", params: "Ransac5Params" = None):
+        """hv_ransac5 (doRansac5): returns (status [n] 0 / 3, E [9], summary [inliers, best iteration, iterations, valid])."""
+        rp = params if params is not None else ransac5_default_params()
+        a, b = np.ascontiguousarray(c1, np.float32).reshape(-1, 2), np.ascontiguousarray(c2, np.float32).reshape(-1, 2)
+        st, E, sm = np.zeros(len(a), np.int32), np.zeros(9), np.zeros(4, np.int32)
+        vp = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(lib().hv_ransac5(self._h, C.byref(rp), len(a), vp(a), vp(b), C.byref(cam1), C.byref(cam2), vp(st), vp(E), vp(sm)),
+                  "hv_ransac5")
+        return st, E, sm
+
+    def ransac5_batch_dev(self, n_sets, max_points, n_points_dev, c1_dev, c2_dev, cam1, cam2, status_dev, E_dev=0, summary_dev=0,
+                          params: "Ransac5Params" = None):
+        rp = params if params is not None else ransac5_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_ransac5_batch_dev(self._h, C.byref(rp), n_sets, max_points, p(n_points_dev), p(c1_dev), p(c2_dev),
+                                             C.byref(cam1), C.byref(cam2), p(status_dev), p(E_dev), p(summary_dev)),
+                  "hv_ransac5_batch_dev")
+
+    def hybrid_ransac_lk_batch_dev(self, n_sets, max_points, n_points_dev, c1_dev, c2_dev, track_status_dev, r2_status_dev,
+                                   r2_summary_dev, cam1, cam2, result_dev, score_dev, E_dev=0, r5_summary_dev=0,
+                                   params: "Ransac5Params" = None):
+        rp = params if params is not None else ransac5_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_hybrid_ransac_lk_batch_dev(self._h, C.byref(rp), n_sets, max_points, p(n_points_dev), p(c1_dev), p(c2_dev),
+                                                      p(track_status_dev), p(r2_status_dev), p(r2_summary_dev), C.byref(cam1),
+                                                      C.byref(cam2), p(result_dev), p(score_dev), p(E_dev), p(r5_summary_dev)),
+                  "hv_hybrid_ransac_lk_batch_dev")
+
     # ---- image ingest (f2): colour -> gray and the undistort / rectify remap in front of the pyramid ----
     def ingest_set_undistort_map(self, camera: int, pix_orig=None, valid=None):
         """pix_orig (h, w, 2) f64 = original-image position of every rectified pixel (None removes the table)."""
@@ -437,6 +479,14 @@ class Context:
 def gftt_default_params(**over) -> GfttParams:
     p = GfttParams()
     lib().hv_gftt_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def ransac5_default_params(**over) -> Ransac5Params:
+    p = Ransac5Params()
+    lib().hv_ransac5_default_params(C.byref(p))
     for k, v in over.items():
         setattr(p, k, v)
     return p

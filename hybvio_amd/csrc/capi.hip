@@ -334,6 +334,7 @@ static int create_ctx(const hv_params *params, int high_priority, hv_ctx **out)
         rc = hv::ensure_point_staging(c, p.max_tracks);
         if (rc == HV_OK) rc = hv::fill_gradient_borders(c, 0, p.pool_size);
         if (rc == HV_OK) rc = hv::rot_ransac_alloc_split(c);     // (r05 advisor: once, here -- never inside a launch that may be under capture)
+        if (rc == HV_OK) rc = hv::ransac5_init(c);
     } while (0);
     if (rc != HV_OK) { hv_destroy(h); return rc; }
     *out = h;
@@ -400,6 +401,7 @@ void hv_destroy(hv_ctx *h)
     if (c->d_ransac_stage) (void)hipFree(c->d_ransac_stage);
     if (c->d_ransac_split) (void)hipFree(c->d_ransac_split);
     if (c->d_subpix_stage) (void)hipFree(c->d_subpix_stage);
+    if (c->d_r5_stage) (void)hipFree(c->d_r5_stage);
     for (int k = 0; k < HV_INGEST_CAMERAS; ++k)
         if (c->d_tile_box[k]) (void)hipFree(c->d_tile_box[k]);
     for (int k = 0; k < HV_INGEST_CAMERAS; ++k)

@@ -116,6 +116,8 @@ struct Ctx {
     size_t ingest_stage_bytes = 0;
     unsigned char *d_ransac_stage = nullptr;   // staging of the host-pointer rotation-RANSAC entry (f4)
     size_t ransac_stage_bytes = 0;
+    unsigned char *d_r5_stage = nullptr;       // points, statuses, E and summary of the host-pointer five-point entry (ransac5.hip)
+    size_t r5_stage_bytes = 0;
     unsigned char *d_subpix_stage = nullptr;   // points + update counts of the host-pointer sub-pixel entry (subpix.hip)
     size_t subpix_stage_bytes = 0;
     unsigned char *d_ransac_split = nullptr;   // records of the split rotation-RANSAC launches (rot_ransac.hip), ransac_split_sets of them
@@ -211,6 +213,7 @@ struct VuPrepareArgs {
 };
 // doubles per factor record of vu_tri_kernel for tracks of up to np poses on ncam cameras
 inline int vu_tri_rec_stride(int np, int ncam) { return 17 * np * ncam + 21 * np + 4; }
+int ransac5_init(Ctx *c);              // ransac5.hip: the kernel's dynamic-LDS limit, set once per context
 int rot_ransac_alloc_split(Ctx *c);     // rot_ransac.hip: the split form's record buffer, allocated and zeroed once per context
 int launch_vu_tri(Ctx *c, const VuPrepareArgs &a, hipStream_t stream = nullptr);       // the triangulation front of the split form
 bool vu_split_supported(const Ctx *c, const VuPrepareArgs &a, int fused);              // shapes the record-fed gate builds serve

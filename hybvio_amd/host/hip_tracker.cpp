@@ -1,7 +1,9 @@
 // HIP-backed tracker::ImagePyramid::Factory and tracker::OpticalFlow (see hybvio_host.hpp).
 // Counterparts of CpuImagePyramidFactory (src/tracker/image_pyramid.cpp:27-49) and
 // OpenCvOpticalFlow (src/tracker/optical_flow.cpp:61-103).
+#include <algorithm>
 #include <cassert>
+#include <cmath>
 #include <cstdio>
 #include <stdexcept>
 
@@ -47,6 +49,7 @@ FeatureDetector::~FeatureDetector() = default;
 SubPixelAdjuster::~SubPixelAdjuster() = default;
 Undistorter::~Undistorter() = default;
 rot_ransac::RotRansac::~RotRansac() = default;
+RansacPipeline::~RansacPipeline() = default;
 
 void FeatureDetector::applyMinDistance(std::vector<Feature::Point> &corners, const std::vector<Feature::Point> &prevCorners,
                                        int minDistance) const
@@ -250,6 +253,125 @@ public:
 std::unique_ptr<rot_ransac::RotRansac> rot_ransac::RotRansac::buildHip(Session &s)
 {
     return std::unique_ptr<rot_ransac::RotRansac>(new HipRotRansac(s));
+}
+
+namespace {
+// Counterpart of RansacPipelineImplementation (src/tracker/ransac_pipeline.cpp:43-151) on its RANSAC2 and hybrid paths.
+class HipRansacPipeline : public RansacPipeline {
+    Session &session;
+    const RansacPipelineParameters parameters;
+    std::mt19937 rng;
+    std::unique_ptr<rot_ransac::RotRansac> rotRansac;
+    RansacResult ransacResult, ransac2Result, ransac5Result;
+    std::vector<Feature::Point> c1, c2;
+    std::vector<int> status5;
+
+    static void initialize(RansacResult &r, std::size_t n) {                 // RansacResult::initialize (:20-27)
+        r.type = RansacResult::Type::SKIPPED;
+        r.inlierCount = 0;
+        r.inliers.assign(n, Feature::Status::RANSAC_OUTLIER);
+        r.R.fill(0.0);
+        r.t.fill(0.0);
+    }
+
+    static void updateTrackStatus(const RansacResult &r, std::vector<Feature::Status> &trackStatus) {   // :29-40
+        if (r.type == RansacResult::Type::SKIPPED) return;
+        std::size_t j = 0;
+        for (auto &st : trackStatus) {
+            if (st != Feature::Status::TRACKED) continue;
+            if (r.inliers.at(j) != Feature::Status::TRACKED) st = Feature::Status::RANSAC_OUTLIER;
+            j++;
+        }
+        assert(j == r.inliers.size());
+    }
+
+    bool doRansac2(const hv_camera_model &camera1, const hv_camera_model &camera2) {   // :197-216
+        const std::size_t n = c1.size();
+        initialize(ransac2Result, n);
+        if (n < 2) return false;
+        const std::array<float, 9> R = rotRansac->fit(c1, c2, camera1, camera2, ransac2Result.inliers, rng);
+        for (int k = 0; k < 9; ++k) ransac2Result.R[k] = R[k];
+        ransac2Result.inlierCount = rotRansac->bestInlierCount;
+        ransac2Result.type = RansacResult::Type::R2;
+        return true;
+    }
+
+    bool doRansac5(const hv_camera_model &camera1, const hv_camera_model &camera2) {   // :274-397 (non-Theia)
+        const std::size_t n = c1.size();
+        initialize(ransac5Result, n);
+        if (n < 5) return false;
+        status5.assign(n, 3);
+        double E[9];
+        int summary[4];
+        static_assert(sizeof(Feature::Point) == 2 * sizeof(float), "Point must be two packed floats");
+        session.check(hv_ransac5(session.ctx(), &parameters.ransac5, static_cast<int>(n), reinterpret_cast<const float *>(c1.data()),
+                                 reinterpret_cast<const float *>(c2.data()), &camera1, &camera2, status5.data(), E, summary),
+                      "hv_ransac5");
+        if (summary[3] < 5) return false;                                    // fewer than 5 valid points (:344)
+        for (std::size_t i = 0; i < n; ++i) ransac5Result.inliers[i] = static_cast<Feature::Status>(status5[i]);
+        ransac5Result.inlierCount = static_cast<std::size_t>(summary[0]);
+        ransac5Result.type = RansacResult::Type::R5;
+        return true;
+    }
+
+    void computeHybridRansac(const hv_camera_model &camera1, const hv_camera_model &camera2, bool ransac2Done) {   // :158-195
+        const auto &p = parameters.ransac5;
+        const std::size_t n = c1.size();
+        const bool useRansac2Inliers = ransac2Result.inlierCount > p.ransac2InliersToSkipRansac5 * n;
+        bool ransac5Done = !useRansac2Inliers && doRansac5(camera1, camera2);
+        const double f5 = static_cast<double>(ransac5Result.inlierCount) / static_cast<double>(n);
+        const double f2 = static_cast<double>(ransac2Result.inlierCount) / static_cast<double>(n);
+        if (f5 < p.ransacMinInlierFraction) ransac5Done = false;
+        if (f2 < p.ransacMinInlierFraction) ransac2Done = false;
+        if (ransac2Done && !ransac5Done) ransacResult = ransac2Result;
+        else if (ransac5Done && !ransac2Done) ransacResult = ransac5Result;
+        else if (ransac2Done && ransac5Done)
+            ransacResult = (useRansac2Inliers || ransac2Result.inlierCount > p.ransac2InliersOverRansac5Needed * ransac5Result.inlierCount)
+                               ? ransac2Result : ransac5Result;
+        else ransacResult = RansacResult();
+    }
+
+public:
+    HipRansacPipeline(Session &s, int width, int height, const RansacPipelineParameters &p)
+        : session(s), parameters(p), rng(p.ransacRngSeed), rotRansac(rot_ransac::RotRansac::buildHip(s)) {
+        const double su = std::min(height, width) / 720.0;                   // :91-93
+        rotRansac->threshold_pow2 = static_cast<float>(std::pow(p.ransac2Threshold * su, 2));
+    }
+
+    double compute(const std::vector<std::array<const hv_camera_model *, 2>> &cameras,
+                   const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners, const void *,
+                   std::vector<Feature::Status> &trackStatus) final {
+        assert(!cameras.empty() && !corners.empty());
+        c1.clear();
+        c2.clear();
+        for (std::size_t i = 0; i < trackStatus.size(); i++) {             // :106-112
+            if (trackStatus[i] != Feature::Status::TRACKED) continue;
+            c1.push_back((*corners[0][0])[i]);
+            c2.push_back((*corners[0][1])[i]);
+        }
+        const std::size_t n = c1.size();
+        const bool ransac2Done = doRansac2(*cameras[0][0], *cameras[0][1]);
+        if (!parameters.useHybridRansac) return ransac2Result.inlierCount / static_cast<double>(n);   // :133-135
+        computeHybridRansac(*cameras[0][0], *cameras[0][1], ransac2Done);
+        if (ransacResult.type != RansacResult::Type::SKIPPED) updateTrackStatus(ransacResult, trackStatus);
+        else
+            for (auto &st : trackStatus) st = Feature::Status::RANSAC_OUTLIER;   // :139-144
+        if (n == 0) return 0.0;
+        return ransac2Result.inlierCount / static_cast<double>(n);
+    }
+
+    const RansacResult &lastResult() const final { return ransacResult; }
+};
+}  // namespace
+
+std::unique_ptr<RansacPipeline> RansacPipeline::buildHip(Session &s, int width, int height, const RansacPipelineParameters &p)
+{
+    if (p.useRansac3)
+        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useRansac3 (Theia P3P RANSAC) is not implemented on the device; "
+                                    "set useRansac3 false to use the hybrid RANSAC2 / RANSAC5 path");
+    if (p.useStereoUpright2p)
+        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useStereoUpright2p is not implemented on the device");
+    return std::unique_ptr<RansacPipeline>(new HipRansacPipeline(s, width, height, p));
 }
 
 std::unique_ptr<Undistorter> Undistorter::buildRectifiedHip(Session &s, int cameraIndex, std::shared_ptr<const Camera> rectified)

@@ -5,6 +5,7 @@
 //   tracker::OpticalFlow                            src/tracker/optical_flow.hpp:20-40
 //   tracker::Feature::{Point,Status}                src/tracker/track.hpp:8-32
 //   tracker::SubPixelAdjuster                       src/tracker/subpixel_adjuster.hpp:10-15
+//   tracker::RansacPipeline / RansacResult          src/tracker/ransac_pipeline.hpp:15-45, ransac_result.hpp:9-33
 //   odometry::EKF                                   src/odometry/ekf.hpp:62-174
 //
 // Same class and method names, argument order and meaning, ownership (factories return unique_ptr,
@@ -226,6 +227,46 @@ public:
     float threshold_pow2 = 2.0f * 2.0f;      // "Likely set later with information of the frame size." (rot_ransac.cpp:164)
 };
 }  // namespace rot_ransac
+
+// tracker::RansacResult (src/tracker/ransac_result.hpp:9-33). R / t are the cv::Matx33d / Matx31d, row-major; RANSAC5 leaves
+// both zero (ransac_pipeline.cpp:375-380), RANSAC2 fills R with its rotation.
+struct RansacResult {
+    enum class Type : std::uint8_t { SKIPPED = 0, R2 = 1, R3 = 2, R5 = 3, UPRIGHT_2P = 4 };
+    Type type = Type::SKIPPED;
+    std::size_t inlierCount = 0;
+    std::array<double, 9> R{};
+    std::array<double, 3> t{};
+    std::vector<Feature::Status> inliers;
+};
+
+// The tracker.* parameters RansacPipeline reads (codegen/parameter_definitions.c:268-305).
+struct RansacPipelineParameters {
+    bool useHybridRansac = true;
+    bool useRansac3 = true;                  // the reference's default; buildHip refuses it (Theia P3P is not implemented)
+    bool useStereoUpright2p = false;         // refused as well
+    double ransac2Threshold = 4.0;
+    unsigned ransacRngSeed = 4649;
+    hv_ransac5_params ransac5{0.999, 2.0, 75, 0.9, 0.3, 0.9};
+};
+
+// tracker::RansacPipeline (src/tracker/ransac_pipeline.hpp:15-45) on the hybrid path (ransac_pipeline.cpp:95-195): RANSAC2
+// through RotRansac::buildHip with the pipeline's own std::mt19937(ransacRngSeed), then hv_ransac5 unless RANSAC2 already
+// explains more than ransac2InliersToSkipRansac5 of the tracks, the hybrid choice and the status rewrite. With
+// useHybridRansac false compute() only runs RANSAC2 and returns its score, as the reference does. buildHip throws
+// std::invalid_argument when the parameters ask for RANSAC3 or the upright 2-point solver. The cameras are
+// hv_camera_model descriptions of cameras[i][0 / 1]; poses are not used on these paths and may be null.
+class RansacPipeline {
+public:
+    static std::unique_ptr<RansacPipeline> buildHip(Session &session, int imageWidth, int imageHeight,
+                                                    const RansacPipelineParameters &parameters);
+    virtual ~RansacPipeline();
+    virtual double compute(
+        const std::vector<std::array<const hv_camera_model *, 2>> &cameras,
+        const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners,
+        const void *poses,
+        std::vector<Feature::Status> &trackStatus) = 0;
+    virtual const RansacResult &lastResult() const = 0;
+};
 
 }  // namespace tracker
 

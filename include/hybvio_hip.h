@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HV_ABI_VERSION 4   /* 4 (r05; later additions within 4: hv_subpix_default_params, hv_corner_subpix, hv_corner_subpix_batch_dev, HV_K_SUBPIX): host-pointer forms of the r04 frame entries (hv_ekf_visual_frame_batch, hv_ekf_visual_track_hybrid, hv_ekf_symmetrize_augment), hv_ekf_insert_map_point / hv_ekf_get_map_point; 3 (r04): hv_lanes_*, hv_get_stream; 2 (r03): hv_debug_*_knob, hv_ekf_frame_error, HV_ERR_TIMEOUT; maxSuccessfulVisualUpdates <= 0 = no limit */
+#define HV_ABI_VERSION 4   /* 4 (r05; later additions within 4: hv_subpix_default_params, hv_corner_subpix, hv_corner_subpix_batch_dev, HV_K_SUBPIX; hv_ransac5_default_params, hv_ransac5, hv_ransac5_batch_dev, hv_hybrid_ransac_lk_batch_dev, HV_K_RANSAC5): host-pointer forms of the r04 frame entries (hv_ekf_visual_frame_batch, hv_ekf_visual_track_hybrid, hv_ekf_symmetrize_augment), hv_ekf_insert_map_point / hv_ekf_get_map_point; 3 (r04): hv_lanes_*, hv_get_stream; 2 (r03): hv_debug_*_knob, hv_ekf_frame_error, HV_ERR_TIMEOUT; maxSuccessfulVisualUpdates <= 0 = no limit */
 #define HV_MAX_LEVELS 6
 
 typedef enum hv_status {
@@ -514,12 +514,62 @@ int hv_rot_ransac_lk_batch_dev(hv_ctx *ctx, int n_sets, int max_points, const in
                                const hv_camera_model *camera1, const hv_camera_model *camera2, const uint32_t *draws_dev,
                                float threshold_pow2, int *status_dev, float *R_dev, int *summary_dev);
 
+/* ---- five-point essential-matrix RANSAC and the hybrid RANSAC2 / RANSAC5 filter (added within ABI 4) ---------------
+ * Replaces doRansac5 without Theia (src/tracker/ransac_pipeline.cpp:274-397): Camera::normalizePixel of both frames
+ * (camera.cpp:471-476; failing points are outliers and take no part), threshold = 2 ransac5Threshold / (f1 + f2) with
+ * f = (fx + fy) / 2, then findEssentialMatRansacMaxIter (five_point.cpp:404-416): RANSACPointSetRegistrator::run
+ * (ptsetreg.hpp:130-220) with a fresh cv::RNG((uint64)-1), getSubset, Nister's solver (five_point.cpp:41-146), the float
+ * Sampson error (:374-400) and RANSACUpdateNumIters (ptsetreg.cpp:58-79). Equal to the numpy restatement in
+ * tests/ransac5_restatement.py; where it departs from OpenCV (null-space basis, elimination, solvePoly restated, the
+ * null vector of B(z)) see DESIGN.md. Fewer than 5 points or 5 valid ones: not done, every point an outlier. Exactly 5
+ * valid points: every valid point an inlier (the single kernel call decides nothing). No model ever qualifying: every
+ * valid point an inlier (the pre-filled mask survives). Field names are the reference's parameters
+ * (codegen/parameter_definitions.c:268-282). HV_ERR_UNSUPPORTED: ransacMaxIters > HV_RANSAC5_MAX_ITERS or more than
+ * 1024 points; HV_ERR_INVALID: ransac5Prob outside (0, 1) (OpenCV asserts) or ransacMaxIters < 1. The parameter and size
+ * checks come before the context is looked at. */
+#define HV_RANSAC5_MAX_ITERS 75
+typedef struct hv_ransac5_params {
+    double ransac5Prob; double ransac5Threshold; int ransacMaxIters;
+    double ransac2InliersToSkipRansac5; double ransacMinInlierFraction; double ransac2InliersOverRansac5Needed;
+} hv_ransac5_params;
+void hv_ransac5_default_params(hv_ransac5_params *p);   /* 0.999, 2.0, 75, 0.9, 0.3, 0.9 (parameter_definitions.c:270-282) */
+/* doRansac5 on one set of n points (c1 = previous, c2 = current frame pixels, camera1 / camera2 = cameras[0][0] /
+ * cameras[0][1]): status[n] 0 TRACKED / 3 RANSAC_OUTLIER, E[9] (row-major, unit norm; zeros without a model; NULL ok),
+ * summary[4] (NULL ok) = {inlier count, iteration of the best model (-1: none), iterations run, valid points}.
+ * Synchronous. */
+int hv_ransac5(hv_ctx *ctx, const hv_ransac5_params *p, int n, const float *c1_xy, const float *c2_xy,
+               const hv_camera_model *camera1, const hv_camera_model *camera2, int *status, double *E, int *summary);
+/* n_sets sets in device memory: set s = n_points_dev[s] <= max_points (<= 1024) points at c*_dev + s * max_points * 2;
+ * status_dev [n_sets][max_points], E_dev [n_sets][9] and summary_dev [n_sets][4] as above (E / summary NULL ok).
+ * Asynchronous on the context stream, no allocation or synchronisation inside (capturable in a HIP graph).
+ * n_sets <= 65535. */
+int hv_ransac5_batch_dev(hv_ctx *ctx, const hv_ransac5_params *p, int n_sets, int max_points, const int *n_points_dev,
+                         const float *c1_dev, const float *c2_dev, const hv_camera_model *camera1,
+                         const hv_camera_model *camera2, int *status_dev, double *E_dev, int *summary_dev);
+/* The mono device chain step after hv_rot_ransac_lk_batch_dev: RansacPipeline::compute on the hybrid path
+ * (ransac_pipeline.cpp:95-151, 158-195). Set s = the features of LK pair s: c1 / c2 as for hv_rot_ransac_lk_batch_dev,
+ * track_status_dev [n_sets][max_points] int32 Feature::Status (TRACKED = 0 selects the set, in feature order),
+ * r2_status_dev / r2_summary_dev = the status_dev / summary_dev of hv_rot_ransac_lk_batch_dev on the same set.
+ * RANSAC5 runs unless RANSAC2's bestInlierCount > ransac2InliersToSkipRansac5 * n; the selection follows :174-194.
+ * track_status_dev is rewritten at the original feature numbers: the chosen result's outliers -> 3 (updateTrackStatus,
+ * :29-40); SKIPPED -> every entry < n_points_dev[s] becomes 3 (:139-144). result_dev [n_sets][2] = {type 0 SKIPPED /
+ * 1 R2 / 3 R5, inlierCount}, score_dev [n_sets] = RANSAC2 inliers / n (0 when n == 0), the return value of compute.
+ * E_dev / r5_summary_dev (NULL ok) as for hv_ransac5_batch_dev; where RANSAC5 did not run the summary is {0, -1, 0, m}
+ * with m = the valid (normalisable) points when n >= 5 and RANSAC2 did not skip it, else m = 0.
+ * Asynchronous, capturable. */
+int hv_hybrid_ransac_lk_batch_dev(hv_ctx *ctx, const hv_ransac5_params *p, int n_sets, int max_points,
+                                  const int *n_points_dev, const float *c1_dev, const float *c2_dev, int *track_status_dev,
+                                  const int *r2_status_dev, const int *r2_summary_dev, const hv_camera_model *camera1,
+                                  const hv_camera_model *camera2, int *result_dev, double *score_dev, double *E_dev,
+                                  int *r5_summary_dev);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
        HV_K_VU_TRI = 11 /* r06: the triangulation front of the split form (vu_tri_kernel); HV_K_VU_PREPARE then times the record-fed gates */,
        HV_K_SUBPIX = 12 /* added within ABI 4: hv_corner_subpix* */,
-       HV_K_COUNT = 13 };
+       HV_K_RANSAC5 = 13 /* added within ABI 4: hv_ransac5*, hv_hybrid_ransac_lk_batch_dev */,
+       HV_K_COUNT = 14 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
 /* Synchronizes, then returns accumulated device milliseconds and launch count of a kernel class. */
