@@ -30,7 +30,7 @@ f64p = C.POINTER(C.c_double)
 
 HV_MAX_LEVELS = 6
 (K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI,
- K_SUBPIX, K_RANSAC5) = range(14)
+ K_SUBPIX, K_RANSAC5, K_STEREO_GATE) = range(15)
 RANSAC5_MAX_ITERS = 75
 # RansacResult::Type as reported by hv_hybrid_ransac_lk_batch_dev
 R5_TYPE_SKIPPED, R5_TYPE_R2, R5_TYPE_R5 = 0, 1, 3
@@ -38,6 +38,8 @@ SUBPIX_MAX_WIN = 16
 
 # tracker::Feature::Status (src/tracker/track.hpp:9-21)
 ST_TRACKED, ST_NEW, ST_FAILED_FLOW, ST_RANSAC_OUTLIER, ST_FLOW_OUT_OF_RANGE = 0, 1, 2, 3, 4
+ST_OUT_OF_RANGE, ST_FAILED_EPIPOLAR_CHECK, ST_CULLED, ST_BLACKLISTED = 5, 6, 7, 8
+DETECTION_FILTER_MAX_POINTS = 1024
 
 
 class Params(C.Structure):
@@ -69,6 +71,11 @@ class Ransac5Params(C.Structure):
     _fields_ = [("ransac5Prob", C.c_double), ("ransac5Threshold", C.c_double), ("ransacMaxIters", C.c_int),
                 ("ransac2InliersToSkipRansac5", C.c_double), ("ransacMinInlierFraction", C.c_double),
                 ("ransac2InliersOverRansac5Needed", C.c_double)]
+
+
+class StereoGateParams(C.Structure):
+    _fields_ = [("maxStereoEpipolarDistance", C.c_float), ("partOfImageToDetectFeatures", C.c_double), ("fisheyeCamera", C.c_int),
+                ("independentStereoOpticalFlow", C.c_int), ("cam0ToCam1", C.c_double * 16)]
 
 
 class HvError(RuntimeError):
@@ -174,6 +181,12 @@ PROTOTYPES = {
     "hv_ransac5": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int] + [C.c_void_p] * 7),
     "hv_ransac5_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int, C.c_int] + [C.c_void_p] * 8),
     "hv_hybrid_ransac_lk_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int, C.c_int] + [C.c_void_p] * 12),
+    "hv_stereo_gate_default_params": (None, [C.POINTER(StereoGateParams)]),
+    "hv_flow_status_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "hv_track_gate": (C.c_int, [C.c_void_p, C.POINTER(StereoGateParams), C.c_int] + [C.c_void_p] * 7),
+    "hv_track_gate_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(StereoGateParams), C.c_int, C.c_int] + [C.c_void_p] * 9),
+    "hv_detection_filter": (C.c_int, [C.c_void_p, C.POINTER(StereoGateParams), C.c_int] + [C.c_void_p] * 9),
+    "hv_detection_filter_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(StereoGateParams), C.c_int, C.c_int] + [C.c_void_p] * 10),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -353,6 +366,61 @@ class Context:
                                                       C.byref(cam2), p(result_dev), p(score_dev), p(E_dev), p(r5_summary_dev)),
                   "hv_hybrid_ransac_lk_batch_dev")
 
+    # ---- stereo track gate: flow status, epipolar check, crop, blacklist and the detection filter ----
+    def flow_status_batch_dev(self, n_sets, max_points, n_points_dev, xy_dev, lk_status_dev, status_dev):
+        """hv_flow_status_batch_dev: LK uint8 status + level-0 range test -> int32 Feature::Status, on the device."""
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_flow_status_batch_dev(self._h, n_sets, max_points, p(n_points_dev), p(xy_dev), p(lk_status_dev), p(status_dev)),
+                  "hv_flow_status_batch_dev")
+
+    def track_gate(self, corners, second_corners, stereo_status, track_status, cam0: "CameraModel", cam1: "CameraModel" = None,
+                   blacklist=None, params: "StereoGateParams" = None):
+        """hv_track_gate (tracker.cpp:441-478): returns the new int32 track statuses; second_corners None = mono."""
+        gp = params if params is not None else stereo_gate_default_params()
+        a = np.ascontiguousarray(corners, np.float32).reshape(-1, 2)
+        b = None if second_corners is None else np.ascontiguousarray(second_corners, np.float32).reshape(-1, 2)
+        ss = None if stereo_status is None else np.ascontiguousarray(stereo_status, np.int32)
+        bl = None if blacklist is None else np.ascontiguousarray(blacklist, np.uint8)
+        ts = np.array(track_status, np.int32).copy()
+        vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        self._chk(lib().hv_track_gate(self._h, C.byref(gp), len(a), vp(a), vp(b), vp(ss), vp(bl), C.byref(cam0),
+                                      C.byref(cam1) if cam1 is not None else None, vp(ts)), "hv_track_gate")
+        return ts
+
+    def track_gate_batch_dev(self, n_sets, max_points, n_points_dev, corners_dev, second_corners_dev, stereo_status_dev, blacklist_dev,
+                             cam0, cam1, track_status_dev, tracked_mask_dev=0, params: "StereoGateParams" = None):
+        gp = params if params is not None else stereo_gate_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_track_gate_batch_dev(self._h, C.byref(gp), n_sets, max_points, p(n_points_dev), p(corners_dev),
+                                                p(second_corners_dev), p(stereo_status_dev), p(blacklist_dev), C.byref(cam0),
+                                                C.byref(cam1) if cam1 is not None else None, p(track_status_dev), p(tracked_mask_dev)),
+                  "hv_track_gate_batch_dev")
+
+    def detection_filter(self, corners, second_corners, stereo_status, cam0: "CameraModel", cam1: "CameraModel" = None,
+                         params: "StereoGateParams" = None):
+        """hv_detection_filter (tracker.cpp:266-311) -> (kept corners [m, 2], kept right corners [m, 2] or None, statuses [n])."""
+        gp = params if params is not None else stereo_gate_default_params()
+        a = np.ascontiguousarray(corners, np.float32).reshape(-1, 2)
+        b = None if second_corners is None else np.ascontiguousarray(second_corners, np.float32).reshape(-1, 2)
+        ss = None if stereo_status is None else np.ascontiguousarray(stereo_status, np.int32)
+        oa, ob = np.zeros_like(a), None if b is None else np.zeros_like(b)
+        st, n = np.zeros(len(a), np.int32), C.c_int(-1)
+        vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        self._chk(lib().hv_detection_filter(self._h, C.byref(gp), len(a), vp(a), vp(b), vp(ss), C.byref(cam0),
+                                            C.byref(cam1) if cam1 is not None else None, vp(st), vp(oa), vp(ob), C.byref(n)),
+                  "hv_detection_filter")
+        return oa[:n.value].copy(), None if ob is None else ob[:n.value].copy(), st
+
+    def detection_filter_batch_dev(self, n_sets, max_points, n_points_dev, corners_dev, second_corners_dev, stereo_status_dev, cam0, cam1,
+                                   status_dev, out_corners_dev, out_second_dev, n_out_dev, params: "StereoGateParams" = None):
+        gp = params if params is not None else stereo_gate_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_detection_filter_batch_dev(self._h, C.byref(gp), n_sets, max_points, p(n_points_dev), p(corners_dev),
+                                                      p(second_corners_dev), p(stereo_status_dev), C.byref(cam0),
+                                                      C.byref(cam1) if cam1 is not None else None, p(status_dev), p(out_corners_dev),
+                                                      p(out_second_dev), p(n_out_dev)),
+                  "hv_detection_filter_batch_dev")
+
     # ---- image ingest (f2): colour -> gray and the undistort / rectify remap in front of the pyramid ----
     def ingest_set_undistort_map(self, camera: int, pix_orig=None, valid=None):
         """pix_orig (h, w, 2) f64 = original-image position of every rectified pixel (None removes the table)."""
@@ -489,6 +557,18 @@ def ransac5_default_params(**over) -> Ransac5Params:
     lib().hv_ransac5_default_params(C.byref(p))
     for k, v in over.items():
         setattr(p, k, v)
+    return p
+
+
+def stereo_gate_default_params(**over) -> StereoGateParams:
+    """hv_stereo_gate_default_params; cam0ToCam1 may be given as any 4 x 4 / 16-element array (row-major)."""
+    p = StereoGateParams()
+    lib().hv_stereo_gate_default_params(C.byref(p))
+    for k, v in over.items():
+        if k == "cam0ToCam1":
+            p.cam0ToCam1[:] = [float(x) for x in np.asarray(v, np.float64).reshape(16)]
+        else:
+            setattr(p, k, v)
     return p
 
 

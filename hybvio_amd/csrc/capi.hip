@@ -402,6 +402,7 @@ void hv_destroy(hv_ctx *h)
     if (c->d_ransac_split) (void)hipFree(c->d_ransac_split);
     if (c->d_subpix_stage) (void)hipFree(c->d_subpix_stage);
     if (c->d_r5_stage) (void)hipFree(c->d_r5_stage);
+    if (c->d_gate_stage) (void)hipFree(c->d_gate_stage);
     for (int k = 0; k < HV_INGEST_CAMERAS; ++k)
         if (c->d_tile_box[k]) (void)hipFree(c->d_tile_box[k]);
     for (int k = 0; k < HV_INGEST_CAMERAS; ++k)

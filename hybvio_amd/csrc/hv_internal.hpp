@@ -118,6 +118,8 @@ struct Ctx {
     size_t ransac_stage_bytes = 0;
     unsigned char *d_r5_stage = nullptr;       // points, statuses, E and summary of the host-pointer five-point entry (ransac5.hip)
     size_t r5_stage_bytes = 0;
+    unsigned char *d_gate_stage = nullptr;     // inputs and outputs of the host-pointer stereo-gate entries (stereo_gate.hip)
+    size_t gate_stage_bytes = 0;
     unsigned char *d_subpix_stage = nullptr;   // points + update counts of the host-pointer sub-pixel entry (subpix.hip)
     size_t subpix_stage_bytes = 0;
     unsigned char *d_ransac_split = nullptr;   // records of the split rotation-RANSAC launches (rot_ransac.hip), ransac_split_sets of them

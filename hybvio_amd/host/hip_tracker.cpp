@@ -50,6 +50,7 @@ SubPixelAdjuster::~SubPixelAdjuster() = default;
 Undistorter::~Undistorter() = default;
 rot_ransac::RotRansac::~RotRansac() = default;
 RansacPipeline::~RansacPipeline() = default;
+StereoGate::~StereoGate() = default;
 
 void FeatureDetector::applyMinDistance(std::vector<Feature::Point> &corners, const std::vector<Feature::Point> &prevCorners,
                                        int minDistance) const
@@ -372,6 +373,83 @@ std::unique_ptr<RansacPipeline> RansacPipeline::buildHip(Session &s, int width, 
     if (p.useStereoUpright2p)
         throw std::invalid_argument("RansacPipeline::buildHip: tracker.useStereoUpright2p is not implemented on the device");
     return std::unique_ptr<RansacPipeline>(new HipRansacPipeline(s, width, height, p));
+}
+
+namespace {
+class HipStereoGate : public StereoGate {
+    Session &session;
+    hv_stereo_gate_params params;
+    std::vector<std::int32_t> status, stereoStatus;
+    std::vector<std::uint8_t> blacklist;
+
+    static const float *xy(const std::vector<Feature::Point> &v) { return reinterpret_cast<const float *>(v.data()); }
+
+public:
+    HipStereoGate(Session &s, const StereoGateParameters &p, const std::array<double, 16> &cam0ToCam1) : session(s) {
+        hv_stereo_gate_default_params(&params);
+        params.maxStereoEpipolarDistance = p.maxStereoEpipolarDistance;
+        params.partOfImageToDetectFeatures = p.partOfImageToDetectFeatures;
+        params.fisheyeCamera = p.fisheyeCamera ? 1 : 0;
+        params.independentStereoOpticalFlow = p.independentStereoOpticalFlow ? 1 : 0;
+        for (int i = 0; i < 16; ++i) params.cam0ToCam1[i] = cam0ToCam1[i];
+    }
+
+    void markTrackStatus(const std::vector<Feature::Point> &corners, const std::vector<Feature::Point> *secondCorners,
+                         const std::vector<Feature::Status> *trackStatusStereo, const std::vector<Feature> &tracks,
+                         const hv_camera_model &camera0, const hv_camera_model &camera1,
+                         std::vector<Feature::Status> &trackStatus) final {
+        static_assert(sizeof(Feature::Point) == 2 * sizeof(float), "Point must be two packed floats");
+        const std::size_t n = corners.size();
+        assert(trackStatus.size() == n && tracks.size() == n);
+        assert(!secondCorners || (secondCorners->size() == n && trackStatusStereo && trackStatusStereo->size() == n));
+        if (n == 0) return;
+        status.resize(n);
+        blacklist.resize(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            status[i] = static_cast<std::int32_t>(trackStatus[i]);
+            blacklist[i] = tracks[i].status == Feature::Status::BLACKLISTED ? 1 : 0;   // tracker.cpp:473-477
+        }
+        if (secondCorners) {
+            stereoStatus.resize(n);
+            for (std::size_t i = 0; i < n; ++i) stereoStatus[i] = static_cast<std::int32_t>((*trackStatusStereo)[i]);
+        }
+        session.check(hv_track_gate(session.ctx(), &params, static_cast<int>(n), xy(corners), secondCorners ? xy(*secondCorners) : nullptr,
+                                    secondCorners ? stereoStatus.data() : nullptr, blacklist.data(), &camera0,
+                                    secondCorners ? &camera1 : nullptr, status.data()),
+                      "hv_track_gate");
+        for (std::size_t i = 0; i < n; ++i) trackStatus[i] = static_cast<Feature::Status>(status[i]);
+    }
+
+    void filterDetections(std::vector<Feature::Point> &corners, std::vector<Feature::Point> *secondCorners,
+                          const std::vector<Feature::Status> *detectionStatus, const hv_camera_model &camera0,
+                          const hv_camera_model &camera1) final {
+        const std::size_t n = corners.size();
+        assert(!secondCorners || (secondCorners->size() == n && detectionStatus && detectionStatus->size() == n));
+        if (n == 0) return;
+        if (n > HV_DETECTION_FILTER_MAX_POINTS)
+            throw std::invalid_argument("StereoGate::filterDetections: more than HV_DETECTION_FILTER_MAX_POINTS new corners");
+        if (secondCorners) {
+            stereoStatus.resize(n);
+            for (std::size_t i = 0; i < n; ++i) stereoStatus[i] = static_cast<std::int32_t>((*detectionStatus)[i]);
+        }
+        int kept = 0;
+        float *c = reinterpret_cast<float *>(corners.data());
+        float *c2 = secondCorners ? reinterpret_cast<float *>(secondCorners->data()) : nullptr;
+        session.check(hv_detection_filter(session.ctx(), &params, static_cast<int>(n), c, c2, secondCorners ? stereoStatus.data() : nullptr,
+                                          &camera0, secondCorners ? &camera1 : nullptr, nullptr, c, c2, &kept),
+                      "hv_detection_filter");
+        corners.resize(static_cast<std::size_t>(kept));                        // tracker.cpp:309-310
+        if (secondCorners) secondCorners->resize(static_cast<std::size_t>(kept));
+    }
+};
+}  // namespace
+
+std::unique_ptr<StereoGate> StereoGate::buildHip(Session &s, int width, int height, const StereoGateParameters &p,
+                                                 const std::array<double, 16> &cam0ToCam1)
+{
+    if (width != s.params().width || height != s.params().height)
+        throw std::invalid_argument("StereoGate::buildHip: width / height differ from the session's image size");
+    return std::unique_ptr<StereoGate>(new HipStereoGate(s, p, cam0ToCam1));
 }
 
 std::unique_ptr<Undistorter> Undistorter::buildRectifiedHip(Session &s, int cameraIndex, std::shared_ptr<const Camera> rectified)

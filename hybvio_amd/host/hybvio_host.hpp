@@ -6,6 +6,7 @@
 //   tracker::Feature::{Point,Status}                src/tracker/track.hpp:8-32
 //   tracker::SubPixelAdjuster                       src/tracker/subpixel_adjuster.hpp:10-15
 //   tracker::RansacPipeline / RansacResult          src/tracker/ransac_pipeline.hpp:15-45, ransac_result.hpp:9-33
+//   tracker::StereoGate (no reference class)         the status rules of src/tracker/tracker.cpp:266-311, 441-478
 //   odometry::EKF                                   src/odometry/ekf.hpp:62-174
 //
 // Same class and method names, argument order and meaning, ownership (factories return unique_ptr,
@@ -266,6 +267,39 @@ public:
         const void *poses,
         std::vector<Feature::Status> &trackStatus) = 0;
     virtual const RansacResult &lastResult() const = 0;
+};
+
+// The tracker.* parameters the stereo gate reads (codegen/parameter_definitions.c:210, 217, 246, 353).
+struct StereoGateParameters {
+    float maxStereoEpipolarDistance = 10;
+    double partOfImageToDetectFeatures = 1;
+    bool fisheyeCamera = false;
+    bool independentStereoOpticalFlow = false;
+};
+
+// The per-track status rules of TrackerImplementation, which the reference keeps inline (no class of its own):
+// markTrackStatus replaces tracker.cpp:441-478 (stereo FAILED_FLOW merge, markCornersFailedByEpipolarConstraint,
+// markOutOfDetectionCropCornersAsFailed on both images, blacklist) and filterDetections replaces :266-311 after the stereo
+// LK of new corners (epipolar check, crop marks, the stable compaction of the accepted pairs). Both go through hv_track_gate /
+// hv_detection_filter. cam0ToCam1 = secondImuToCamera * imuToCamera.inverse() (tracker.cpp:362), row-major, formed by the
+// caller with its own Eigen. width / height must be the session's (the kernels use the context's level-0 size); buildHip
+// throws std::invalid_argument otherwise. Mono: secondCorners / trackStatusStereo / detectionStatus null, camera1 unused.
+class StereoGate {
+public:
+    static std::unique_ptr<StereoGate> buildHip(Session &session, int width, int height, const StereoGateParameters &parameters,
+                                                const std::array<double, 16> &cam0ToCam1);
+    virtual ~StereoGate();
+    // corners / secondCorners: the current left / right corners; tracks: for their BLACKLISTED status; trackStatus: the left
+    // flow status on entry, the gated status on return.
+    virtual void markTrackStatus(const std::vector<Feature::Point> &corners, const std::vector<Feature::Point> *secondCorners,
+                                 const std::vector<Feature::Status> *trackStatusStereo, const std::vector<Feature> &tracks,
+                                 const hv_camera_model &camera0, const hv_camera_model &camera1,
+                                 std::vector<Feature::Status> &trackStatus) = 0;
+    // detectionStatus: the stereo flow status of the new corners (the workspace.detectionStatus of detectFeatures); corners and
+    // secondCorners keep the accepted pairs, in order, and are resized to their count.
+    virtual void filterDetections(std::vector<Feature::Point> &corners, std::vector<Feature::Point> *secondCorners,
+                                  const std::vector<Feature::Status> *detectionStatus, const hv_camera_model &camera0,
+                                  const hv_camera_model &camera1) = 0;
 };
 
 }  // namespace tracker

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HV_ABI_VERSION 4   /* 4 (r05; later additions within 4: hv_subpix_default_params, hv_corner_subpix, hv_corner_subpix_batch_dev, HV_K_SUBPIX; hv_ransac5_default_params, hv_ransac5, hv_ransac5_batch_dev, hv_hybrid_ransac_lk_batch_dev, HV_K_RANSAC5): host-pointer forms of the r04 frame entries (hv_ekf_visual_frame_batch, hv_ekf_visual_track_hybrid, hv_ekf_symmetrize_augment), hv_ekf_insert_map_point / hv_ekf_get_map_point; 3 (r04): hv_lanes_*, hv_get_stream; 2 (r03): hv_debug_*_knob, hv_ekf_frame_error, HV_ERR_TIMEOUT; maxSuccessfulVisualUpdates <= 0 = no limit */
+#define HV_ABI_VERSION 4   /* 4 (r05; later additions within 4: hv_subpix_default_params, hv_corner_subpix, hv_corner_subpix_batch_dev, HV_K_SUBPIX; hv_ransac5_default_params, hv_ransac5, hv_ransac5_batch_dev, hv_hybrid_ransac_lk_batch_dev, HV_K_RANSAC5; hv_stereo_gate_default_params, hv_flow_status_batch_dev, hv_track_gate, hv_track_gate_batch_dev, hv_detection_filter, hv_detection_filter_batch_dev, HV_K_STEREO_GATE): host-pointer forms of the r04 frame entries (hv_ekf_visual_frame_batch, hv_ekf_visual_track_hybrid, hv_ekf_symmetrize_augment), hv_ekf_insert_map_point / hv_ekf_get_map_point; 3 (r04): hv_lanes_*, hv_get_stream; 2 (r03): hv_debug_*_knob, hv_ekf_frame_error, HV_ERR_TIMEOUT; maxSuccessfulVisualUpdates <= 0 = no limit */
 #define HV_MAX_LEVELS 6
 
 typedef enum hv_status {
@@ -563,13 +563,78 @@ int hv_hybrid_ransac_lk_batch_dev(hv_ctx *ctx, const hv_ransac5_params *p, int n
                                   const hv_camera_model *camera2, int *result_dev, double *score_dev, double *E_dev,
                                   int *r5_summary_dev);
 
+/* ---- stereo track gate: flow status, epipolar check, crop, blacklist and the detection filter (added within ABI 4) -----
+ * Replaces the per-track status rules between the LK calls and RansacPipeline::compute in TrackerImplementation::track
+ * (src/tracker/tracker.cpp:441-478) and the filter of new corners in detectFeatures (:266-311), with the helpers
+ * computeEpipolarCurve (:81-106), withinDistanceFromCurve (:128-151), isPointInCrop (:315-320),
+ * markOutOfDetectionCropCornersAsFailed (:322-346) and markCornersFailedByEpipolarConstraint (:348-376). Statuses are
+ * int32 Feature::Status (TRACKED 0, FAILED_FLOW 2, FLOW_OUT_OF_RANGE 4, OUT_OF_RANGE 5, FAILED_EPIPOLAR_CHECK 6,
+ * BLACKLISTED 8). Equal to the numpy restatement in tests/stereo_gate_restatement.py: the curve in binary64 through the
+ * cameras of hv_rot_ransac (8 points, s = 0.5, 1, ..., 64, transformVec3ByMat4's order), its points and the distance
+ * tests in binary32, dist = (float)((double)(maxStereoEpipolarDistance * (float)min(w, h)) / 720.0), the crop test in
+ * binary64; w and h are the context's level-0 size. An empty curve (pixelToRay on camera0 or any rayToPixel on camera1
+ * failing) leaves the status as it is.
+ * cam0ToCam1 = secondImuToCamera * imuToCamera^-1 (tracker.cpp:362), 16 row-major doubles formed by the caller: the
+ * library does not restate Eigen's 4 x 4 inverse, so the caller's product is what the reference's must equal.
+ * second_corners == NULL: mono (stereo_status must be NULL too; no epipolar check, no right crop, camera1 may be NULL).
+ * Layouts of the _dev forms: those of hv_klt_track_batch_dev / _ragged_dev, set s = n_points_dev[s] <= max_points entries
+ * at s * max_points; entries at and beyond n_points_dev[s] are not touched. The _dev forms are asynchronous on the context
+ * stream with no allocation or synchronisation inside (capturable in a HIP graph). Checks made before the context is
+ * looked at: HV_ERR_INVALID for NULL required arrays or parameters, negative sizes, or a stereo / mono mismatch;
+ * HV_ERR_UNSUPPORTED for n_sets > 65535 or, in the detection filter, max_points > 1024. */
+#define HV_DETECTION_FILTER_MAX_POINTS 1024
+typedef struct hv_stereo_gate_params {
+    float maxStereoEpipolarDistance;      /* 10  codegen/parameter_definitions.c:217; <= 0: no epipolar check */
+    double partOfImageToDetectFeatures;   /* 1   :353; < 1: the crop test of isPointInCrop */
+    int fisheyeCamera;                    /* 0   :246; != 0: a corner whose pixelToRay fails is OUT_OF_RANGE */
+    int independentStereoOpticalFlow;     /* 0   :210; != 0: track() skips the epipolar check (detectFeatures does not) */
+    double cam0ToCam1[16];                /* row-major; default identity */
+} hv_stereo_gate_params;
+void hv_stereo_gate_default_params(hv_stereo_gate_params *p);
+/* OpticalFlow::compute's status mapping (optical_flow.cpp:52-58) on the device: status = lk == 0 ? FAILED_FLOW : TRACKED,
+ * then FLOW_OUT_OF_RANGE where x < 0 || x >= w || y < 0 || y >= h (binary32, w / h the level-0 size). xy_dev / lk_status_dev
+ * = the next_xy_dev / status_dev of hv_klt_track_batch_dev (or _ragged_dev), [n_sets][max_points]; status_dev int32. */
+int hv_flow_status_batch_dev(hv_ctx *ctx, int n_sets, int max_points, const int *n_points_dev, const float *xy_dev,
+                             const uint8_t *lk_status_dev, int32_t *status_dev);
+/* tracker.cpp:441-478 on n features, in the reference's order, track_status in / out (the left flow status on entry):
+ * (1) stereo_status == FAILED_FLOW -> FAILED_FLOW (only that value is merged); (2) stereo, maxStereoEpipolarDistance > 0
+ * and !independentStereoOpticalFlow: a TRACKED feature whose right corner is not within dist of the left corner's
+ * non-empty curve -> FAILED_EPIPOLAR_CHECK; (3) the crop marks of the left corners (camera0), then of the right ones
+ * (camera1) -> OUT_OF_RANGE, overwriting any status; (4) blacklist[i] != 0 (NULL: none) -> BLACKLISTED (the tracks whose
+ * status is BLACKLISTED). corners = the current left corners, second_corners = the current right ones. Synchronous. */
+int hv_track_gate(hv_ctx *ctx, const hv_stereo_gate_params *p, int n, const float *corners, const float *second_corners,
+                  const int32_t *stereo_status, const uint8_t *blacklist, const hv_camera_model *camera0,
+                  const hv_camera_model *camera1, int32_t *track_status);
+/* The same for n_sets sets in device memory. tracked_mask_dev (NULL ok) [n_sets][max_points] uint8 = (status == TRACKED):
+ * hv_rot_ransac_lk_batch_dev with lk_tracked_value 1 on it selects the features RansacPipeline::compute selects
+ * (ransac_pipeline.cpp:106-112). */
+int hv_track_gate_batch_dev(hv_ctx *ctx, const hv_stereo_gate_params *p, int n_sets, int max_points, const int *n_points_dev,
+                            const float *corners_dev, const float *second_corners_dev, const int32_t *stereo_status_dev,
+                            const uint8_t *blacklist_dev, const hv_camera_model *camera0, const hv_camera_model *camera1,
+                            int32_t *track_status_dev, uint8_t *tracked_mask_dev);
+/* detectFeatures after the stereo LK of the n <= 1024 new corners (tracker.cpp:266-311): the status starts as stereo_status
+ * (mono: TRACKED); stereo and maxStereoEpipolarDistance > 0: the epipolar check (whatever independentStereoOpticalFlow);
+ * the crop marks, left then right; then the TRACKED pairs are compacted in input order into out_corners / out_second
+ * (*n_out of them). status (NULL ok) receives the n final statuses. The outputs may be the inputs. Synchronous. */
+int hv_detection_filter(hv_ctx *ctx, const hv_stereo_gate_params *p, int n, const float *corners, const float *second_corners,
+                        const int32_t *stereo_status, const hv_camera_model *camera0, const hv_camera_model *camera1,
+                        int32_t *status, float *out_corners, float *out_second, int *n_out);
+/* The same for n_sets sets of <= max_points <= 1024 corners, one workgroup per set: set s compacted at s * max_points of
+ * out_corners_dev / out_second_dev, its count in n_out_dev[s]. */
+int hv_detection_filter_batch_dev(hv_ctx *ctx, const hv_stereo_gate_params *p, int n_sets, int max_points,
+                                  const int *n_points_dev, const float *corners_dev, const float *second_corners_dev,
+                                  const int32_t *stereo_status_dev, const hv_camera_model *camera0,
+                                  const hv_camera_model *camera1, int32_t *status_dev, float *out_corners_dev,
+                                  float *out_second_dev, int *n_out_dev);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
        HV_K_VU_TRI = 11 /* r06: the triangulation front of the split form (vu_tri_kernel); HV_K_VU_PREPARE then times the record-fed gates */,
        HV_K_SUBPIX = 12 /* added within ABI 4: hv_corner_subpix* */,
        HV_K_RANSAC5 = 13 /* added within ABI 4: hv_ransac5*, hv_hybrid_ransac_lk_batch_dev */,
-       HV_K_COUNT = 14 };
+       HV_K_STEREO_GATE = 14 /* added within ABI 4: hv_flow_status_batch_dev, hv_track_gate*, hv_detection_filter* */,
+       HV_K_COUNT = 15 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
 /* Synchronizes, then returns accumulated device milliseconds and launch count of a kernel class. */
