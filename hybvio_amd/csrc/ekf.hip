@@ -24,7 +24,6 @@
 //     matrix A P A' + Q, which is a gather of P and never materialised; mirrored tile pairs meet
 //     through an in-wave LDS transpose for the fused (P+P')/2, and the result goes to the second of
 //     two ping-pong buffers: one read and one write of P per augmentation.
-#include <functional>
 #include <limits.h>
 #include <math.h>
 
@@ -33,6 +32,7 @@
 #include <stdlib.h>
 
 #include "ekf_device.hpp"
+#include "ekf_host.hpp"
 
 // The library is built with -ffp-contract=off for the tracker's bit-exact binary32 sequence; the
 // EKF is judged against a relative tolerance, and a fused multiply-add is one rounding fewer and
@@ -2000,12 +2000,6 @@ __global__ __launch_bounds__(1024) void ekf_symmetrize_kernel(int n, double *Pal
     }
 }
 
-__global__ void fill_doubles_kernel(double *dst, int n, double value)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = value;
-}
-
 __global__ void ekf_normalize_kernel(int n, int map_dim, double *mall, int only_current)
 {
     double *m = mall + (size_t)blockIdx.x * n;
@@ -2072,75 +2066,14 @@ __global__ __launch_bounds__(256) void ekf_transform_kernel(TransformArgs a)
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct Ekf {
-    Ctx *c = nullptr;
-    hv_ekf_params par{};
-    int batch = 0, n = 0, cam = 0, map_dim = 0;
-    double noise_scale = 0;
-    double *m = nullptr, *P = nullptr, *P1 = nullptr, *m1 = nullptr, *Q = nullptr, *dydx = nullptr, *ws = nullptr;
-    double *sH = nullptr, *sv = nullptr, *sr = nullptr, *schi2 = nullptr, *simu = nullptr;   // staging for host-pointer calls
-    int *sstatus = nullptr, *sdrop = nullptr;
-    unsigned char *sactive = nullptr;
-    size_t sH_cap = 0;
-    int max_rows = 0;
-    // buffers of hv_ekf_visual_track_dev (row f3), sized on first use
-    double *vuH = nullptr, *vuv = nullptr, *vupf = nullptr;
-    unsigned char *vuactive = nullptr;
-    int *vurows = nullptr;                                // ragged batches: per-filter rows of the current visit (written by vu_prepare)
-    int *sprows = nullptr;                                // ... and per (track, filter) record of the speculative loop
-    int vu_rows = 0;
-    // speculative frame loop: per (track, filter) records + per-filter cursor and the update count each record was prepared at
-    double *spH = nullptr, *spv = nullptr, *sppf = nullptr;
-    unsigned char *spactive = nullptr;
-    int *spcursor = nullptr, *spepoch = nullptr;
-    int *spcursor2 = nullptr, *sppub = nullptr;           // fused gate + apply passes: second cursor (ping-pong), published decisions
-    size_t sp_records = 0; int sp_rows = 0;
-    // device staging of the host-pointer entry hv_ekf_visual_track: idx | features | velocities | y | status | gate | chi2 | pf
-    unsigned char *vustage = nullptr;
-    size_t vustage_bytes = 0;
-    // fused prepare + gate (compact Jacobians live in vuH / spH): the active-column lists of the records
-    int *vuacol = nullptr, *spacol = nullptr;
-    // long-track classes of a ragged visit (visual_track_dev_impl): own stream, events, Jacobian / residual / active buffers
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;    // fork onto / join of the context's second stream (Ctx::aux_stream) inside a visit
-    double *sideH = nullptr, *sidev = nullptr;
-    unsigned char *side_active = nullptr;
-    int side_rows = 0;
-    int *side_acol = nullptr; double *side_dm = nullptr;
-    double *tri_rec = nullptr; int tri_stride = 0;        // factor records of vu_tri_kernel (split form of a visit, r06): [batch][tri_stride]
-    int *err_dev = nullptr;                               // device error word (UpdateArgs::err)
-    double *bH = nullptr, *bv = nullptr; int *brows = nullptr; unsigned char *bany = nullptr; int b_rows = 0;   // batchVisualUpdate: stacked [H; v], rows, flags
-    double *gate_scale = nullptr;                         // [batch] per-filter multiplier of the outlier thresholds inside a frame loop (backend.cpp:1192-1193)
-    bool gate_scale_on = false;                           // set by the frame loop while its visits run with a growth factor != 1
-    int *visit_counts = nullptr, *visit_lists = nullptr;  // compaction lists of a visit: counts {inliers short, long records, inliers long}, lists 3 x [batch]
-    // the counts exist once per visit of a frame loop (VISIT_SLOTS x 4 ints, zeroed by ONE memset per frame; visit_slot = the running
-    // visit, set by the loop) plus one set for stand-alone visits (zeroed per call): a memset node per visit was 20 more graph nodes
-    static constexpr int VISIT_SLOTS = 64;
-    int visit_slot = -1;
-    int *visit_order = nullptr;                           // [VISIT_SLOTS][batch] launch_visit_order of the running frame loop, valid while visit_order_ok
-    int *visit_long = nullptr, *visit_long_count = nullptr;   // ... its long-class lists [VISIT_SLOTS][batch] and their lengths [VISIT_SLOTS]
-    bool visit_order_ok = false;
-};
-
-// compact-H description handed to ekf_launch_update (null acol: dense H of l columns); half / nr_full / dm: block update of a long
-// track (UpdateArgs::half)
-struct CompactH { const int *acol = nullptr; int na_max = 0, ncam = 1; int half = 0, nr_full = 0; double *dm = nullptr; const int *rec_count = nullptr, *rec_list = nullptr; int *gate_rw = nullptr;
-                  int half_auto = 0; int *sel_io = nullptr; int *epoch = nullptr; };
-
-// an update launch prepared but not issued (ekf_launch_update's `defer`): two of them can share one grid (ekf_launch_update_dual)
+// an update launch prepared but not issued (UpdateRequest::defer): two of them can share one grid (ekf_launch_update_dual)
 struct UpdateLaunch { UpdateArgs a; size_t base_bytes = 0; int kmode = -1, ti = 0, lbk = 0; };
 
-static int ekf_launch_update(Ekf *e, int nr, int l, const double *H_dev, const double *v_dev, const double *rdiag_dev,
-                             double rd0, int mode, int generic, int normalize_all, double *chi2_dev, int *status_dev,
-                             const unsigned char *active_dev, const int *require_inlier_dev = nullptr,
-                             int *success_counter_dev = nullptr, double rd1 = 0.0, bool *two_r_done = nullptr,
-                             int spec = 0, int n_tracks = 0, int *cursor_dev = nullptr, int max_successful = 0,
-                             const int *gate_in_dev = nullptr, int *cursor_out_dev = nullptr, int *pub_dev = nullptr, int pass_id = 0,
-                             const int *nr_rec_dev = nullptr, const CompactH *compact = nullptr, int nr_stride = 0, UpdateLaunch *defer = nullptr)
+int ekf_launch_update(Ekf *e, const UpdateRequest &rq)
 {
-    // nr_stride (ragged launches that serve one length class): rows of the LONGEST record of the batch = the record stride of H and v;
-    // nr is then the most rows this launch processes (kernel variant, LDS carve), longer records are skipped by their `active` flag
     Ctx *c = e->c;
-    if (nr_stride <= 0) nr_stride = nr;
+    const int nr = rq.nr, l = rq.l, mode = rq.mode, generic = rq.generic, spec = rq.spec;
+    const int nr_stride = rq.nr_stride <= 0 ? nr : rq.nr_stride;
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
     // the chi2 gate needs chi2inv95[nr] (the reference asserts n < chi2inv95.size(): ekf.cpp:806); mode 1 with an
     // inlier requirement is the update half of a gate that already ran
@@ -2153,13 +2086,14 @@ static int ekf_launch_update(Ekf *e, int nr, int l, const double *H_dev, const d
     int r_pad = a.R;
     while ((r_pad & 31) != 15 && (r_pad & 31) != 17) r_pad++;
     a.Rs = r_pad;
-    a.mode = mode; a.generic = generic; a.normalize_all = normalize_all; a.map_dim = e->map_dim;
-    a.m = e->m; a.P = e->P; a.H = H_dev; a.v = v_dev; a.rdiag = rdiag_dev; a.rd0 = rd0; a.rd1 = rd1; a.noise_scale = e->noise_scale;
-    a.ws = e->ws; a.chi2 = chi2_dev; a.status = status_dev; a.active = active_dev; a.require_inlier = require_inlier_dev; a.success_counter = success_counter_dev;
-    a.spec = spec; a.n_tracks = n_tracks; a.cursor = cursor_dev; a.max_successful = max_successful; a.gate_in = gate_in_dev;
-    a.cursor_out = cursor_out_dev; a.pub = pub_dev; a.pass_id = pass_id; a.nr_rec = nr_rec_dev; a.err = e->err_dev;
+    a.mode = mode; a.generic = generic; a.normalize_all = rq.normalize_all; a.map_dim = e->map_dim;
+    a.m = e->m; a.P = e->P; a.H = rq.H_dev; a.v = rq.v_dev; a.rdiag = rq.rdiag_dev; a.rd0 = rq.rd0; a.rd1 = rq.rd1; a.noise_scale = e->noise_scale;
+    a.ws = e->ws; a.chi2 = rq.chi2_dev; a.status = rq.status_dev; a.active = rq.active_dev; a.require_inlier = rq.require_inlier_dev; a.success_counter = rq.success_counter_dev;
+    a.spec = spec; a.n_tracks = rq.n_tracks; a.cursor = rq.cursor_dev; a.max_successful = rq.max_successful; a.gate_in = rq.gate_in_dev;
+    a.cursor_out = rq.cursor_out_dev; a.pub = rq.pub_dev; a.pass_id = rq.pass_id; a.nr_rec = rq.nr_rec_dev; a.err = e->err_dev;
     a.h_stride = (size_t)nr_stride * l; a.v_stride = nr_stride;
-    if (compact && compact->acol) {
+    if (rq.compact.acol) {
+        const CompactH *compact = &rq.compact;
         a.acol = compact->acol; a.na_max = compact->na_max; a.ncam = compact->ncam; a.h_stride = (size_t)nr_stride * compact->na_max;
         a.half = compact->half; a.nr_full = compact->nr_full;
         if (a.half == 1) { a.dm_out = compact->dm; a.gate_rw = compact->gate_rw; }
@@ -2181,13 +2115,13 @@ static int ekf_launch_update(Ekf *e, int nr, int l, const double *H_dev, const d
     if (a.acol && kmode != 2) return HV_ERR_UNSUPPORTED; // compact H is staged by the LDS-resident kernel only (vu_fused_supported)
     if (mode == 3) {                                     // gate (rd0) + update (rd1) in one launch: MODE 2 kernels only
         const bool can = kmode == 2 && ((size_t)(nr + 1) * nr + 256) * sizeof(double) <= hbytes;
-        if (two_r_done) *two_r_done = can;
+        if (rq.two_r_done) *rq.two_r_done = can;
         if (!can) return HV_OK;                          // the caller falls back to two launches
     }
     if (spec && kmode != 2) return HV_ERR_UNSUPPORTED;   // the speculative loop keeps every record in the LDS-resident kernel
     const size_t shmem = kmode == 2 ? tall + small + hbytes : kmode == 1 ? tall + small : small;
     a.batch = e->batch;
-    if (defer) {
+    if (UpdateLaunch *defer = rq.defer) {
         if (mode == 3 || spec) return HV_ERR_INVALID;
         defer->a = a; defer->base_bytes = tall + small; defer->kmode = kmode; defer->ti = ti; defer->lbk = lbk;
         return HV_OK;
@@ -2205,7 +2139,7 @@ static int ekf_launch_update(Ekf *e, int nr, int l, const double *H_dev, const d
         attr_set = true;
     }
     ScopedKernelTime tm(c, HV_K_EKF_UPDATE);
-    hipLaunchKernelGGL(kern, dim3(e->batch, (spec == 1 || spec == 3) ? n_tracks : 1), dim3(UPD_THREADS), shmem, c->stream, a);
+    hipLaunchKernelGGL(kern, dim3(e->batch, (spec == 1 || spec == 3) ? rq.n_tracks : 1), dim3(UPD_THREADS), shmem, c->stream, a);
     HV_HIP(c, hipGetLastError());
     return HV_OK;
 }
@@ -2237,11 +2171,27 @@ static int ekf_launch_update_dual(Ekf *e, const UpdateLaunch &A, const UpdateLau
     return HV_OK;
 }
 
-static int ekf_launch_gate_stream(Ekf *e, int nr, int l, const double *H_dev, const double *v_dev, double rd, double *chi2_dev,
-                                  int *status_dev, const unsigned char *active_dev, const int *success_counter_dev, int max_successful,
-                                  bool *done)
+int ekf_launch_update_paired(Ekf *e, const UpdateRequest &us, const UpdateRequest &b1, const UpdateRequest &b2, bool *done)
+{
+    // (short class beside block 1, what did not fit on the chip beside block 2: see ekf_update_dual_kernel)
+    UpdateLaunch s, u1, u2;
+    *done = false;
+    const auto prepare = [e](UpdateRequest rq, UpdateLaunch *out) { rq.defer = out; return ekf_launch_update(e, rq); };
+    int rc = prepare(us, &s);
+    if (rc == HV_OK) rc = prepare(b1, &u1);
+    if (rc == HV_OK) rc = prepare(b2, &u2);
+    if (rc != HV_OK) return rc;
+    rc = ekf_launch_update_dual(e, s, u1, 0, done);
+    if (rc != HV_OK || !*done) return rc;
+    bool again = false;
+    return ekf_launch_update_dual(e, s, u2, 1, &again);              // (same shapes: accepted again)
+}
+
+int ekf_launch_gate_stream(Ekf *e, const GateStreamRequest &rq)
 {
     Ctx *c = e->c;
+    const int nr = rq.nr, l = rq.l;
+    bool *done = rq.done;
     *done = false;
     if (nr < 1 || nr > 48 || nr >= HV_CHI2INV95_N || l < 1 || l > e->n) return HV_OK;        // the caller keeps its other route
     GateArgs a{};
@@ -2249,8 +2199,8 @@ static int ekf_launch_gate_stream(Ekf *e, int nr, int l, const double *H_dev, co
     int r_pad = nr + 1;
     while ((r_pad & 31) != 15 && (r_pad & 31) != 17) r_pad++;
     a.Rs = r_pad;
-    a.P = e->P; a.H = H_dev; a.v = v_dev; a.rd = rd; a.noise_scale = e->noise_scale; a.chi2 = chi2_dev; a.status = status_dev;
-    a.active = active_dev; a.success_counter = success_counter_dev; a.max_successful = max_successful;
+    a.P = e->P; a.H = rq.H_dev; a.v = rq.v_dev; a.rd = rq.rd; a.noise_scale = e->noise_scale; a.chi2 = rq.chi2_dev; a.status = rq.status_dev;
+    a.active = rq.active_dev; a.success_counter = rq.success_counter_dev; a.max_successful = rq.max_successful;
     const int ti = (nr + 15) / 16, lbk = (l + 15) / 16;
     const size_t hs = (size_t)(16 * ti) * (16 * lbk), shmem = sizeof(double) * (hs + (size_t)a.Rs * nr + 2);
     if (hs < 256 + 544 + 8) return HV_OK;                          // W / col / red borrow the H area
@@ -2271,110 +2221,17 @@ static int ekf_launch_gate_stream(Ekf *e, int nr, int l, const double *H_dev, co
     return HV_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Hybrid map (backend.cpp:1160-1168): an inlier pose-trail track that is OFFERED a map slot becomes a map point -- insertMapPoint
-// (ekf.cpp:911-921: the slot's rows and columns of P zeroed, 1e6 on its diagonal, the triangulated point in the mean) -- INSTEAD of
-// being applied. One workgroup per filter; active_out = the filters whose track still takes updateVisualTrack.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ekf_hybrid_insert_kernel(int n, int map_base, double *m_all, double *P_all, const unsigned char *active,
-                                                                const int *gate, const int *map_index, const int *offer, const double *pf,
-                                                                unsigned char *active_out)
-{
-    const int b = blockIdx.x, t = threadIdx.x;
-    const bool act = active[b] != 0, inlier = act && gate[b] == 0;
-    const int slot = (inlier && (!map_index || map_index[b] < 0) && offer) ? offer[b] : -1;
-    if (t == 0) active_out[b] = (act && slot < 0) ? 1 : 0;
-    if (slot < 0) return;
-    const int off = map_base + 3 * slot;
-    double *m = m_all + (size_t)b * n, *P = P_all + (size_t)b * n * n;
-    for (int i = t; i < 3 * n; i += 256) {
-        const int k = i / n, j = i - k * n;
-        P[(size_t)(off + k) * n + j] = 0.0;
-        P[(size_t)j * n + off + k] = 0.0;
-    }
-    __syncthreads();
-    if (t < 3) { P[(size_t)(off + t) * n + off + t] = 1e6; m[off + t] = pf[3 * b + t]; }
-}
-
-// ---------------------------------------------------------------------------------------------
-// batchVisualUpdate (backend.cpp:1001-1010, 1169-1183, 1255-1262): inside a batch every track is gated against the SAME (m, P) -- the
-// updates are deferred --, so one speculative pass (every pending track prepared and gated in one launch) IS the reference's loop up to
-// the next flush. This kernel is the bookkeeping of that loop for one filter: it walks the pending tracks in visit order, appends the
-// inliers' blocks [H; v] to the filter's batch while they fit max_rows and the quota lasts, and leaves the stacked dense H (column-major,
-// leading dimension = the batch's row count) and v for ONE updateVisualTrack launch (ragged dense update: rows_out). A block that does
-// not fit ends the pass: the batch is flushed by that update, the block opens the NEXT batch unchanged (carry), and the next pass gates
-// the tracks behind it against the updated state -- the reference's flush-then-append.
-// ---------------------------------------------------------------------------------------------
-struct BatchAssembleArgs {
-    int n, n_tracks, batch, max_rows, max_successful, rows_stride, na_max, ncam;
-    const double *Hc, *v;             // compact records of the gate launch: [n_tracks][batch] x (rows_stride x na_max), x rows_stride
-    const int *acol, *nr_rec;         // [records][na_max]; rows of every record (null: rows_stride)
-    const unsigned char *active; const int *gate;
-    int *cursor, *success_counter, *carry;   // carry [batch]: the track whose block opens the next batch (-1: none)
-    double *Hd, *vd;                  // [batch][max_rows x n], [batch][max_rows]
-    int *rows_out; unsigned char *any_out;
-};
-constexpr int BATCH_THREADS = 256;
-__global__ __launch_bounds__(BATCH_THREADS) void ekf_batch_assemble_kernel(BatchAssembleArgs a)
-{
-    __shared__ int s_list[64], s_off[64], s_cnt, s_rows;
-    const int b = blockIdx.x, t = threadIdx.x;
-    if (t == 0) {
-        int succ = a.success_counter[b], rows = 0, cnt = 0, j = a.cursor[b];
-        // the track whose block did not fit the previous batch opens this one AS IT WAS prepared and gated -- against the state before
-        // the flush: the reference has its H, f, y in hand when it flushes and appends them afterwards (backend.cpp:1171-1182)
-        const int cj = a.carry[b];
-        if (cj >= 0) {
-            const int rec = cj * a.batch + b;
-            s_list[0] = cj; s_off[0] = 0; rows = a.nr_rec ? a.nr_rec[rec] : a.rows_stride; cnt = 1; ++succ;
-            a.carry[b] = -1;
-        }
-        for (; j < a.n_tracks; ++j) {
-            if (succ >= a.max_successful) break;                                   // quota (backend.cpp:1233): the next pass marks the rest NOT_VISITED
-            const int rec = j * a.batch + b;
-            if (!a.active[rec] || a.gate[rec] != 0) continue;                     // failed triangulation / outlier: final, nothing to apply
-            const int nr = a.nr_rec ? a.nr_rec[rec] : a.rows_stride;
-            if (rows + nr > a.max_rows || cnt == 64) { a.carry[b] = j; ++j; break; }      // flush first; the block waits for the next batch
-            s_list[cnt] = j; s_off[cnt] = rows; rows += nr; ++cnt; ++succ;
-        }
-        a.cursor[b] = j;                                                           // (n_tracks when every pending track is final)
-        a.success_counter[b] = succ;
-        a.rows_out[b] = rows; a.any_out[b] = rows > 0 ? 1 : 0;
-        s_cnt = cnt; s_rows = rows;
-    }
-    __syncthreads();
-    const int cnt = s_cnt, rows = s_rows;
-    if (rows == 0) return;
-    double *Hd = a.Hd + (size_t)b * a.max_rows * a.n, *vd = a.vd + (size_t)b * a.max_rows;
-    for (int i = t; i < rows * a.n; i += BATCH_THREADS) Hd[i] = 0.0;
-    __syncthreads();
-    for (int q = 0; q < cnt; ++q) {
-        const int rec = s_list[q] * a.batch + b, off = s_off[q];
-        const int nr = a.nr_rec ? a.nr_rec[rec] : a.rows_stride, na = 7 * (nr / (2 * a.ncam)) + 1;
-        const double *Hc = a.Hc + (size_t)rec * a.rows_stride * a.na_max, *v = a.v + (size_t)rec * a.rows_stride;
-        const int *acol = a.acol + (size_t)rec * a.na_max;
-        for (int i = t; i < na * nr; i += BATCH_THREADS) {
-            const int u = i / nr, r = i - u * nr;
-            Hd[(size_t)acol[u] * rows + off + r] = Hc[i];                          // (compact column u of the record, leading dimension nr)
-        }
-        for (int r = t; r < nr; r += BATCH_THREADS) vd[off + r] = v[r];
-    }
-}
-
-// ekf_sparse_gate_kernel over the compact records of a prepare launch (np = poses of the longest record)
-static int ekf_launch_sparse_gate(Ekf *e, int np, int ncam, const double *Hc_dev, const double *v_dev, const int *acol_dev, const int *nr_rec_dev,
-                                  const unsigned char *active_dev, double rd, double *chi2_dev, int *status_dev,
-                                  const int *rec_count = nullptr, const int *rec_list = nullptr, int *inl_count = nullptr, int *inl_list = nullptr,
-                                  hipStream_t stream = nullptr)
+int ekf_launch_sparse_gate(Ekf *e, const SparseGateRequest &rq)
 {
     Ctx *c = e->c;
-    if (!stream) stream = c->stream;
+    const int np = rq.np, ncam = rq.ncam;
+    const hipStream_t stream = rq.stream ? rq.stream : c->stream;
     const int nr = 2 * np * ncam, na_max = 7 * np + 1, na4 = (na_max + 3) & ~3, nrp = 16 * ((nr + 15) / 16);
-    if (nr < 2 || nr > 96 || nr >= HV_CHI2INV95_N || !active_dev || !status_dev) return HV_ERR_INVALID;
+    if (nr < 2 || nr > 96 || nr >= HV_CHI2INV95_N || !rq.active_dev || !rq.status_dev) return HV_ERR_INVALID;
     const bool big = nr > 48;
     SparseGateArgs a{};
-    a.n = e->n; a.nr = nr; a.ncam = ncam; a.na_max = na_max; a.P = e->P; a.Hc = Hc_dev; a.v = v_dev; a.acol = acol_dev; a.nr_rec = nr_rec_dev;
-    a.active = active_dev; a.rd = rd; a.noise_scale = e->noise_scale; a.chi2 = chi2_dev; a.status = status_dev;
+    a.n = e->n; a.nr = nr; a.ncam = ncam; a.na_max = na_max; a.P = e->P; a.Hc = rq.Hc_dev; a.v = rq.v_dev; a.acol = rq.acol_dev; a.nr_rec = rq.nr_rec_dev;
+    a.active = rq.active_dev; a.rd = rq.rd; a.noise_scale = e->noise_scale; a.chi2 = rq.chi2_dev; a.status = rq.status_dev;
     int Rs = nr + 1;
     while ((Rs & 31) != 15 && (Rs & 31) != 17) Rs++;
     // LDS: Hc staged [na4][nrp] + [S; v'] (Rs x nr) + the column list. The launch is sized for its longest record; in the big build a
@@ -2399,7 +2256,7 @@ static int ekf_launch_sparse_gate(Ekf *e, int np, int ncam, const double *Hc_dev
         attr_set = true;
     }
     ScopedKernelTime tm(c, HV_K_EKF_GATE, stream);
-    a.rec_count = rec_count; a.rec_list = rec_list; a.inl_count = inl_count; a.inl_list = inl_list;
+    a.rec_count = rq.rec_count; a.rec_list = rq.rec_list; a.inl_count = rq.inl_count; a.inl_list = rq.inl_list;
     a.batch = e->batch;
     if (big) hipLaunchKernelGGL(ekf_sparse_gate_big_kernel, dim3((unsigned)e->batch), dim3(SGATE_BIG_THREADS), shmem, stream, a);
     else     hipLaunchKernelGGL(ekf_sparse_gate_kernel, dim3(e->batch), dim3(SGATE_THREADS), shmem, stream, a);
@@ -2413,8 +2270,6 @@ using hv::Ctx;
 using hv::Ekf;
 
 extern "C" {
-
-struct hv_ekf { Ekf e; };
 
 void hv_ekf_default_params(hv_ekf_params *p)
 {
@@ -2522,879 +2377,6 @@ void hv_vu_default_params(hv_vu_params *p)
     }
     const double tr[3] = {0.0075, 0.013, -0.0003};                                               // :187 stereoCameraTranslation
     for (int r = 0; r < 3; ++r) p->secondImuToCamera[4 * r + 3] += tr[r];                         // tracker/util.cpp:100-105
-}
-
-static int vu_fill_args(Ekf *e, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
-                        const double *y, hv::VuPrepareArgs &a)
-{
-    if (!p || !idx || !feat || !vel || np < 2 || np > e->cam + 1) return HV_ERR_INVALID;
-    a = hv::VuPrepareArgs{};
-    a.batch = e->batch; a.n = e->n; a.np = np; a.stereo = p->useStereo ? 1 : 0;
-    a.m = e->m; a.pose_index = idx; a.features = feat; a.velocities = vel; a.y = y;
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) {
-        a.imu_to_cam[0][4 * r + c] = p->imuToCamera[4 * r + c];
-        a.imu_to_cam[1][4 * r + c] = p->secondImuToCamera[4 * r + c];
-    }
-    a.conv_threshold = p->triangulationConvergenceThreshold; a.conv_r = p->triangulationConvergenceR;
-    a.rcond_threshold = p->triangulationRcondThreshold; a.min_dist = p->triangulationMinDist; a.max_dist = p->triangulationMaxDist;
-    a.gn_iters = (int)p->triangulationGaussNewtonIterations; a.est_shift = p->estimateImuCameraTimeShift ? 1 : 0;
-    a.defer_h = e->c->knob.ekf_defer_jacobian != 0;
-    a.linear = p->useLinearTriangulation ? 1 : 0;
-    // adaptive outlier thresholds (ABI 3): the RMSE test applies everywhere the fused gate runs; the per-filter growth only inside a
-    // frame loop (visual_frame_dev_impl hands the multiplier array over through Ekf::gate_scale_on)
-    a.rmse_thr = p->trackRmseThreshold; a.growth = p->trackOutlierThresholdGrowthFactor;
-    a.gate_scale = e->gate_scale_on ? e->gate_scale : nullptr;
-    if (!(a.growth > 0.0)) return HV_ERR_INVALID;
-    return HV_OK;
-}
-
-int hv_ekf_visual_prepare_dev(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
-                              const double *y, double *H_dev, double *v_dev, double *f_dev, double *pf_dev, int *status_dev,
-                              unsigned char *active_dev)
-{
-    if (!h || !H_dev || !v_dev || !pf_dev || !status_dev) return HV_ERR_INVALID;
-    Ekf *e = &h->e;
-    hv::VuPrepareArgs a;
-    int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
-    if (rc != HV_OK) return rc;
-    a.H = H_dev; a.v = v_dev; a.f = f_dev; a.pf = pf_dev; a.status = status_dev; a.active = active_dev;
-    return hv::launch_vu_prepare(e->c, a);
-}
-
-static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
-                                 const double *y, double r_gate, double r_update, int *status_dev, int *gate_status_dev,
-                                 double *chi2_dev, double *pf_dev, int *success_counter_dev, int max_successful,
-                                 const int *np_rec_dev = nullptr);
-
-// shapes of a track visit: the longest track the short class's fused two-per-CU kernels serve, whether tracks of np poses take the
-// long-class launches (49 .. 96 rows), and whether a ragged visit of up to np poses runs as TWO length classes
-struct VisitShape { int ncam, np_short, rows; bool long_ok, two_class; };
-// (r06: where the split form serves the visit -- stereo, iterative triangulation, more filters than CUs -- the short class ends at
-//  12 poses = 48 rows, what the record-fed gate stages three to a CU, instead of 11: 4 % of a ragged visit's records leave the long
-//  class, its 158 KB gate and its two block updates)
-static VisitShape visit_shape(const Ekf *e, int np, bool stereo, bool linear)
-{
-    VisitShape v{};
-    v.ncam = stereo ? 2 : 1; v.np_short = 22 / v.ncam; v.rows = 2 * np * v.ncam;
-    if (hv::vu_split_short_ok(e->c, e->n, stereo, e->batch, linear)) v.np_short = hv::vu_split_short_np(e->c);
-    v.long_ok = e->c->knob.ekf_fused_gate != 0 && e->n <= 160 && v.rows > 48 && v.rows <= 96 && v.rows < HV_CHI2INV95_N && (v.rows + 3) / 4 * 2 <= 48;
-    v.two_class = np > v.np_short && v.long_ok && hv::vu_fused_supported(e->c, e->n, v.np_short, stereo, e->batch);
-    return v;
-}
-
-int hv_ekf_visual_track_dev(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
-                            const double *y, double r_gate, double r_update, int *status_dev, int *gate_status_dev,
-                            double *chi2_dev, double *pf_dev)
-{
-    return visual_track_dev_impl(h, p, np, idx, feat, vel, y, r_gate, r_update, status_dev, gate_status_dev, chi2_dev, pf_dev, nullptr, 0);
-}
-
-int hv_ekf_visual_track_limited_dev(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
-                                    const double *y, double r_gate, double r_update, int *status_dev, int *gate_status_dev,
-                                    double *chi2_dev, double *pf_dev, int *success_counter_dev, int max_successful)
-{
-    if (!success_counter_dev) return HV_ERR_INVALID;
-    // maxSuccessfulVisualUpdates <= 0 is the reference's "no limit" (backend.cpp:1233), as in the frame entry points (r03 advisor)
-    if (max_successful <= 0) max_successful = INT_MAX;
-    return visual_track_dev_impl(h, p, np, idx, feat, vel, y, r_gate, r_update, status_dev, gate_status_dev, chi2_dev, pf_dev,
-                                 success_counter_dev, max_successful);
-}
-
-// One track visit of a session with a hybrid map (odometry.hybridMapSize > 0; backend.cpp:1016, 1075-1082, 1146, 1160-1168):
-//   map_update_dev [batch]: the map point a mapPointUpdate track belongs to (>= 0) -- the point is read from the state, status
-//                           HV_TRI_HYBRID, H carries dip R in the point's columns -- or -1 for a pose-trail track;
-//   map_offer_dev [batch]:  the slot ekfStateIndex.offerMapPoint would hand to this track if the gate accepts it (-1: none; the offer
-//                           does not depend on the filter, so the adapter evaluates it up front): such an inlier is INSERTED as a map
-//                           point instead of being applied.
-// Dense kernels (the state is wider than 160 columns). Either array may be NULL.
-int hv_ekf_visual_track_hybrid_dev(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
-                                   const double *y, const int *map_update_dev, const int *map_offer_dev, double r_gate, double r_update,
-                                   int *status_dev, int *gate_status_dev, double *chi2_dev, double *pf_dev)
-{
-    if (!h || !status_dev || !gate_status_dev || !y) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
-    if (e->map_dim <= 0 && (map_update_dev || map_offer_dev)) return HV_ERR_INVALID;
-    hv::VuPrepareArgs a;
-    int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
-    if (rc != HV_OK) return rc;
-    if (a.rmse_thr >= 0.0) return HV_ERR_UNSUPPORTED;                  // (the dense gate has no RMSE test)
-    const int rows = 2 * np * (a.stereo ? 2 : 1);
-    if (rows > e->max_rows || rows >= HV_CHI2INV95_N) return HV_ERR_INVALID;
-    if (e->vu_rows < rows) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        void *old[] = {e->vuH, e->vuv};
-        for (void *q : old) if (q) (void)hipFree(q);
-        e->vuH = e->vuv = nullptr; e->vu_rows = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuH), sizeof(double) * (size_t)rows * e->n * e->batch));
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuv), sizeof(double) * (size_t)rows * e->batch));
-        if (!e->vupf) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vupf), sizeof(double) * 3 * e->batch));
-        if (!e->vuactive) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuactive), e->batch));
-        if (!e->vuacol) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuacol), sizeof(int) * (size_t)e->n * e->batch));
-        e->vu_rows = rows;
-    }
-    const double ns = e->noise_scale;
-    double *pf = pf_dev ? pf_dev : e->vupf;
-    a.H = e->vuH; a.v = e->vuv; a.f = nullptr; a.pf = pf; a.status = status_dev; a.active = e->vuactive; a.gate_status = gate_status_dev;
-    a.map_index = map_update_dev; a.map_base = e->n - e->map_dim;
-    rc = hv::launch_vu_prepare(c, a);
-    if (rc != HV_OK) return rc;
-    // visualTrackOutlierCheck, then -- per filter -- insertMapPoint or updateVisualTrack where it passed
-    rc = hv::ekf_launch_update(e, rows, e->n, e->vuH, e->vuv, nullptr, r_gate * r_gate * ns, 0, 0, 0, chi2_dev, gate_status_dev, e->vuactive);
-    if (rc != HV_OK) return rc;
-    hipLaunchKernelGGL(hv::ekf_hybrid_insert_kernel, dim3(e->batch), dim3(256), 0, c->stream, e->n, e->n - e->map_dim, e->m, e->P, e->vuactive,
-                       gate_status_dev, map_update_dev, map_offer_dev, pf, e->sactive);
-    HV_HIP(c, hipGetLastError());
-    return hv::ekf_launch_update(e, rows, e->n, e->vuH, e->vuv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr, nullptr, e->sactive, gate_status_dev);
-}
-
-static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
-                                 const double *y, double r_gate, double r_update, int *status_dev, int *gate_status_dev,
-                                 double *chi2_dev, double *pf_dev, int *success_counter_dev, int max_successful,
-                                 const int *np_rec_dev)
-{
-    if (!h || !status_dev || !gate_status_dev || !y) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
-    hv::VuPrepareArgs a;
-    int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
-    if (rc != HV_OK) return rc;
-    const int rows = 2 * np * (a.stereo ? 2 : 1);
-    if (rows > e->max_rows) return HV_ERR_INVALID;
-    if (e->vu_rows < rows) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        void *old[] = {e->vuH, e->vuv};
-        for (void *q : old) if (q) (void)hipFree(q);
-        e->vuH = e->vuv = nullptr; e->vu_rows = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuH), sizeof(double) * (size_t)rows * e->n * e->batch));
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuv), sizeof(double) * (size_t)rows * e->batch));
-        if (!e->vupf) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vupf), sizeof(double) * 3 * e->batch));
-        if (!e->vuactive) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuactive), e->batch));
-        if (!e->vuacol) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuacol), sizeof(int) * (size_t)e->n * e->batch));
-        e->vu_rows = rows;
-    }
-    // ragged batch (filters with tracks of different lengths, or none, in one visit): np is the longest track = the record stride;
-    // the prepare launch writes every filter's row count for the gate / update launch
-    const int *nr_rec = nullptr;
-    if (np_rec_dev) {
-        if (!e->vurows) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vurows), sizeof(int) * e->batch));
-        a.np_rec = np_rec_dev; a.rows_out = e->vurows; nr_rec = e->vurows;
-    }
-    a.H = e->vuH; a.v = e->vuv; a.f = nullptr; a.pf = pf_dev ? pf_dev : e->vupf; a.status = status_dev; a.active = e->vuactive;
-    a.gate_status = gate_status_dev;                       // preset to NOT_COMPUTED; the gate overwrites it where it runs
-    a.success_counter = success_counter_dev; a.max_successful = max_successful;
-    const double ns = e->noise_scale;
-    hipStream_t main_stream = c->stream;
-    // r03 default: visualTrackOutlierCheck runs INSIDE the prepare launch on the active columns of H (vu_gate kernels: the Jacobian
-    // of a rejected track never leaves LDS and only P(a, a) is read); updateVisualTrack then runs where the gate said INLIER, staging the
-    // compact Jacobian through its column map (7 of 20 visits at most -- backend.cpp:1233-1238 -- pay the full H P + downdate).
-    // Long tracks (more than 48 rows / 22 camera poses: 12 .. 21 stereo poses): prepare + column-sparse gate of up to 96 rows in ONE
-    // launch (r04: vu_gate_long_kernel; r03: vu_compact_kernel + ekf_sparse_gate_big_kernel, kept behind knob ekf_long_fused = 0) and the
-    // update as TWO block updates of at most 48 rows each on the P-resident kernel (UpdateArgs::half).
-    const VisitShape shape = visit_shape(e, np, a.stereo != 0, a.linear != 0);
-    const int ncam = shape.ncam, np_short = shape.np_short;
-    const bool long_ok = shape.long_ok;
-    // compaction lists of this visit (VuPrepareArgs): zeroed here, filled by the kernels, consumed by the launches behind them
-    const bool own_counts = e->visit_slot < 0 || e->visit_slot >= Ekf::VISIT_SLOTS;
-    int *counts = e->visit_counts + 4 * (own_counts ? Ekf::VISIT_SLOTS : e->visit_slot);
-    int *cnt_inl = counts, *cnt_long = counts + 1, *cnt_inl_long = counts + 2;
-    int *list_inl = e->visit_lists, *list_long = e->visit_lists + e->batch, *list_inl_long = e->visit_lists + 2 * (size_t)e->batch;
-    // frame loop with sorted visits (launch_visit_order): the long class's records are known -- longest first -- before the fused launch runs
-    const bool presorted = !own_counts && e->visit_order_ok;
-    if (presorted) { cnt_long = e->visit_long_count + e->visit_slot; list_long = e->visit_long + (size_t)e->visit_slot * e->batch; }
-    if (own_counts) HV_HIP(c, hipMemsetAsync(counts, 0, 4 * sizeof(int), main_stream));
-    // short_upd (ragged two-class visits): issues the short class's update, or only prepares it (non-null argument) so that it shares
-    // a grid with the first block update of the long class
-    using ShortUpd = std::function<int(hv::UpdateLaunch *)>;
-    // buffers of the long class: compact Jacobians, residuals, column lists, active flags, block 1's mean step; the fork / join events
-    auto ensure_long = [&]() -> int {
-        if (!e->ev_fork) {
-            HV_HIP(c, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-            HV_HIP(c, hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-        }
-        if (e->side_rows < rows) {
-            HV_HIP(c, hipStreamSynchronize(main_stream));
-            HV_HIP(c, hipStreamSynchronize(c->aux_stream));
-            if (e->sideH) (void)hipFree(e->sideH);
-            if (e->sidev) (void)hipFree(e->sidev);
-            e->sideH = e->sidev = nullptr; e->side_rows = 0;
-            HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->sideH), sizeof(double) * (size_t)rows * e->n * e->batch));
-            HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->sidev), sizeof(double) * (size_t)rows * e->batch));
-            if (!e->side_active) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->side_active), e->batch));
-            if (!e->side_acol) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->side_acol), sizeof(int) * (size_t)e->n * e->batch));
-            if (!e->side_dm) {
-                HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->side_dm), sizeof(double) * (size_t)e->n * e->batch));
-                HV_HIP(c, hipMemsetAsync(e->side_dm, 0, sizeof(double) * (size_t)e->n * e->batch, main_stream));   // (r03 advisor: never read uninitialised)
-            }
-            e->side_rows = rows;
-        }
-        return HV_OK;
-    };
-    // factor records of the split form (knob ekf_split_tri, r06): vu_tri_kernel -> record -> record-fed gate
-    auto ensure_tri = [&]() -> int {
-        const int stride = hv::vu_tri_rec_stride(np, ncam);
-        if (e->tri_stride >= stride) return HV_OK;
-        HV_HIP(c, hipStreamSynchronize(main_stream));
-        if (c->aux_stream) HV_HIP(c, hipStreamSynchronize(c->aux_stream));
-        if (e->tri_rec) (void)hipFree(e->tri_rec);
-        e->tri_rec = nullptr; e->tri_stride = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->tri_rec), sizeof(double) * (size_t)stride * e->batch));
-        e->tri_stride = stride;
-        return HV_OK;
-    };
-    // the gate launch `g` of one length class in split form: the triangulation front first, on the same stream; false = not a shape
-    // the split form serves (the caller issues the fused launch)
-    // phase: 0 = both launches, 1 = the triangulation only, 2 = the gate only (one-stream visits interleave the two classes' launches:
-    // knob ekf_long_first)
-    auto split_launch = [&](hv::VuPrepareArgs &g, hipStream_t stream, int *rc_out, int phase = 0) -> bool {
-        if (!hv::vu_split_supported(c, g, g.fused)) return false;
-        int rc2 = ensure_tri();
-        g.tri_rec = e->tri_rec; g.tri_stride = e->tri_stride;
-        if (rc2 == HV_OK && phase != 2) rc2 = hv::launch_vu_tri(c, g, stream);
-        if (rc2 == HV_OK && phase != 1) { g.from_rec = 1; rc2 = hv::launch_vu_prepare(c, g, stream); }
-        *rc_out = rc2;
-        return true;
-    };
-    // prepare + gate of the long class on `stream` (nothing else touches c->stream: r03 swapped the context's stream for these calls)
-    auto long_prepare_gate = [&](hv::VuPrepareArgs l_, double *Hc, double *vv, int *acol, unsigned char *act, bool listed, hipStream_t stream, int phase = 0) -> int {
-        l_.H = nullptr; l_.Hc = Hc; l_.v = vv; l_.acol = acol; l_.na_max = 7 * np + 1; l_.active = act; l_.chi2 = chi2_dev;
-        if (listed) { l_.rec_count = cnt_long; l_.rec_list = list_long; }
-        const bool adaptive_gate = l_.rmse_thr >= 0.0 || l_.gate_scale;     // (served by the fused gates only)
-        if (c->knob.ekf_long_fused == 0 && adaptive_gate) return HV_ERR_UNSUPPORTED;
-        if (c->knob.ekf_long_fused != 0) {
-            l_.fused = 3; l_.P = e->P; l_.rd_gate = r_gate * r_gate * ns; l_.noise_scale = ns;
-            l_.inl_count = cnt_inl_long; l_.inl_list = list_inl_long;
-            int rc_s = HV_OK;
-            if (split_launch(l_, stream, &rc_s, phase)) return rc_s;
-            if (phase == 1) return HV_OK;                      // (not a split shape: the fused launch is the gate phase)
-            return hv::launch_vu_prepare(c, l_, stream);
-        }
-        l_.fused = 2;
-        const int rc2 = hv::launch_vu_prepare(c, l_, stream);
-        if (rc2 != HV_OK) return rc2;
-        return hv::ekf_launch_sparse_gate(e, np, ncam, Hc, vv, acol, nr_rec, act, r_gate * r_gate * ns, chi2_dev, gate_status_dev,
-                                          listed ? cnt_long : nullptr, listed ? list_long : nullptr, cnt_inl_long, list_inl_long, stream);
-    };
-    // the two block updates of the long class's inliers on the context stream; with short_upd the short class's update shares their grids
-    auto long_updates = [&](double *Hc, double *vv, int *acol, unsigned char *act, double *dm, const ShortUpd *short_upd) -> int {
-        const int half_rows = 2 * ((rows + 3) / 4);            // the longer of the two blocks of the longest record
-        const int na_max = 7 * np + 1;
-        hv::CompactH h1{acol, na_max, ncam, 1, rows, dm, cnt_inl_long, list_inl_long, gate_status_dev}, h2{acol, na_max, ncam, 2, rows, dm, cnt_inl_long, list_inl_long};
-        // (block 1 may turn a record's gate status into CHI2 when it meets a non-positive pivot: block 2 then skips it -- r03 advisor)
-        auto block1 = [&](hv::UpdateLaunch *defer) -> int {
-            return hv::ekf_launch_update(e, half_rows, e->n, Hc, vv, nullptr, r_update * r_update * ns, 1, 0, -1, nullptr, nullptr, act, gate_status_dev,
-                                         nullptr, 0.0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, nr_rec, &h1, rows, defer);
-        };
-        auto block2 = [&](hv::UpdateLaunch *defer) -> int {
-            return hv::ekf_launch_update(e, half_rows, e->n, Hc, vv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr, nullptr, act, gate_status_dev,
-                                         success_counter_dev, 0.0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, nr_rec, &h2, rows, defer);
-        };
-        int rc2 = HV_OK;
-        if (short_upd) {
-            // (short class beside block 1, what did not fit on the chip beside block 2: see ekf_update_dual_kernel)
-            hv::UpdateLaunch us, u1, u2;
-            bool dual = false;
-            rc2 = (*short_upd)(&us);
-            if (rc2 == HV_OK) rc2 = block1(&u1);
-            if (rc2 == HV_OK) rc2 = block2(&u2);
-            if (rc2 == HV_OK) rc2 = hv::ekf_launch_update_dual(e, us, u1, 0, &dual);
-            if (rc2 == HV_OK && dual) return hv::ekf_launch_update_dual(e, us, u2, 1, &dual);      // (same shapes: accepted again)
-            if (rc2 == HV_OK) { rc2 = (*short_upd)(nullptr); if (rc2 == HV_OK) rc2 = block1(nullptr); }
-        } else rc2 = block1(nullptr);
-        if (rc2 != HV_OK) return rc2;
-        return block2(nullptr);
-    };
-    // Ragged batch with long AND short tracks: two length CLASSES per visit. The short tracks -- 4 of 5 at the reference's defaults, see
-    // bench.py sample_track_lengths -- run on the fused two-per-CU kernels, the long ones through the launches above; the records of a visit
-    // belong to different filters, so the two launch sequences are independent up to the shared update grids. Every launch skips the
-    // other class's records (VuPrepareArgs::np_lo / np_hi, `active`). Schedule of a visit inside a frame loop over more filters than CUs
-    // (knob ekf_side_stream != 0, default; HIP-graph capturable: fork at the start of the visit, join in front of the updates):
-    //     second stream (Ctx::aux_stream):  prepare + gate (long)              -- enqueued FIRST: it takes its CUs while all are free
-    //     context stream:                   fused prepare + gate (short)  | join |  short update + long block 1  ->  rest of short + long block 2
-    // Stand-alone visits and small batches: everything on the context's stream, short class first (its launch collects the long list).
-    // (r03 also had the whole long chain on the second stream -- knob values 1 and 4 -- and the long class enqueued BEHIND the fused
-    //  launch -- 2: all measured slower, removed in r04 together with the stream swap they needed.)
-    if (np_rec_dev && shape.two_class) {
-        rc = ensure_long();
-        if (rc != HV_OK) return rc;
-        bool use_aux = c->knob.ekf_side_stream != 0 && presorted && c->aux_stream;
-        if (use_aux && c->knob.ekf_side_stream == 5) {
-            // lanes (knob value 5, their default): no fork while the context stream is being CAPTURED. A captured fork does not run on
-            // the library's high-priority second stream when the graph is replayed but on a stream the graph instance creates for the
-            // branch -- default priority, bound to whichever hardware queue the process history left least used --, which is exactly the
-            // placement lottery the lanes exist to end (r04, scripts/lanes_probe.py: 2 x 1024 sequences 19.2 / 16.3 ms per step with the
-            // captured fork after two different process histories, 15.84 ms without it)
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(main_stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) use_aux = false;
-        }
-        hv::VuPrepareArgs s_ = a;                              // class "short": 2 .. np_short poses (and the records without a track)
-        s_.np_lo = 2; s_.np_hi = np_short; s_.class_inactive = 1;
-        s_.fused = 1; s_.H = nullptr; s_.Hc = e->vuH; s_.acol = e->vuacol; s_.na_max = 7 * np + 1; s_.P = e->P;
-        s_.rd_gate = r_gate * r_gate * ns; s_.noise_scale = ns; s_.chi2 = chi2_dev;
-        s_.inl_count = cnt_inl; s_.inl_list = list_inl;
-        if (!presorted) { s_.long_count = cnt_long; s_.long_list = list_long; }      // (else nothing to collect)
-        if (presorted) s_.order = e->visit_order + (size_t)e->visit_slot * e->batch;     // (frame loop: sorted once per frame)
-        hv::VuPrepareArgs l_ = a;
-        l_.np_lo = np_short + 1; l_.np_hi = np; l_.class_inactive = 1;
-        // fork ... join: every exit between the two goes through the join (a HIP-graph capture must not be left with a dangling fork)
-        bool forked = false;
-        if (use_aux) {
-            hipError_t he = hipEventRecord(e->ev_fork, main_stream);
-            if (he == hipSuccess) he = hipStreamWaitEvent(c->aux_stream, e->ev_fork, 0);
-            if (he != hipSuccess) return hv::hip_fail(c, he, "fork onto the second stream");
-            forked = true;
-        }
-        rc = HV_OK;
-        // which class runs on which stream when the visit forks: the launch that has to START first -- the long class's, which needs
-        // whole CUs and finds them only while the chip is empty -- belongs on the stream that does NOT wait for the fork event.
-        // r04 default (knob 6, and 5 = the lanes' form of it): long class on the context stream, short class on the second stream.
-        // Knob 3 = r03's arrangement: the long class on the second stream, enqueued first -- but released by the fork event about when
-        // the short class's 810 two-per-CU workgroups are, so that part of it got its CUs a round late (144 us under that load against
-        // 95 alone, profiles/r04/kernel_stats.csv). Measured, one context of 1024 sequences: eager 10.13 -> 9.82 ms per step, HIP-graph
-        // replay 9.67 -> 9.63 (profiles/r04/lanes_probe.txt, session 9).
-        const bool swap = forked && c->knob.ekf_side_stream != 3;
-        hipStream_t long_stream = forked && !swap ? c->aux_stream : main_stream, short_stream = swap ? c->aux_stream : main_stream;
-        const bool long_first = presorted && (forked || c->knob.ekf_long_first == 1);
-        auto short_phase = [&](int phase) -> int {
-            int rc_s = HV_OK;
-            if (split_launch(s_, short_stream, &rc_s, phase)) return rc_s;
-            return phase == 1 ? HV_OK : hv::launch_vu_prepare(c, s_, short_stream);
-        };
-        // one-stream sorted visits, knob ekf_long_first: 0 = short class (triangulation, gate) then long class; 1 = long class first;
-        // 2 .. 4 (split form, r06) = both triangulations in front of both gates: T long, T short, G long, G short / T short, T long,
-        // G short, G long / T long, T short, G short, G long (profiles/r06/visit_launch_order_sweep.txt)
-        const int order = presorted && !forked ? c->knob.ekf_long_first : -1;
-        if (order >= 2 && order <= 4) {
-            const bool lf = order != 3;
-            if (lf) rc = long_prepare_gate(l_, e->sideH, e->sidev, e->side_acol, e->side_active, true, main_stream, 1);
-            if (rc == HV_OK) rc = short_phase(1);
-            if (rc == HV_OK && !lf) rc = long_prepare_gate(l_, e->sideH, e->sidev, e->side_acol, e->side_active, true, main_stream, 1);
-            const bool gl_first = order == 2;
-            if (rc == HV_OK && gl_first) rc = long_prepare_gate(l_, e->sideH, e->sidev, e->side_acol, e->side_active, true, main_stream, 2);
-            if (rc == HV_OK) rc = short_phase(2);
-            if (rc == HV_OK && !gl_first) rc = long_prepare_gate(l_, e->sideH, e->sidev, e->side_acol, e->side_active, true, main_stream, 2);
-        } else {
-        if (long_first) rc = long_prepare_gate(l_, e->sideH, e->sidev, e->side_acol, e->side_active, true, long_stream);
-        if (rc == HV_OK) rc = short_phase(0);
-        if (rc == HV_OK && !long_first) rc = long_prepare_gate(l_, e->sideH, e->sidev, e->side_acol, e->side_active, true, main_stream);
-        }
-        if (forked) {
-            hipError_t he = hipEventRecord(e->ev_join, c->aux_stream);
-            if (he == hipSuccess) he = hipStreamWaitEvent(main_stream, e->ev_join, 0);
-            if (he != hipSuccess && rc == HV_OK) rc = hv::hip_fail(c, he, "join of the second stream");
-        }
-        if (rc != HV_OK) return rc;
-        const hv::CompactH ch{e->vuacol, s_.na_max, ncam, 0, 0, nullptr, cnt_inl, list_inl};
-        const ShortUpd short_upd = [&](hv::UpdateLaunch *defer) -> int {
-            return hv::ekf_launch_update(e, 2 * np_short * ncam, e->n, e->vuH, e->vuv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr, nullptr,
-                                         e->vuactive, gate_status_dev, success_counter_dev, 0.0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr,
-                                         nullptr, 0, nr_rec, &ch, rows, defer);
-        };
-        // knob ekf_dual_update (default 1): the short class's update shares a grid with the first block update of the long class (the two
-        // serve different filters)
-        const bool pair = c->knob.ekf_dual_update != 0;
-        if (!pair) { rc = short_upd(nullptr); if (rc != HV_OK) return rc; }
-        return long_updates(e->sideH, e->sidev, e->side_acol, e->side_active, e->side_dm, pair ? &short_upd : nullptr);
-    }
-    if (long_ok && np > np_short) {                            // every record of the launch may be long (uniform 12 .. 21 stereo poses, or ragged)
-        rc = ensure_long();
-        if (rc != HV_OK) return rc;
-        rc = long_prepare_gate(a, e->vuH, e->vuv, e->vuacol, e->vuactive, false, main_stream);
-        if (rc != HV_OK) return rc;
-        return long_updates(e->vuH, e->vuv, e->vuacol, e->vuactive, e->side_dm, nullptr);
-    }
-    if (hv::vu_fused_supported(c, e->n, np, a.stereo, e->batch)) {
-        // knob ekf_fused_gate: -1 auto / 1 = the gate inside the prepare launch (vu_gate kernels); 2 = its own launch (vu_compact kernels +
-        // ekf_sparse_gate_kernel, three 43 KB workgroups per CU). Measured at 1024 filters x 10 stereo poses (r03, scripts/vu_microbench.py):
-        // 156 us against 84 + 67 us per visit, and 9.0 against 9.25 ms for the chained C3 step -- the gate costs ~17 us of a CU per filter
-        // in either form (a 40-pivot Cholesky chain on one wave + 430 MFMAs at low occupancy), so the form with one launch and no round trip
-        // of Hc through HBM stays the default at every batch size.
-        const int fg = c->knob.ekf_fused_gate;
-        const bool split_gate = fg == 2;
-        if (split_gate && (a.rmse_thr >= 0.0 || a.gate_scale)) return HV_ERR_UNSUPPORTED;   // (adaptive thresholds: fused gates only)
-        a.fused = split_gate ? 2 : 1; a.H = nullptr; a.Hc = e->vuH; a.acol = e->vuacol; a.na_max = 7 * np + 1; a.P = e->P;
-        a.rd_gate = r_gate * r_gate * ns; a.noise_scale = ns; a.chi2 = chi2_dev;
-        if (!split_gate) { a.inl_count = cnt_inl; a.inl_list = list_inl; }
-        { int rc_s = HV_OK; rc = (!split_gate && split_launch(a, main_stream, &rc_s)) ? rc_s : hv::launch_vu_prepare(c, a); }
-        if (rc != HV_OK) return rc;
-        if (split_gate) {
-            rc = hv::ekf_launch_sparse_gate(e, np, a.stereo ? 2 : 1, e->vuH, e->vuv, e->vuacol, nr_rec, e->vuactive, a.rd_gate, chi2_dev, gate_status_dev,
-                                            nullptr, nullptr, cnt_inl, list_inl);
-            if (rc != HV_OK) return rc;
-        }
-        const hv::CompactH ch{e->vuacol, a.na_max, a.stereo ? 2 : 1, 0, 0, nullptr, cnt_inl, list_inl};
-        return hv::ekf_launch_update(e, rows, e->n, e->vuH, e->vuv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr, nullptr,
-                                     e->vuactive, gate_status_dev, success_counter_dev, 0.0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr,
-                                     nullptr, 0, nr_rec, &ch);
-    }
-    // (the dense kernels below know neither the RMSE test nor the per-filter threshold growth)
-    if (a.rmse_thr >= 0.0 || a.gate_scale) return HV_ERR_UNSUPPORTED;
-    rc = hv::launch_vu_prepare(c, a);
-    if (rc != HV_OK) return rc;
-    // Dense path (tracks of more than 48 rows, filters wider than 160, knob ekf_fused_gate = 0): visualTrackOutlierCheck with chiOutlierR,
-    // then updateVisualTrack with visualR where everything passed: one launch when the shape runs on the register-resident kernel
-    // (mode 3), otherwise a gate launch and an update launch.
-    // knob ekf_stream_gate = 1 (experiment): the streaming gate kernel (two filters per CU) for everybody, then the
-    // register-resident update where the gate passed. Measured at 1024 filters (r02): a rejected track costs 0.110 ms instead of the
-    // fused launch's 0.130, an accepted one 0.110 + 0.21 instead of 0.23.
-    if (c->knob.ekf_stream_gate == 1 && !nr_rec) {
-        bool done = false;
-        rc = hv::ekf_launch_gate_stream(e, rows, e->n, e->vuH, e->vuv, r_gate * r_gate * ns, chi2_dev, gate_status_dev, e->vuactive,
-                                        success_counter_dev, max_successful, &done);
-        if (rc != HV_OK) return rc;
-        if (done)
-            return hv::ekf_launch_update(e, rows, e->n, e->vuH, e->vuv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr,
-                                         nullptr, e->vuactive, gate_status_dev, success_counter_dev);
-    }
-    bool fused = false;
-    rc = hv::ekf_launch_update(e, rows, e->n, e->vuH, e->vuv, nullptr, r_gate * r_gate * ns, 3, 0, 1, chi2_dev,
-                               gate_status_dev, e->vuactive, nullptr, success_counter_dev, r_update * r_update * ns, &fused,
-                               0, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, nr_rec);
-    if (rc != HV_OK || fused) return rc;
-    rc = hv::ekf_launch_update(e, rows, e->n, e->vuH, e->vuv, nullptr, r_gate * r_gate * ns, 0, 0, 0, chi2_dev,
-                               gate_status_dev, e->vuactive, nullptr, nullptr, 0.0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, nr_rec);
-    if (rc != HV_OK) return rc;
-    return hv::ekf_launch_update(e, rows, e->n, e->vuH, e->vuv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr,
-                                 nullptr, e->vuactive, gate_status_dev, success_counter_dev, 0.0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr,
-                                 nullptr, 0, nr_rec);
-}
-
-
-// work buffers of the speculative frame loops and the batch loop: one record per (track, filter) -- compact or dense Jacobian, residual,
-// point, flags, column list, rows -- plus the per-filter cursors; grown on first use of a shape and never shrunk in either dimension
-// (r04 advisor: reallocating to exactly (rec, rows) let alternating shapes -- a short and a long frame, the speculative and the batch
-// loop -- free and allocate on every call, which a stream capture cannot hold)
-static int ensure_spec_buffers(Ekf *e, size_t rec, int rows)
-{
-    Ctx *c = e->c;
-    if (e->sp_records >= rec && e->sp_rows >= rows) return HV_OK;
-    rec = std::max(rec, e->sp_records); rows = std::max(rows, e->sp_rows);
-    const size_t B = (size_t)e->batch;
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    void *old[] = {e->spH, e->spv, e->sppf, e->spactive, e->spcursor, e->spepoch, e->spcursor2, e->sppub, e->spacol, e->sprows};
-    for (void *q : old) if (q) (void)hipFree(q);
-    e->spH = e->spv = e->sppf = nullptr; e->spactive = nullptr; e->spcursor = e->spepoch = e->spcursor2 = e->sppub = e->spacol = e->sprows = nullptr; e->sp_records = 0;
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->spH), sizeof(double) * rec * rows * e->n));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->spv), sizeof(double) * rec * rows));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->sppf), sizeof(double) * rec * 3));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->spactive), rec));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->spcursor), sizeof(int) * B));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->spepoch), sizeof(int) * rec));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->spcursor2), sizeof(int) * B));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->sppub), sizeof(int) * rec));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->spacol), sizeof(int) * rec * e->n));
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->sprows), sizeof(int) * rec));
-    e->sp_records = rec; e->sp_rows = rows;
-    return HV_OK;
-}
-
-static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np, const int *np_rec_dev, const int *idx,
-                                 const double *feat, const double *vel,
-                            const double *y, double r_gate, double r_update, int *status_dev, int *gate_status_dev, double *chi2_dev,
-                            double *pf_dev, int *success_counter_dev, int max_successful)
-{
-    if (!h || n_tracks < 0 || !success_counter_dev) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
-    // maxSuccessfulVisualUpdates <= 0 is the reference's "no limit" (backend.cpp:1233: the test is `> 0 && count >= max`): every track
-    // is visited, which a quota of n_tracks expresses exactly (r02 advisor)
-    if (max_successful <= 0 || max_successful > n_tracks) max_successful = n_tracks > 0 ? n_tracks : 1;
-    const size_t B = (size_t)e->batch, nt = (size_t)np * (p && p->useStereo ? 2 : 1);
-    HV_HIP(c, hipMemsetAsync(success_counter_dev, 0, sizeof(int) * B, c->stream));          // updateSuccessCount = 0 (backend.cpp:1017)
-    // adaptive outlier thresholds (backend.cpp:994-996,1192-1193): every filter starts the frame at the base thresholds; a rejected
-    // track multiplies its filter's thresholds for the tracks behind it. Kept per filter on the device, reset here.
-    const bool adaptive = p && p->trackOutlierThresholdGrowthFactor != 1.0;
-    struct ScaleScope { Ekf *e; ~ScaleScope() { e->gate_scale_on = false; } } scale_scope{e};
-    if (adaptive) {
-        if (!e->gate_scale) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->gate_scale), sizeof(double) * B));
-        hipLaunchKernelGGL(hv::fill_doubles_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, e->gate_scale, (int)B, 1.0);
-        HV_HIP(c, hipGetLastError());
-        e->gate_scale_on = true;
-    }
-    // Few sequences (one, for the reference's `main`): the frame is latency bound -- 20 dependent visits of a ~26 us prepare and a
-    // ~34 us gate. While the GPU has idle CUs the loop is run SPECULATIVELY instead: a pass prepares and gates
-    // EVERY pending track of a filter against the current (m, P) in parallel, applies the first inlier in visit order, and only the
-    // tracks behind it are re-examined: <= min(max_successful, n_tracks) + 1 passes, the same statuses and the same filter as the
-    // sequential loop (tracks in front of the first inlier saw the state they would have seen anyway).
-    const int rows = 2 * (int)nt;
-    // Long tracks (49 .. 84 rows; ragged frames whose longest track is that long: the reference's default stereo configuration, SURVEY
-    // app. B) -- r04, VERDICT r03 item 6: the same speculative loop with the long build of the fused prepare + gate launch serving EVERY
-    // pending record of whatever length (grid (filters, tracks), one 158 KB workgroup per CU while the chip is idle), and the first
-    // pending inlier applied by the two block-update launches of the long class: a record of at most 48 rows whole by the first of them,
-    // a longer one block by block (UpdateArgs::half_auto; sel_io hands the chosen track from the first launch to the second).
-    // <= quota + 1 passes of three launches instead of n_tracks visits of four.
-    if (!c->knob.ekf_no_speculation && !adaptive && n_tracks >= 2 && B * (size_t)n_tracks <= (size_t)c->num_cus && rows > 48 && p && idx && feat && vel && y &&
-        c->knob.ekf_spec_split == 0 && c->knob.ekf_spec_mode != 3 && c->knob.ekf_long_fused != 0 && visit_shape(e, np, p->useStereo != 0, p->useLinearTriangulation != 0).long_ok) {
-        const size_t rec = B * (size_t)n_tracks;
-        { const int rc_sp = ensure_spec_buffers(e, rec, rows); if (rc_sp != HV_OK) return rc_sp; }
-        if (!e->side_dm) {
-            HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->side_dm), sizeof(double) * (size_t)e->n * B));
-            HV_HIP(c, hipMemsetAsync(e->side_dm, 0, sizeof(double) * (size_t)e->n * B, c->stream));
-        }
-        HV_HIP(c, hipMemsetAsync(e->spcursor, 0, sizeof(int) * B, c->stream));
-        HV_HIP(c, hipMemsetAsync(e->spcursor2, 0xFF, sizeof(int) * B, c->stream));                // sel_io: -1
-        HV_HIP(c, hipMemsetAsync(e->spepoch, 0xFF, sizeof(int) * rec, c->stream));               // -1: nothing prepared yet
-        hv::VuPrepareArgs a;
-        int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
-        if (rc != HV_OK) return rc;
-        const double ns = e->noise_scale;
-        const int ncam = a.stereo ? 2 : 1;
-        a.H = nullptr; a.v = e->spv; a.f = nullptr; a.pf = pf_dev ? pf_dev : e->sppf; a.status = status_dev; a.active = e->spactive;
-        a.gate_status = gate_status_dev; a.success_counter = success_counter_dev; a.max_successful = max_successful;
-        a.spec_tracks = n_tracks; a.cursor = e->spcursor; a.epoch = e->spepoch;
-        const int *nr_rec = nullptr;
-        if (np_rec_dev) { a.np_rec = np_rec_dev; a.rows_out = e->sprows; nr_rec = e->sprows; }
-        a.fused = 3; a.Hc = e->spH; a.acol = e->spacol; a.na_max = 7 * np + 1; a.P = e->P;
-        a.rd_gate = r_gate * r_gate * ns; a.noise_scale = ns; a.chi2 = chi2_dev;
-        hv::CompactH h1{e->spacol, a.na_max, ncam, 1, rows, e->side_dm, nullptr, nullptr, gate_status_dev}, h2{e->spacol, a.na_max, ncam, 2, rows, e->side_dm};
-        h1.half_auto = h2.half_auto = 1; h1.sel_io = h2.sel_io = e->spcursor2; h2.epoch = e->spepoch;
-        const int n_pass = (max_successful < n_tracks ? max_successful : n_tracks) + 1;
-        for (int pass = 0; pass < n_pass; ++pass) {
-            rc = hv::launch_vu_prepare(c, a);
-            if (rc != HV_OK) return rc;
-            for (const hv::CompactH *hh : {&h1, &h2}) {
-                // (rows per launch: a whole short record of up to 48 rows, or the longer block -- 2 ceil(rows / 4) rows, the first camera's --
-                //  of a long one; 48 for everything visit_shape admits today, rows <= 96)
-                rc = hv::ekf_launch_update(e, std::max(48, 2 * ((rows + 3) / 4)), e->n, e->spH, e->spv, nullptr, r_update * r_update * ns, 1, 0, hh == &h1 ? -1 : 1, nullptr,
-                                           nullptr, e->spactive, nullptr, success_counter_dev, 0.0, nullptr, 2, n_tracks, e->spcursor, max_successful,
-                                           gate_status_dev, nullptr, nullptr, 0, nr_rec, hh, rows);
-                if (rc != HV_OK) return rc;
-            }
-        }
-        return HV_OK;
-    }
-    // (a growth factor != 1 makes the threshold of a track depend on the verdicts of the tracks in front of it: no parallel gating)
-    if (!c->knob.ekf_no_speculation && !adaptive && n_tracks >= 2 && B * (size_t)n_tracks <= 256 && e->n <= 160 && rows <= 48 && p && idx && feat && vel && y) {
-        const size_t rec = B * (size_t)n_tracks;
-        { const int rc_sp = ensure_spec_buffers(e, rec, rows); if (rc_sp != HV_OK) return rc_sp; }
-        HV_HIP(c, hipMemsetAsync(e->spcursor, 0, sizeof(int) * B, c->stream));
-        HV_HIP(c, hipMemsetAsync(e->spcursor2, 0, sizeof(int) * B, c->stream));                   // (ping-pong partner: never read uninitialised)
-        HV_HIP(c, hipMemsetAsync(e->spepoch, 0xFF, sizeof(int) * rec, c->stream));               // -1: nothing prepared yet
-        hv::VuPrepareArgs a;
-        int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
-        if (rc != HV_OK) return rc;
-        a.H = e->spH; a.v = e->spv; a.f = nullptr; a.pf = pf_dev ? pf_dev : e->sppf; a.status = status_dev; a.active = e->spactive;
-        a.gate_status = gate_status_dev; a.success_counter = success_counter_dev; a.max_successful = max_successful;
-        a.spec_tracks = n_tracks; a.cursor = e->spcursor; a.epoch = e->spepoch;
-        const int *nr_rec = nullptr;                                  // ragged: per-record rows, written by the prepare launches
-        if (np_rec_dev) { a.np_rec = np_rec_dev; a.rows_out = e->sprows; nr_rec = e->sprows; }
-        const double ns = e->noise_scale;
-        const int n_pass = (max_successful < n_tracks ? max_successful : n_tracks) + 1;
-        // Pass forms (knob ekf_spec_mode; -1 = auto):
-        //   2  (r03 default where the fused gate serves the shape) launch A: every pending track prepared AND gated on its active columns
-        //      (vu_gate kernel, grid (filters, tracks)); launch B: per filter the first pending inlier is applied, the cursor moves behind it.
-        //      No hand-shake between workgroups: what a pass computes does not depend on how the dispatcher places them.
-        //   3  (r02) dense prepare, then ONE launch that gates every pending track and lets the first inlier apply itself after a spin-wait
-        //      on the decisions in front of it. A wait that times out raises the filter batch's error word (hv_ekf_frame_error).
-        //   knob ekf_spec_split = 1: dense prepare + dense gate-all + apply (the first r02 form).
-        const int spec_mode = c->knob.ekf_spec_mode;
-        const bool split = c->knob.ekf_spec_split != 0;
-        if (!split && spec_mode != 3 && hv::vu_fused_supported(c, e->n, np, a.stereo, e->batch)) {
-            a.fused = 1; a.H = nullptr; a.Hc = e->spH; a.acol = e->spacol; a.na_max = 7 * np + 1; a.P = e->P;
-            a.rd_gate = r_gate * r_gate * ns; a.noise_scale = ns; a.chi2 = chi2_dev;
-            const hv::CompactH ch{e->spacol, a.na_max, a.stereo ? 2 : 1};
-            for (int pass = 0; pass < n_pass; ++pass) {
-                rc = hv::launch_vu_prepare(c, a);
-                if (rc != HV_OK) return rc;
-                rc = hv::ekf_launch_update(e, rows, e->n, e->spH, e->spv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr,
-                                           nullptr, e->spactive, nullptr, success_counter_dev, 0.0, nullptr, 2, n_tracks, e->spcursor, max_successful,
-                                           gate_status_dev, nullptr, nullptr, 0, nr_rec, &ch);
-                if (rc != HV_OK) return rc;
-            }
-            return HV_OK;
-        }
-        if (a.rmse_thr >= 0.0) return HV_ERR_UNSUPPORTED;             // (the dense pass forms have no RMSE test)
-        if (!split) HV_HIP(c, hipMemsetAsync(e->sppub, 0, sizeof(int) * rec, c->stream));
-        int *cur = e->spcursor, *nxt = e->spcursor2;
-        for (int pass = 0; pass < n_pass; ++pass) {
-            a.cursor = cur;
-            rc = hv::launch_vu_prepare(c, a);
-            if (rc != HV_OK) return rc;
-            if (!split) {
-                bool fused = false;
-                rc = hv::ekf_launch_update(e, rows, e->n, e->spH, e->spv, nullptr, r_gate * r_gate * ns, 3, 0, 1, chi2_dev,
-                                           gate_status_dev, e->spactive, nullptr, success_counter_dev, r_update * r_update * ns, &fused,
-                                           3, n_tracks, cur, max_successful, nullptr, nxt, e->sppub, pass + 1, nr_rec);
-                if (rc != HV_OK) return rc;
-                if (fused) { int *sw = cur; cur = nxt; nxt = sw; continue; }
-                // (mode 3 not available for this shape: the two launches below, on the same cursor)
-            }
-            rc = hv::ekf_launch_update(e, rows, e->n, e->spH, e->spv, nullptr, r_gate * r_gate * ns, 0, 0, 0, chi2_dev,
-                                       gate_status_dev, e->spactive, nullptr, success_counter_dev, 0.0, nullptr, 1, n_tracks, cur, max_successful,
-                                       nullptr, nullptr, nullptr, 0, nr_rec);
-            if (rc != HV_OK) return rc;
-            rc = hv::ekf_launch_update(e, rows, e->n, e->spH, e->spv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr,
-                                       nullptr, e->spactive, nullptr, success_counter_dev, 0.0, nullptr, 2, n_tracks, cur, max_successful,
-                                       gate_status_dev, nullptr, nullptr, 0, nr_rec);
-            if (rc != HV_OK) return rc;
-        }
-        return HV_OK;
-    }
-    HV_HIP(c, hipMemsetAsync(e->visit_counts, 0, 4 * sizeof(int) * Ekf::VISIT_SLOTS, c->stream));
-    // ragged visits with two length classes: the short class's fused launches take their records longest track first (one sort per frame)
-    e->visit_order_ok = false;
-    // (many filters only: below one workgroup per CU nothing queues, and the sort, the fork and the join are pure launch overhead --
-    //  a single sequence went from 1.14 to 1.51 ms per frame with them)
-    if (p && np_rec_dev && c->knob.ekf_visit_order != 0 && n_tracks >= 1 && n_tracks <= Ekf::VISIT_SLOTS && (B > (size_t)c->num_cus || c->knob.ekf_visit_order == 2)) {
-        // (only where the visits really run as two length classes: 12 stereo poses = 48 rows still ride the short class -- r03 advisor)
-        const VisitShape shape = visit_shape(e, np, p->useStereo != 0, p->useLinearTriangulation != 0);
-        if (shape.two_class) {
-            const int rc = hv::launch_visit_order(c, n_tracks, B, np_rec_dev, 2, shape.np_short, np, e->visit_order, e->visit_long, e->visit_long_count);
-            if (rc != HV_OK) return rc;
-            e->visit_order_ok = true;
-        }
-    }
-    for (int k = 0; k < n_tracks; ++k) {
-        e->visit_slot = k;
-        const int rc = visual_track_dev_impl(h, p, np, idx + (size_t)k * B * np, feat + (size_t)k * B * nt * 2, vel + (size_t)k * B * nt * 2,
-                                             y + (size_t)k * B * nt * 2, r_gate, r_update, status_dev + (size_t)k * B * 2,
-                                             gate_status_dev + (size_t)k * B, chi2_dev ? chi2_dev + (size_t)k * B : nullptr,
-                                             pf_dev ? pf_dev + (size_t)k * B * 3 : nullptr, success_counter_dev, max_successful,
-                                             np_rec_dev ? np_rec_dev + (size_t)k * B : nullptr);
-        e->visit_slot = -1;
-        if (rc != HV_OK) { e->visit_order_ok = false; return rc; }
-    }
-    e->visit_order_ok = false;
-    return HV_OK;
-}
-
-int hv_ekf_visual_frame_dev(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np, const int *idx, const double *feat, const double *vel,
-                            const double *y, double r_gate, double r_update, int *status_dev, int *gate_status_dev, double *chi2_dev,
-                            double *pf_dev, int *success_counter_dev, int max_successful)
-{
-    return visual_frame_dev_impl(h, p, n_tracks, np, nullptr, idx, feat, vel, y, r_gate, r_update, status_dev, gate_status_dev, chi2_dev,
-                                 pf_dev, success_counter_dev, max_successful);
-}
-
-int hv_ekf_visual_frame_ragged_dev(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np_max, const int *n_poses_dev, const int *idx,
-                                   const double *feat, const double *vel, const double *y, double r_gate, double r_update,
-                                   int *status_dev, int *gate_status_dev, double *chi2_dev, double *pf_dev, int *success_counter_dev,
-                                   int max_successful)
-{
-    if (!n_poses_dev) return HV_ERR_INVALID;
-    return visual_frame_dev_impl(h, p, n_tracks, np_max, n_poses_dev, idx, feat, vel, y, r_gate, r_update, status_dev, gate_status_dev,
-                                 chi2_dev, pf_dev, success_counter_dev, max_successful);
-}
-
-// Session::trackerVisualUpdate with batchVisualUpdate (or a frame that is not a "full visual update": backend.cpp:1005): see
-// ekf_batch_assemble_kernel. <= min(quota, n_tracks) + 1 passes of (prepare + gate of every pending track | assemble | one dense update).
-int hv_ekf_visual_frame_batch_dev(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np, const int *np_rec_dev, const int *idx,
-                                  const double *feat, const double *vel, const double *y, double r_gate, double r_update,
-                                  int *status_dev, int *gate_status_dev, double *chi2_dev, double *pf_dev, int *success_counter_dev,
-                                  int max_successful, int max_update_rows)
-{
-    if (!h || !p || n_tracks < 1 || !success_counter_dev || !status_dev || !gate_status_dev || !idx || !feat || !vel || !y) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
-    const int ncam = p->useStereo ? 2 : 1, rows = 2 * np * ncam;
-    if (max_update_rows <= 0) max_update_rows = e->n;                        // batchVisualUpdateMaxSizeMultiplier 1 (parameter_definitions.c:17)
-    if (max_successful <= 0 || max_successful > n_tracks) max_successful = n_tracks;
-    // a batch holds at least one whole track (the reference would write past its batch matrix otherwise) and at most stateDim rows (the
-    // dense update kernels' limit); the per-filter multiplier of the outlier thresholds would need the tracks of a pass in sequence
-    if (max_update_rows < rows || max_update_rows > e->max_rows || n_tracks > 64) return HV_ERR_INVALID;
-    if (p->trackOutlierThresholdGrowthFactor != 1.0) return HV_ERR_UNSUPPORTED;
-    const size_t B = (size_t)e->batch, rec = B * (size_t)n_tracks;
-    if (rec > 8192) return HV_ERR_UNSUPPORTED;                               // (every record's compact Jacobian is resident during a pass)
-    const VisitShape shape = visit_shape(e, np, p->useStereo != 0, p->useLinearTriangulation != 0);
-    const bool long_build = rows > 48;
-    if (long_build ? !(shape.long_ok && c->knob.ekf_long_fused != 0) : !hv::vu_fused_supported(c, e->n, np, p->useStereo != 0, (int)rec)) return HV_ERR_UNSUPPORTED;
-    { const int rc_sp = ensure_spec_buffers(e, rec, rows); if (rc_sp != HV_OK) return rc_sp; }
-    if (e->b_rows < max_update_rows) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        void *old[] = {e->bH, e->bv, e->brows, e->bany};
-        for (void *q : old) if (q) (void)hipFree(q);
-        e->bH = e->bv = nullptr; e->brows = nullptr; e->bany = nullptr; e->b_rows = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->bH), sizeof(double) * B * max_update_rows * e->n));
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->bv), sizeof(double) * B * max_update_rows));
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->brows), sizeof(int) * B));
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->bany), B));
-        e->b_rows = max_update_rows;
-    }
-    HV_HIP(c, hipMemsetAsync(success_counter_dev, 0, sizeof(int) * B, c->stream));
-    HV_HIP(c, hipMemsetAsync(e->spcursor, 0, sizeof(int) * B, c->stream));
-    HV_HIP(c, hipMemsetAsync(e->spepoch, 0xFF, sizeof(int) * rec, c->stream));
-    HV_HIP(c, hipMemsetAsync(e->spcursor2, 0xFF, sizeof(int) * B, c->stream));               // carry: -1
-    hv::VuPrepareArgs a;
-    int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
-    if (rc != HV_OK) return rc;
-    const double ns = e->noise_scale;
-    a.H = nullptr; a.v = e->spv; a.f = nullptr; a.pf = pf_dev ? pf_dev : e->sppf; a.status = status_dev; a.active = e->spactive;
-    a.gate_status = gate_status_dev; a.success_counter = success_counter_dev; a.max_successful = max_successful;
-    a.spec_tracks = n_tracks; a.cursor = e->spcursor; a.epoch = e->spepoch;
-    const int *nr_rec = nullptr;
-    if (np_rec_dev) { a.np_rec = np_rec_dev; a.rows_out = e->sprows; nr_rec = e->sprows; }
-    a.fused = long_build ? 3 : 1; a.Hc = e->spH; a.acol = e->spacol; a.na_max = 7 * np + 1; a.P = e->P;
-    a.rd_gate = r_gate * r_gate * ns; a.noise_scale = ns; a.chi2 = chi2_dev;
-    hv::BatchAssembleArgs g{};
-    g.n = e->n; g.n_tracks = n_tracks; g.batch = e->batch; g.max_rows = max_update_rows; g.max_successful = max_successful;
-    g.rows_stride = rows; g.na_max = a.na_max; g.ncam = ncam; g.Hc = e->spH; g.v = e->spv; g.acol = e->spacol; g.nr_rec = nr_rec;
-    g.active = e->spactive; g.gate = gate_status_dev; g.cursor = e->spcursor; g.success_counter = success_counter_dev; g.carry = e->spcursor2;
-    g.Hd = e->bH; g.vd = e->bv; g.rows_out = e->brows; g.any_out = e->bany;
-    const int n_pass = max_successful + 1;
-    for (int pass = 0; pass < n_pass; ++pass) {
-        rc = hv::launch_vu_prepare(c, a);
-        if (rc != HV_OK) return rc;
-        hipLaunchKernelGGL(hv::ekf_batch_assemble_kernel, dim3(e->batch), dim3(hv::BATCH_THREADS), 0, c->stream, g);
-        HV_HIP(c, hipGetLastError());
-        rc = hv::ekf_launch_update(e, max_update_rows, e->n, e->bH, e->bv, nullptr, r_update * r_update * ns, 1, 0, 1, nullptr, nullptr, e->bany,
-                                   nullptr, nullptr, 0.0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, e->brows);
-        if (rc != HV_OK) return rc;
-    }
-    return HV_OK;
-}
-
-int hv_ekf_visual_track(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
-                        const double *y, double r_gate, double r_update, int *status, int *gate_status, double *chi2, double *pf)
-{
-    if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
-    const size_t B = (size_t)e->batch, nt = (size_t)np * (p->useStereo ? 2 : 1);
-    // one staging block, 16-byte aligned sections
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_idx = 0, o_feat = up(o_idx + B * np * sizeof(int)), o_vel = up(o_feat + B * nt * 2 * sizeof(double));
-    const size_t o_y = up(o_vel + B * nt * 2 * sizeof(double)), o_st = up(o_y + B * nt * 2 * sizeof(double));
-    const size_t o_gs = up(o_st + B * 2 * sizeof(int)), o_chi = up(o_gs + B * sizeof(int)), o_pf = up(o_chi + B * sizeof(double));
-    const size_t total = up(o_pf + B * 3 * sizeof(double));
-    if (e->vustage_bytes < total) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        if (e->vustage) (void)hipFree(e->vustage);
-        e->vustage = nullptr; e->vustage_bytes = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vustage), total));
-        e->vustage_bytes = total;
-    }
-    unsigned char *d = e->vustage;
-    HV_HIP(c, hipMemcpyAsync(d + o_idx, idx, B * np * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_feat, feat, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_vel, vel, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_y, y, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    int rc = hv_ekf_visual_track_dev(h, p, np, reinterpret_cast<const int *>(d + o_idx), reinterpret_cast<const double *>(d + o_feat),
-                                     reinterpret_cast<const double *>(d + o_vel), reinterpret_cast<const double *>(d + o_y), r_gate,
-                                     r_update, reinterpret_cast<int *>(d + o_st), reinterpret_cast<int *>(d + o_gs),
-                                     reinterpret_cast<double *>(d + o_chi), reinterpret_cast<double *>(d + o_pf));
-    if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(status, d + o_st, B * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(gate_status, d + o_gs, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, d + o_chi, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (pf) HV_HIP(c, hipMemcpyAsync(pf, d + o_pf, B * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    return HV_OK;
-}
-
-// batch_rows: 0 = the sequential visit loop (visual_frame_dev_impl); != 0 = the batchVisualUpdate loop with this max_update_rows (< 0: the
-// library's default, stateDim)
-static int visual_frame_host_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np, const int *n_poses, const int *idx,
-                                  const double *feat, const double *vel,
-                        const double *y, double r_gate, double r_update, int *status, int *gate_status, double *chi2, double *pf,
-                        int *success_count, int max_successful, int batch_rows = 0)
-{
-    if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2 || n_tracks < 1) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
-    const size_t B = (size_t)e->batch * n_tracks, nt = (size_t)np * (p->useStereo ? 2 : 1);
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_idx = 0, o_feat = up(o_idx + B * np * sizeof(int)), o_vel = up(o_feat + B * nt * 2 * sizeof(double));
-    const size_t o_y = up(o_vel + B * nt * 2 * sizeof(double)), o_st = up(o_y + B * nt * 2 * sizeof(double));
-    const size_t o_gs = up(o_st + B * 2 * sizeof(int)), o_chi = up(o_gs + B * sizeof(int)), o_pf = up(o_chi + B * sizeof(double));
-    const size_t o_cnt = up(o_pf + B * 3 * sizeof(double)), o_np = up(o_cnt + (size_t)e->batch * sizeof(int));
-    const size_t total = up(o_np + B * sizeof(int));
-    if (e->vustage_bytes < total) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        if (e->vustage) (void)hipFree(e->vustage);
-        e->vustage = nullptr; e->vustage_bytes = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vustage), total));
-        e->vustage_bytes = total;
-    }
-    unsigned char *d = e->vustage;
-    HV_HIP(c, hipMemcpyAsync(d + o_idx, idx, B * np * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_feat, feat, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_vel, vel, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_y, y, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (n_poses) HV_HIP(c, hipMemcpyAsync(d + o_np, n_poses, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    const int *d_np = n_poses ? reinterpret_cast<const int *>(d + o_np) : nullptr;
-    const int rc = batch_rows == 0
-        ? visual_frame_dev_impl(h, p, n_tracks, np, d_np,
-                                           reinterpret_cast<const int *>(d + o_idx), reinterpret_cast<const double *>(d + o_feat),
-                                           reinterpret_cast<const double *>(d + o_vel), reinterpret_cast<const double *>(d + o_y), r_gate, r_update,
-                                           reinterpret_cast<int *>(d + o_st), reinterpret_cast<int *>(d + o_gs), reinterpret_cast<double *>(d + o_chi),
-                                           reinterpret_cast<double *>(d + o_pf), reinterpret_cast<int *>(d + o_cnt), max_successful)
-        : hv_ekf_visual_frame_batch_dev(h, p, n_tracks, np, d_np, reinterpret_cast<const int *>(d + o_idx), reinterpret_cast<const double *>(d + o_feat),
-                                        reinterpret_cast<const double *>(d + o_vel), reinterpret_cast<const double *>(d + o_y), r_gate, r_update,
-                                        reinterpret_cast<int *>(d + o_st), reinterpret_cast<int *>(d + o_gs), reinterpret_cast<double *>(d + o_chi),
-                                        reinterpret_cast<double *>(d + o_pf), reinterpret_cast<int *>(d + o_cnt), max_successful,
-                                        batch_rows < 0 ? 0 : batch_rows);
-    if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(status, d + o_st, B * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(gate_status, d + o_gs, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, d + o_chi, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (pf) HV_HIP(c, hipMemcpyAsync(pf, d + o_pf, B * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (success_count) HV_HIP(c, hipMemcpyAsync(success_count, d + o_cnt, (size_t)e->batch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    int flags = 0;
-    const int rc2 = hv_ekf_frame_error(h, &flags);                // the hand-shake form of the speculative pass never fails silently
-    if (rc2 != HV_OK) return rc2;
-    return flags ? HV_ERR_TIMEOUT : HV_OK;
-}
-
-int hv_ekf_visual_frame(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np, const int *idx, const double *feat, const double *vel,
-                        const double *y, double r_gate, double r_update, int *status, int *gate_status, double *chi2, double *pf,
-                        int *success_count, int max_successful)
-{
-    return visual_frame_host_impl(h, p, n_tracks, np, nullptr, idx, feat, vel, y, r_gate, r_update, status, gate_status, chi2, pf,
-                                  success_count, max_successful);
-}
-
-int hv_ekf_visual_frame_ragged(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np_max, const int *n_poses, const int *idx,
-                               const double *feat, const double *vel, const double *y, double r_gate, double r_update, int *status,
-                               int *gate_status, double *chi2, double *pf, int *success_count, int max_successful)
-{
-    if (!n_poses) return HV_ERR_INVALID;
-    return visual_frame_host_impl(h, p, n_tracks, np_max, n_poses, idx, feat, vel, y, r_gate, r_update, status, gate_status, chi2, pf,
-                                  success_count, max_successful);
-}
-
-int hv_ekf_visual_frame_batch(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np_max, const int *n_poses, const int *idx,
-                              const double *feat, const double *vel, const double *y, double r_gate, double r_update, int *status,
-                              int *gate_status, double *chi2, double *pf, int *success_count, int max_successful, int max_update_rows)
-{
-    return visual_frame_host_impl(h, p, n_tracks, np_max, n_poses, idx, feat, vel, y, r_gate, r_update, status, gate_status, chi2, pf,
-                                  success_count, max_successful, max_update_rows > 0 ? max_update_rows : -1);
-}
-
-// host-pointer form of hv_ekf_visual_track_hybrid_dev: one track per filter, arrays [batch]...
-int hv_ekf_visual_track_hybrid(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel, const double *y,
-                               const int *map_update, const int *map_offer, double r_gate, double r_update, int *status, int *gate_status,
-                               double *chi2, double *pf)
-{
-    if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
-    const size_t B = (size_t)e->batch, nt = (size_t)np * (p->useStereo ? 2 : 1);
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_idx = 0, o_feat = up(o_idx + B * np * sizeof(int)), o_vel = up(o_feat + B * nt * 2 * sizeof(double));
-    const size_t o_y = up(o_vel + B * nt * 2 * sizeof(double)), o_st = up(o_y + B * nt * 2 * sizeof(double));
-    const size_t o_gs = up(o_st + B * 2 * sizeof(int)), o_chi = up(o_gs + B * sizeof(int)), o_pf = up(o_chi + B * sizeof(double));
-    const size_t o_mu = up(o_pf + B * 3 * sizeof(double)), o_mo = up(o_mu + B * sizeof(int)), total = up(o_mo + B * sizeof(int));
-    if (e->vustage_bytes < total) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        if (e->vustage) (void)hipFree(e->vustage);
-        e->vustage = nullptr; e->vustage_bytes = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vustage), total));
-        e->vustage_bytes = total;
-    }
-    unsigned char *d = e->vustage;
-    HV_HIP(c, hipMemcpyAsync(d + o_idx, idx, B * np * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_feat, feat, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_vel, vel, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_y, y, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (map_update) HV_HIP(c, hipMemcpyAsync(d + o_mu, map_update, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    if (map_offer) HV_HIP(c, hipMemcpyAsync(d + o_mo, map_offer, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    const int rc = hv_ekf_visual_track_hybrid_dev(h, p, np, reinterpret_cast<const int *>(d + o_idx), reinterpret_cast<const double *>(d + o_feat),
-                                                  reinterpret_cast<const double *>(d + o_vel), reinterpret_cast<const double *>(d + o_y),
-                                                  map_update ? reinterpret_cast<const int *>(d + o_mu) : nullptr,
-                                                  map_offer ? reinterpret_cast<const int *>(d + o_mo) : nullptr, r_gate, r_update,
-                                                  reinterpret_cast<int *>(d + o_st), reinterpret_cast<int *>(d + o_gs),
-                                                  reinterpret_cast<double *>(d + o_chi), reinterpret_cast<double *>(d + o_pf));
-    if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(status, d + o_st, B * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(gate_status, d + o_gs, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, d + o_chi, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (pf) HV_HIP(c, hipMemcpyAsync(pf, d + o_pf, B * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    return HV_OK;
 }
 
 // insertMapPoint (ekf.cpp:911-921) on the resident state of one filter: nothing but the three coordinates crosses the bus
@@ -3601,8 +2583,10 @@ int hv_ekf_update(hv_ekf *h, int nr, int l, const double *H, const double *y, co
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
     int rc = stage_update_inputs(e, nr, l, H, y, r_diag, active);
     if (rc != HV_OK) return rc;
-    return hv::ekf_launch_update(e, nr, l, e->sH, e->sv, e->sr, 0.0, 1, 1, normalize_all, nullptr, nullptr,
-                                 active ? e->sactive : nullptr);
+    hv::UpdateRequest rq;
+    rq.nr = nr; rq.l = l; rq.H_dev = e->sH; rq.v_dev = e->sv; rq.rdiag_dev = e->sr; rq.mode = 1; rq.generic = 1; rq.normalize_all = normalize_all;
+    if (active) rq.active_dev = e->sactive;
+    return hv::ekf_launch_update(e, rq);
 }
 
 int hv_ekf_visual_gate(hv_ekf *h, int nr, int l, const double *H, const double *v, double r, double *chi2, int *status)
@@ -3612,7 +2596,7 @@ int hv_ekf_visual_gate(hv_ekf *h, int nr, int l, const double *H, const double *
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
     int rc = stage_update_inputs(e, nr, l, H, v, nullptr, nullptr);
     if (rc != HV_OK) return rc;
-    rc = hv::ekf_launch_update(e, nr, l, e->sH, e->sv, nullptr, r * r * e->noise_scale, 0, 0, 0, e->schi2, e->sstatus, nullptr);
+    rc = hv::ekf_launch_update(e, hv::gate_request(nr, l, e->sH, e->sv, r * r * e->noise_scale, e->schi2, e->sstatus));
     if (rc != HV_OK) return rc;
     if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, e->schi2, sizeof(double) * e->batch, hipMemcpyDeviceToHost, c->stream));
     if (status) HV_HIP(c, hipMemcpyAsync(status, e->sstatus, sizeof(int) * e->batch, hipMemcpyDeviceToHost, c->stream));
@@ -3627,8 +2611,7 @@ int hv_ekf_visual_update(hv_ekf *h, int nr, int l, const double *H, const double
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
     int rc = stage_update_inputs(e, nr, l, H, v, nullptr, active);
     if (rc != HV_OK) return rc;
-    return hv::ekf_launch_update(e, nr, l, e->sH, e->sv, nullptr, r * r * e->noise_scale, 1, 0, 1, nullptr, nullptr,
-                                 active ? e->sactive : nullptr);
+    return hv::ekf_launch_update(e, hv::inlier_update_request(nr, l, e->sH, e->sv, r * r * e->noise_scale, active ? e->sactive : nullptr));
 }
 
 int hv_ekf_visual_dev(hv_ekf *h, int nr, int l, const double *H_dev, const double *v_dev, double r, int mode,
@@ -3639,29 +2622,40 @@ int hv_ekf_visual_dev(hv_ekf *h, int nr, int l, const double *H_dev, const doubl
     const int stream_gate = e->c->knob.ekf_stream_gate;
     if (mode == 0 && (stream_gate == 1 || (stream_gate < 0 && e->batch > 256))) {      // gate only, many filters: two per CU
         bool done = false;
-        const int rc = hv::ekf_launch_gate_stream(e, nr, l, H_dev, v_dev, r * r * e->noise_scale, chi2_dev, status_dev, nullptr, nullptr, 0, &done);
+        hv::GateStreamRequest g;
+        g.nr = nr; g.l = l; g.H_dev = H_dev; g.v_dev = v_dev; g.rd = r * r * e->noise_scale; g.chi2_dev = chi2_dev; g.status_dev = status_dev; g.done = &done;
+        const int rc = hv::ekf_launch_gate_stream(e, g);
         if (rc != HV_OK || done) return rc;
     }
-    return hv::ekf_launch_update(e, nr, l, H_dev, v_dev, nullptr, r * r * e->noise_scale, mode, 0, 1, chi2_dev, status_dev, nullptr);
+    hv::UpdateRequest rq = hv::gate_request(nr, l, H_dev, v_dev, r * r * e->noise_scale, chi2_dev, status_dev);
+    rq.mode = mode; rq.normalize_all = 1;
+    return hv::ekf_launch_update(e, rq);
+}
+
+// the arguments of an augmentation that do not depend on the entry (dropped0 = -1, no `dropped` / `active` arrays) and its dynamic LDS
+static size_t augment_fill(const Ekf *e, hv::AugmentArgs &a)
+{
+    a = hv::AugmentArgs{};
+    a.n = e->n; a.cam_poses = e->cam; a.map_dim = e->map_dim;
+    a.m = e->m; a.P = e->P; a.P1 = e->P1; a.m1 = e->m1;
+    a.dropped0 = -1;
+    a.q_pos = e->par.noiseInitialPosTrail * e->par.noiseInitialPosTrail * e->noise_scale;
+    a.q_ori = e->par.noiseInitialOriTrail * e->par.noiseInitialOriTrail * e->noise_scale;
+    a.rd = e->par.augmentR * e->noise_scale;
+    return sizeof(double) * (3 * hv::POSE * e->n + 2 * hv::POSE * hv::POSE + hv::POSE + 1 + (hv::AUG_THREADS / 64) * 16 * 17);
 }
 
 int hv_ekf_augment(hv_ekf *h, const int *discarded, const unsigned char *active)
 {
     if (!h) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    hv::AugmentArgs a{};
-    a.n = e->n; a.cam_poses = e->cam; a.map_dim = e->map_dim;
-    a.m = e->m; a.P = e->P; a.P1 = e->P1; a.m1 = e->m1;
-    a.dropped0 = -1;
+    hv::AugmentArgs a;
+    const size_t shmem = augment_fill(e, a);
     if (discarded) {
         if (e->batch == 1) a.dropped0 = discarded[0];
         else { HV_HIP(c, hipMemcpyAsync(e->sdrop, discarded, sizeof(int) * e->batch, hipMemcpyHostToDevice, c->stream)); a.dropped = e->sdrop; }
     }
     if (active) { HV_HIP(c, hipMemcpyAsync(e->sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); a.active = e->sactive; }
-    a.q_pos = e->par.noiseInitialPosTrail * e->par.noiseInitialPosTrail * e->noise_scale;
-    a.q_ori = e->par.noiseInitialOriTrail * e->par.noiseInitialOriTrail * e->noise_scale;
-    a.rd = e->par.augmentR * e->noise_scale;
-    const size_t shmem = sizeof(double) * (3 * hv::POSE * e->n + 2 * hv::POSE * hv::POSE + hv::POSE + 1 + (hv::AUG_THREADS / 64) * 16 * 17);
     if (shmem > 64 * 1024) {                 // state vectors with map points (n > ~190): beyond the default dynamic-LDS limit
         if (shmem > 158 * 1024) return HV_ERR_UNSUPPORTED;
         static bool aug_attr_set_dev[64] = {};
@@ -3682,14 +2676,9 @@ static int augment_dev_impl(hv_ekf *h, const int *discarded_dev, const unsigned 
 {
     if (!h) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    hv::AugmentArgs a{};
-    a.n = e->n; a.cam_poses = e->cam; a.map_dim = e->map_dim;
-    a.m = e->m; a.P = e->P; a.P1 = e->P1; a.m1 = e->m1;
-    a.dropped0 = -1; a.dropped = discarded_dev; a.active = active_dev;
-    a.q_pos = e->par.noiseInitialPosTrail * e->par.noiseInitialPosTrail * e->noise_scale;
-    a.q_ori = e->par.noiseInitialOriTrail * e->par.noiseInitialOriTrail * e->noise_scale;
-    a.rd = e->par.augmentR * e->noise_scale;
-    const size_t shmem = sizeof(double) * (3 * hv::POSE * e->n + 2 * hv::POSE * hv::POSE + hv::POSE + 1 + (hv::AUG_THREADS / 64) * 16 * 17);
+    hv::AugmentArgs a;
+    const size_t shmem = augment_fill(e, a);
+    a.dropped = discarded_dev; a.active = active_dev;
     if (shmem > 64 * 1024) return HV_ERR_UNSUPPORTED;        // map-point states: use hv_ekf_augment (it raises the LDS limit)
     hv::ScopedKernelTime tm(c, HV_K_EKF_AUGMENT);
     if (sym_input) hipLaunchKernelGGL(hv::ekf_augment_kernel<true>, dim3(e->batch), dim3(hv::AUG_THREADS), shmem, c->stream, a);

@@ -66,7 +66,7 @@ struct Knobs {
     int ingest_gather = 0;        // HV_INGEST_GATHER: 1 = plain gather kernel for the remap
     int ekf_fused_gate = -1;      // HV_EKF_FUSED_GATE: column-sparse chi2 gate: -1 auto = 1 inside the prepare kernel, 2 own launch (ekf_sparse_gate_kernel), 0 off (dense kernels)
     int ekf_spec_mode = -1;       // HV_EKF_SPEC_MODE: speculative pass form: -1 auto, 2 = gate launch + apply launch, 3 = one launch with hand-shake
-    int ekf_side_stream = 6;      // HV_EKF_SIDE_STREAM, ragged visits with two length classes inside a frame loop over more filters than CUs (needs the per-frame sort of launch_visit_order): 0 = one stream; 6 (default of hv_create) = the visit forks: long class's prepare + gate launch on the context stream, short class's fused launch on the context's second stream, joined in front of the update launches (+6 % on the realistic C3 step against 0); 3 = r03's arrangement of the fork (long class on the second stream, enqueued first: 3 % slower than 6 with eager launches, equal under graph replay); 5 (default of the contexts of an hv_lanes set) = 6, but never inside a stream capture (a captured fork is replayed on a default-priority stream of the graph instance, not on the lane's own: ekf.hip). r03's other forms (1, 2, 4: whole long chain on the second stream / enqueued behind) measured slower and were removed in r04
+    int ekf_side_stream = 6;      // HV_EKF_SIDE_STREAM, ragged visits with two length classes inside a frame loop over more filters than CUs (needs the per-frame sort of launch_visit_order): 0 = one stream; 6 (default of hv_create) = the visit forks: long class's prepare + gate launch on the context stream, short class's fused launch on the context's second stream, joined in front of the update launches (+6 % on the realistic C3 step against 0); 3 = r03's arrangement of the fork (long class on the second stream, enqueued first: 3 % slower than 6 with eager launches, equal under graph replay); 5 (default of the contexts of an hv_lanes set) = 6, but never inside a stream capture (a captured fork is replayed on a default-priority stream of the graph instance, not on the lane's own: ekf_visit.hip). r03's other forms (1, 2, 4: whole long chain on the second stream / enqueued behind) measured slower and were removed in r04
     int ekf_long_fused = 1;       // HV_EKF_LONG_FUSED: 1 (r04 default) = prepare + column-sparse gate of the long class (49 .. 84 rows) in ONE launch (vu_gate_long_kernel); 0 = r03's vu_compact_kernel + ekf_sparse_gate_big_kernel
     int ekf_predict_chain = 1;    // HV_EKF_PREDICT_CHAIN: 1 (late r06) = launches of >= 3 IMU samples run ekf_predict_chain_kernel (the samples' mean recursion on one wavefront without workgroup barriers, dR / F / L of up to five samples per pass, then the 20 x 20 recursions); 2 = every launch; 0 = ekf_predict_kernel (nine barrier-separated stages per sample). Bit-identical
     int ekf_short_np = 12;        // HV_EKF_SHORT_NP: longest stereo track of the short class where the split form serves the visit: 12 (48 rows, r06 default) or 11 (the fused builds' boundary, r03 .. r05)
@@ -90,7 +90,7 @@ struct Ctx {
     bool own_stream = false;
     // second stream of the context, library-owned, created WITH the context (r04; r03 created it lazily inside the first ragged visit,
     // so which hardware queue it landed on depended on what the process had done by then): the long-track class of a ragged visit
-    // runs its prepare + gate launches on it beside the short class's launch on `stream` (ekf.hip), joined again inside the visit
+    // runs its prepare + gate launches on it beside the short class's launch on `stream` (ekf_visit.hip), joined again inside the visit
     hipStream_t aux_stream = nullptr;
     int stream_priority = 0;              // 0: default priority; 1: both streams from the device's HIGH-priority queue pool (hv_lanes_create)
     int num_cus = 256;                    // multiProcessorCount of the device
@@ -187,7 +187,7 @@ struct VuPrepareArgs {
     int *gate_status;                  // optional [batch]: preset to VuOutlierStatus::NOT_COMPUTED (1)
     const int *success_counter;        // optional [batch]: filters that already applied max_successful updates this frame are skipped
     int max_successful;
-    // speculative frame loop (ekf.hip, hv_ekf_visual_frame_dev): grid (batch, spec_tracks), every array a [track][filter] record.
+    // speculative frame loop (ekf_visit.hip, hv_ekf_visual_frame_dev): grid (batch, spec_tracks), every array a [track][filter] record.
     // A record is prepared when its track is pending (>= cursor[filter]) and was last prepared at another update count (epoch).
     int spec_tracks;
     const int *cursor;                 // [batch]

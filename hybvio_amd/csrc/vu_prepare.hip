@@ -1685,7 +1685,7 @@ bool vu_fused_supported(const Ctx *c, int n_state, int np, int stereo, int batch
 
 // shapes the split form serves: iterative triangulation of pose-trail tracks, no speculation; the record-fed short-class gate holds
 // stereo tracks of up to 12 poses (its staged Jacobian is 88 x 48 doubles), the long-class gate everything vu_gate_long_kernel does
-// vu_split_short_ok: what a caller knows before the arguments of a launch exist (ekf.hip visit_shape: where the short class ends)
+// vu_split_short_ok: what a caller knows before the arguments of a launch exist (ekf_visit.hip visit_shape: where the short class ends)
 bool vu_split_short_ok(const Ctx *c, int n_state, bool stereo, int batch, bool linear)
 {
     // (knob value 2: at every batch size -- tests; 1: where the two-per-CU fused build would run)
