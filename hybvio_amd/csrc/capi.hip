@@ -135,20 +135,15 @@ int compute_layout(const hv_params &p, PyrLayout &L)
     return HV_OK;
 }
 
-int ensure_point_staging(Ctx *c, int n)
-{
-    if (n <= c->stage_points) return HV_OK;
-    int cap = c->stage_points ? c->stage_points : 256;
-    while (cap < n) cap *= 2;
-    if (c->d_prev_xy) { (void)hipFree(c->d_prev_xy); (void)hipFree(c->d_next_xy); (void)hipFree(c->d_err); (void)hipFree(c->d_status); }
-    c->d_prev_xy = c->d_next_xy = c->d_err = nullptr; c->d_status = nullptr; c->stage_points = 0;
-    HV_HIP(c, hipMalloc(&c->d_prev_xy, sizeof(float) * 2 * cap));
-    HV_HIP(c, hipMalloc(&c->d_next_xy, sizeof(float) * 2 * cap));
-    HV_HIP(c, hipMalloc(&c->d_err, sizeof(float) * cap));
-    HV_HIP(c, hipMalloc(&c->d_status, cap));
-    c->stage_points = cap;
-    return HV_OK;
-}
+// staging sections of hv_klt_track for n points; hv_create reserves them for max_tracks points, so that the first frame of a
+// session allocates nothing
+struct KltStage {
+    Stage s;
+    StageSection<float> prev, next, err;
+    StageSection<uint8_t> status;
+    KltStage(Ctx *c, int n)
+        : s(c), prev(s.take<float>(2 * (size_t)n)), next(s.take<float>(2 * (size_t)n)), err(s.take<float>(n)), status(s.take<uint8_t>(n)) {}
+};
 
 bool slot_ok(Ctx *c, int s) { return s >= 0 && s < c->p.pool_size && c->slot_used[s]; }
 
@@ -331,7 +326,7 @@ static int create_ctx(const hv_params *params, int high_priority, hv_ctx **out)
         if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = HV_ERR_HIP; break; }      // the context stream has run its first command
         c->slot_used.assign(p.pool_size, 0);
         for (int s = p.pool_size - 1; s >= 0; --s) c->free_slots.push_back(s);
-        rc = hv::ensure_point_staging(c, p.max_tracks);
+        rc = hv::KltStage(c, p.max_tracks).s.reserve();
         if (rc == HV_OK) rc = hv::fill_gradient_borders(c, 0, p.pool_size);
         if (rc == HV_OK) rc = hv::rot_ransac_alloc_split(c);     // (r05 advisor: once, here -- never inside a launch that may be under capture)
         if (rc == HV_OK) rc = hv::ransac5_init(c);
@@ -392,17 +387,8 @@ void hv_destroy(hv_ctx *h)
     if (c->d_l0_ptr) (void)hipFree(c->d_l0_ptr);
     if (c->d_l0_stride) (void)hipFree(c->d_l0_stride);
     if (c->d_slots) (void)hipFree(c->d_slots);
-    if (c->d_prev_xy) (void)hipFree(c->d_prev_xy);
-    if (c->d_next_xy) (void)hipFree(c->d_next_xy);
-    if (c->d_err) (void)hipFree(c->d_err);
-    if (c->d_status) (void)hipFree(c->d_status);
-    if (c->d_gftt_kp) (void)hipFree(c->d_gftt_kp);
-    if (c->d_ingest_stage) (void)hipFree(c->d_ingest_stage);
-    if (c->d_ransac_stage) (void)hipFree(c->d_ransac_stage);
+    if (c->d_stage) (void)hipFree(c->d_stage);
     if (c->d_ransac_split) (void)hipFree(c->d_ransac_split);
-    if (c->d_subpix_stage) (void)hipFree(c->d_subpix_stage);
-    if (c->d_r5_stage) (void)hipFree(c->d_r5_stage);
-    if (c->d_gate_stage) (void)hipFree(c->d_gate_stage);
     for (int k = 0; k < HV_INGEST_CAMERAS; ++k)
         if (c->d_tile_box[k]) (void)hipFree(c->d_tile_box[k]);
     for (int k = 0; k < HV_INGEST_CAMERAS; ++k)
@@ -534,21 +520,23 @@ int hv_klt_track(hv_ctx *h, int prev_slot, int next_slot, int n, const float *pr
     if (!prev_xy || !next_xy || !status) return HV_ERR_INVALID;
     Ctx *c = &h->c;
     if (!hv::slot_ok(c, prev_slot) || !hv::slot_ok(c, next_slot)) return HV_ERR_POOL;
-    int rc = hv::ensure_point_staging(c, n);
+    hv::KltStage ks(c, n);
+    int rc = ks.s.reserve();
     if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(c->d_prev_xy, prev_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    float *d_prev = ks.s.at(ks.prev), *d_next = ks.s.at(ks.next), *d_err = ks.s.at(ks.err);
+    uint8_t *d_status = ks.s.at(ks.status);
+    HV_HIP(c, hipMemcpyAsync(d_prev, prev_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
     if (use_initial_flow)
-        HV_HIP(c, hipMemcpyAsync(c->d_next_xy, next_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        HV_HIP(c, hipMemcpyAsync(d_next, next_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
     hv::IntPack pk{{prev_slot, next_slot, 0, 0}};
     hipLaunchKernelGGL(hv::set_ints_kernel, dim3(1), dim3(64), 0, c->stream, c->d_slots + 2, pk, 2);
     HV_HIP(c, hipGetLastError());
     const int iters = max_iter_override > 0 ? max_iter_override : c->p.max_iter;
-    rc = hv::launch_klt(c, 1, c->d_slots + 2, c->d_slots + 3, n, n, c->d_prev_xy, c->d_next_xy,
-                        c->d_status, err ? c->d_err : nullptr, use_initial_flow, iters);
+    rc = hv::launch_klt(c, 1, c->d_slots + 2, c->d_slots + 3, n, n, d_prev, d_next, d_status, err ? d_err : nullptr, use_initial_flow, iters);
     if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(next_xy, c->d_next_xy, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, c->stream));
-    if (err) HV_HIP(c, hipMemcpyAsync(err, c->d_err, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(next_xy, d_next, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c->stream));
+    if (err) HV_HIP(c, hipMemcpyAsync(err, d_err, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }

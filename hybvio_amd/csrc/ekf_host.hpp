@@ -1,8 +1,6 @@
 // Host side of the EKF shared by ekf.hip (kernels, their launchers, the one-launch entries) and ekf_visit.hip (track visits, frame
-// loops, host-pointer staging): the filter object, the launch requests, the buffer-growth helper. Plain C++ and HIP host types, no kernel.
+// loops, host-pointer staging): the filter object, the launch requests. Plain C++ and HIP host types, no kernel.
 #pragma once
-#include <initializer_list>
-
 #include "hv_internal.hpp"
 
 namespace hv {
@@ -30,9 +28,6 @@ struct Ekf {
     int *spcursor = nullptr, *spepoch = nullptr;
     int *spcursor2 = nullptr, *sppub = nullptr;           // fused gate + apply passes: second cursor (ping-pong), published decisions
     size_t sp_records = 0; int sp_rows = 0;
-    // device staging of the host-pointer entry hv_ekf_visual_track: idx | features | velocities | y | status | gate | chi2 | pf
-    unsigned char *vustage = nullptr;
-    size_t vustage_bytes = 0;
     // fused prepare + gate (compact Jacobians live in vuH / spH): the active-column lists of the records
     int *vuacol = nullptr, *spacol = nullptr;
     // long-track classes of a ragged visit (ekf_visit.hip, Visit): own stream, events, Jacobian / residual / active buffers
@@ -148,21 +143,6 @@ int ekf_launch_update(Ekf *e, const UpdateRequest &rq);
 int ekf_launch_update_paired(Ekf *e, const UpdateRequest &us, const UpdateRequest &b1, const UpdateRequest &b2, bool *done);
 int ekf_launch_gate_stream(Ekf *e, const GateStreamRequest &rq);
 int ekf_launch_sparse_gate(Ekf *e, const SparseGateRequest &rq);
-
-// Growing device buffers: drains `drain` (in order, before anything is freed), frees and nulls every slot, allocates them again at
-// their new sizes. The caller tests whether growth is needed, zeroes the group's capacity field before the call and sets it after
-// an HV_OK, so that a failure in the middle leaves a group that reads as empty.
-struct GrowSlot {
-    void **slot; size_t bytes;
-    template <class T> GrowSlot(T *&p, size_t b) : slot(reinterpret_cast<void **>(&p)), bytes(b) {}
-};
-inline int grow_buffers(Ctx *c, std::initializer_list<hipStream_t> drain, std::initializer_list<GrowSlot> slots)
-{
-    for (hipStream_t s : drain) HV_HIP(c, hipStreamSynchronize(s));
-    for (const GrowSlot &g : slots) if (*g.slot) { (void)hipFree(*g.slot); *g.slot = nullptr; }
-    for (const GrowSlot &g : slots) HV_HIP(c, hipMalloc(g.slot, g.bytes));
-    return HV_OK;
-}
 
 }  // namespace hv
 

@@ -843,34 +843,28 @@ int hv_ekf_visual_frame_batch_dev(hv_ekf *h, const hv_vu_params *p, int n_tracks
     return HV_OK;
 }
 
-// Device staging of the host-pointer entries: one block (Ekf::vustage) of 16-byte aligned sections
-//     idx | features | velocities | y | status | gate | chi2 | pf | the entry's own sections (`own`, own_bytes)
-// for B records of np poses; the four inputs are uploaded here, the four outputs come back through download()
+// Device staging of the host-pointer entries in the context's arena (hv::Stage): the eight shared sections
+//     idx | features | velocities | y | status | gate | chi2 | pf
+// for B records of np poses, behind whatever sections of its own the entry took from `stage` before upload(); the four inputs are
+// uploaded here, the four outputs come back through download()
 struct TrackStage {
+    hv::Stage stage;
     size_t B = 0;
     int *idx = nullptr, *st = nullptr, *gs = nullptr;
     double *feat = nullptr, *vel = nullptr, *y = nullptr, *chi = nullptr, *pf = nullptr;
-    unsigned char *own = nullptr;
-    static size_t up(size_t v) { return (v + 15) & ~(size_t)15; }
+    explicit TrackStage(Ctx *c) : stage(c) {}
 
-    int upload(Ekf *e, size_t B_, int np, bool stereo, size_t own_bytes, const int *h_idx, const double *h_feat, const double *h_vel, const double *h_y)
+    int upload(size_t B_, int np, bool stereo, const int *h_idx, const double *h_feat, const double *h_vel, const double *h_y)
     {
-        Ctx *c = e->c;
+        Ctx *c = stage.c;
         B = B_;
         const size_t nt = (size_t)np * (stereo ? 2 : 1);
-        const size_t o_idx = 0, o_feat = up(o_idx + B * np * sizeof(int)), o_vel = up(o_feat + B * nt * 2 * sizeof(double));
-        const size_t o_y = up(o_vel + B * nt * 2 * sizeof(double)), o_st = up(o_y + B * nt * 2 * sizeof(double));
-        const size_t o_gs = up(o_st + B * 2 * sizeof(int)), o_chi = up(o_gs + B * sizeof(int)), o_pf = up(o_chi + B * sizeof(double));
-        const size_t o_own = up(o_pf + B * 3 * sizeof(double)), total = o_own + own_bytes;
-        if (e->vustage_bytes < total) {
-            e->vustage_bytes = 0;
-            if (const int rc = hv::grow_buffers(c, {c->stream}, {{e->vustage, total}})) return rc;
-            e->vustage_bytes = total;
-        }
-        unsigned char *d = e->vustage;
-        idx = reinterpret_cast<int *>(d + o_idx); st = reinterpret_cast<int *>(d + o_st); gs = reinterpret_cast<int *>(d + o_gs);
-        feat = reinterpret_cast<double *>(d + o_feat); vel = reinterpret_cast<double *>(d + o_vel); y = reinterpret_cast<double *>(d + o_y);
-        chi = reinterpret_cast<double *>(d + o_chi); pf = reinterpret_cast<double *>(d + o_pf); own = d + o_own;
+        const auto o_idx = stage.take<int>(B * np), o_st = stage.take<int>(B * 2), o_gs = stage.take<int>(B);
+        const auto o_feat = stage.take<double>(B * nt * 2), o_vel = stage.take<double>(B * nt * 2), o_y = stage.take<double>(B * nt * 2);
+        const auto o_chi = stage.take<double>(B), o_pf = stage.take<double>(B * 3);
+        if (const int rc = stage.reserve()) return rc;
+        idx = stage.at(o_idx); st = stage.at(o_st); gs = stage.at(o_gs);
+        feat = stage.at(o_feat); vel = stage.at(o_vel); y = stage.at(o_y); chi = stage.at(o_chi); pf = stage.at(o_pf);
         HV_HIP(c, hipMemcpyAsync(idx, h_idx, B * np * sizeof(int), hipMemcpyHostToDevice, c->stream));
         HV_HIP(c, hipMemcpyAsync(feat, h_feat, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HV_HIP(c, hipMemcpyAsync(vel, h_vel, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -878,9 +872,9 @@ struct TrackStage {
         return HV_OK;
     }
     // ... then the entry's own counters (n_cnt ints at d_cnt, optional) and the synchronise
-    int download(Ekf *e, int *status, int *gate_status, double *chi2, double *h_pf, int *counts = nullptr, const int *d_cnt = nullptr, size_t n_cnt = 0) const
+    int download(int *status, int *gate_status, double *chi2, double *h_pf, int *counts = nullptr, const int *d_cnt = nullptr, size_t n_cnt = 0) const
     {
-        Ctx *c = e->c;
+        Ctx *c = stage.c;
         HV_HIP(c, hipMemcpyAsync(status, st, B * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HV_HIP(c, hipMemcpyAsync(gate_status, gs, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, chi, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -896,10 +890,10 @@ int hv_ekf_visual_track(hv_ekf *h, const hv_vu_params *p, int np, const int *idx
 {
     if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2) return HV_ERR_INVALID;
     Ekf *e = &h->e;
-    TrackStage s;
-    int rc = s.upload(e, (size_t)e->batch, np, p->useStereo != 0, 0, idx, feat, vel, y);
+    TrackStage s(e->c);
+    int rc = s.upload((size_t)e->batch, np, p->useStereo != 0, idx, feat, vel, y);
     if (rc == HV_OK) rc = hv_ekf_visual_track_dev(h, p, np, s.idx, s.feat, s.vel, s.y, r_gate, r_update, s.st, s.gs, s.chi, s.pf);
-    return rc != HV_OK ? rc : s.download(e, status, gate_status, chi2, pf);
+    return rc != HV_OK ? rc : s.download(status, gate_status, chi2, pf);
 }
 
 // batch_rows: 0 = the sequential visit loop (visual_frame_dev_impl); != 0 = the batchVisualUpdate loop with this max_update_rows (< 0: the
@@ -911,17 +905,18 @@ static int visual_frame_host_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks
 {
     if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2 || n_tracks < 1) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    const size_t B = (size_t)e->batch * n_tracks, cnt_bytes = TrackStage::up((size_t)e->batch * sizeof(int));
-    TrackStage s;                                                  // own sections: success counts [batch] | pose counts [B]
-    int rc = s.upload(e, B, np, p->useStereo != 0, cnt_bytes + TrackStage::up(B * sizeof(int)), idx, feat, vel, y);
+    const size_t B = (size_t)e->batch * n_tracks;
+    TrackStage s(c);                                               // own sections: success counts [batch] | pose counts [B]
+    const auto o_cnt = s.stage.take<int>(e->batch), o_np = s.stage.take<int>(B);
+    int rc = s.upload(B, np, p->useStereo != 0, idx, feat, vel, y);
     if (rc != HV_OK) return rc;
-    int *d_cnt = reinterpret_cast<int *>(s.own), *d_np = n_poses ? reinterpret_cast<int *>(s.own + cnt_bytes) : nullptr;
+    int *d_cnt = s.stage.at(o_cnt), *d_np = n_poses ? s.stage.at(o_np) : nullptr;
     if (n_poses) HV_HIP(c, hipMemcpyAsync(d_np, n_poses, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
     rc = batch_rows == 0
         ? visual_frame_dev_impl(h, p, n_tracks, np, d_np, s.idx, s.feat, s.vel, s.y, r_gate, r_update, s.st, s.gs, s.chi, s.pf, d_cnt, max_successful)
         : hv_ekf_visual_frame_batch_dev(h, p, n_tracks, np, d_np, s.idx, s.feat, s.vel, s.y, r_gate, r_update, s.st, s.gs, s.chi, s.pf, d_cnt, max_successful,
                                         batch_rows < 0 ? 0 : batch_rows);
-    if (rc == HV_OK) rc = s.download(e, status, gate_status, chi2, pf, success_count, d_cnt, (size_t)e->batch);
+    if (rc == HV_OK) rc = s.download(status, gate_status, chi2, pf, success_count, d_cnt, (size_t)e->batch);
     if (rc != HV_OK) return rc;
     int flags = 0;
     const int rc2 = hv_ekf_frame_error(h, &flags);                // the hand-shake form of the speculative pass never fails silently
@@ -961,15 +956,16 @@ int hv_ekf_visual_track_hybrid(hv_ekf *h, const hv_vu_params *p, int np, const i
 {
     if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    const size_t B = (size_t)e->batch, map_bytes = TrackStage::up(B * sizeof(int));
-    TrackStage s;                                                  // own sections: map_update [B] | map_offer [B]
-    int rc = s.upload(e, B, np, p->useStereo != 0, 2 * map_bytes, idx, feat, vel, y);
+    const size_t B = (size_t)e->batch;
+    TrackStage s(c);                                               // own sections: map_update [B] | map_offer [B]
+    const auto o_mu = s.stage.take<int>(B), o_mo = s.stage.take<int>(B);
+    int rc = s.upload(B, np, p->useStereo != 0, idx, feat, vel, y);
     if (rc != HV_OK) return rc;
-    int *d_mu = map_update ? reinterpret_cast<int *>(s.own) : nullptr, *d_mo = map_offer ? reinterpret_cast<int *>(s.own + map_bytes) : nullptr;
+    int *d_mu = map_update ? s.stage.at(o_mu) : nullptr, *d_mo = map_offer ? s.stage.at(o_mo) : nullptr;
     if (map_update) HV_HIP(c, hipMemcpyAsync(d_mu, map_update, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (map_offer) HV_HIP(c, hipMemcpyAsync(d_mo, map_offer, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
     rc = hv_ekf_visual_track_hybrid_dev(h, p, np, s.idx, s.feat, s.vel, s.y, d_mu, d_mo, r_gate, r_update, s.st, s.gs, s.chi, s.pf);
-    return rc != HV_OK ? rc : s.download(e, status, gate_status, chi2, pf);
+    return rc != HV_OK ? rc : s.download(status, gate_status, chi2, pf);
 }
 
 }  // extern "C"

@@ -521,15 +521,14 @@ int hv_gftt_detect(hv_ctx *ctx, const hv_gftt_params *p, int slot, const float *
     if (capacity < 2 * nk) return HV_ERR_INVALID;
     *n_out = 0;
     if (nk == 0) return HV_OK;
-    if (c->gftt_cap < nk) {
-        if (c->d_gftt_kp) { (void)hipFree(c->d_gftt_kp); c->d_gftt_kp = nullptr; c->gftt_cap = 0; }
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_gftt_kp), sizeof(float) * 3 * nk));
-        c->gftt_cap = nk;
-    }
-    int rc = hv::launch(c, 1, nullptr, slot, hv_gftt_block_size(p), p->gfttMinResponse, p->gfttBlockSize, c->d_gftt_kp);
+    hv::Stage s(c);
+    const auto o_kp = s.take<float>(3 * (size_t)nk);
+    int rc = s.reserve();
+    if (rc != HV_OK) return rc;
+    rc = hv::launch(c, 1, nullptr, slot, hv_gftt_block_size(p), p->gfttMinResponse, p->gfttBlockSize, s.at(o_kp));
     if (rc != HV_OK) return rc;
     std::vector<float> kp(3 * (size_t)nk);
-    HV_HIP(c, hipMemcpyAsync(kp.data(), c->d_gftt_kp, sizeof(float) * 3 * nk, hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(kp.data(), s.at(o_kp), sizeof(float) * 3 * nk, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     // detect(): stable sort by descending response, then corners.resize(n) + push_back (n zero points first)
     std::vector<int> order(nk);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -99,29 +100,16 @@ struct Ctx {
     int *d_l0_stride = nullptr;           // [pool_size]
     std::vector<int> free_slots;
     std::vector<uint8_t> slot_used;
-    // small staging buffers for the synchronous host-pointer entry points
-    int *d_slots = nullptr;               // [2 * max_pairs]
-    float *d_prev_xy = nullptr, *d_next_xy = nullptr, *d_err = nullptr;
-    uint8_t *d_status = nullptr;
-    int stage_points = 0;
-    float *d_gftt_kp = nullptr;           // key points of the single-image detector entry point
-    int gftt_cap = 0;
-    // ingest (f2): per-camera remap tables and the staging buffer of the host entry point
+    int *d_slots = nullptr;               // [4] slot numbers written by set_ints_kernel: [0] the slot of a one-slot pyramid build, [2] / [3] the pair of hv_klt_track
+    // device staging of every synchronous host-pointer entry point: one block, carved per call through Stage (below)
+    unsigned char *d_stage = nullptr;
+    size_t stage_bytes = 0;
+    // ingest (f2): per-camera remap tables
     uint32_t *d_map_xy[HV_INGEST_CAMERAS] = {};
     float *d_map_xf[HV_INGEST_CAMERAS] = {}, *d_map_yf[HV_INGEST_CAMERAS] = {};
     int map_stride = 0;
     int *d_tile_box[HV_INGEST_CAMERAS] = {};   // per 64 x 16 output tile: source rectangle (remap_tile_kernel)
     bool map_tiled[HV_INGEST_CAMERAS] = {};
-    uint8_t *d_ingest_stage = nullptr;
-    size_t ingest_stage_bytes = 0;
-    unsigned char *d_ransac_stage = nullptr;   // staging of the host-pointer rotation-RANSAC entry (f4)
-    size_t ransac_stage_bytes = 0;
-    unsigned char *d_r5_stage = nullptr;       // points, statuses, E and summary of the host-pointer five-point entry (ransac5.hip)
-    size_t r5_stage_bytes = 0;
-    unsigned char *d_gate_stage = nullptr;     // inputs and outputs of the host-pointer stereo-gate entries (stereo_gate.hip)
-    size_t gate_stage_bytes = 0;
-    unsigned char *d_subpix_stage = nullptr;   // points + update counts of the host-pointer sub-pixel entry (subpix.hip)
-    size_t subpix_stage_bytes = 0;
     unsigned char *d_ransac_split = nullptr;   // records of the split rotation-RANSAC launches (rot_ransac.hip), ransac_split_sets of them
     int ransac_split_sets = 0;
     std::string last_error;
@@ -136,6 +124,49 @@ Ctx *ctx_of(hv_ctx *h);
         hipError_t e__ = (call);                                         \
         if (e__ != hipSuccess) return hv::hip_fail((c), e__, #call);     \
     } while (0)
+
+// Growing device buffers: drains `drain` (in order, before anything is freed), frees and nulls every slot, allocates them again at
+// their new sizes. The caller tests whether growth is needed, zeroes the group's capacity field before the call and sets it after
+// an HV_OK, so that a failure in the middle leaves a group that reads as empty.
+struct GrowSlot {
+    void **slot; size_t bytes;
+    template <class T> GrowSlot(T *&p, size_t b) : slot(reinterpret_cast<void **>(&p)), bytes(b) {}
+};
+inline int grow_buffers(Ctx *c, std::initializer_list<hipStream_t> drain, std::initializer_list<GrowSlot> slots)
+{
+    for (hipStream_t s : drain) HV_HIP(c, hipStreamSynchronize(s));
+    for (const GrowSlot &g : slots) if (*g.slot) { (void)hipFree(*g.slot); *g.slot = nullptr; }
+    for (const GrowSlot &g : slots) HV_HIP(c, hipMalloc(g.slot, g.bytes));
+    return HV_OK;
+}
+
+// Staging of one host-pointer call in the context's arena (Ctx::d_stage): take() every section, reserve() once, then at() for the
+// device pointers. Sections are 16-byte aligned and never overlap; the arena at least doubles when it grows.
+// Invariant: every user copies into, launches on and reads back from the arena on c->stream only, so successive calls are ordered by
+// that stream (hv_ingest_build, which returns before its kernel has read the arena, included); growth drains c->stream before it
+// frees, and hv_set_stream drains the old stream before it swaps. A forked visit (ekf_visit.hip) reads uploaded sections on
+// aux_stream, but joins c->stream again inside the visit, in front of the entry's download and synchronise.
+template <class T> struct StageSection { size_t off; };
+struct Stage {
+    Ctx *c; size_t total = 0;
+    explicit Stage(Ctx *ctx) : c(ctx) {}
+    template <class T> StageSection<T> take(size_t count)
+    {
+        const StageSection<T> s{total};
+        total += (count * sizeof(T) + 15) & ~(size_t)15;
+        return s;
+    }
+    int reserve()
+    {
+        if (total <= c->stage_bytes) return HV_OK;
+        const size_t cap = total > 2 * c->stage_bytes ? total : 2 * c->stage_bytes;
+        c->stage_bytes = 0;
+        if (const int rc = grow_buffers(c, {c->stream}, {{c->d_stage, cap}})) return rc;
+        c->stage_bytes = cap;
+        return HV_OK;
+    }
+    template <class T> T *at(StageSection<T> s) const { return reinterpret_cast<T *>(c->d_stage + s.off); }
+};
 
 // RAII-ish per-launch timing helper (no-op unless profiling is on).
 struct ScopedKernelTime {

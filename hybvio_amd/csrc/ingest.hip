@@ -449,17 +449,12 @@ int hv_ingest_build(hv_ctx *h, int slot, const uint8_t *image_host, int stride_b
     if (slot < 0 || slot >= c->p.pool_size || !c->slot_used[slot]) return HV_ERR_POOL;
     const int w = c->L.w[0], hgt = c->L.h[0];
     const int st = (w * channels + 15) / 16 * 16;
-    const size_t need = (size_t)st * hgt;
-    if (c->ingest_stage_bytes < need) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_ingest_stage) (void)hipFree(c->d_ingest_stage);
-        c->d_ingest_stage = nullptr; c->ingest_stage_bytes = 0;
-        HV_HIP(c, hipMalloc((void **)&c->d_ingest_stage, need));
-        c->ingest_stage_bytes = need;
-    }
-    HV_HIP(c, hipMemcpy2DAsync(c->d_ingest_stage, st, image_host, stride_bytes, (size_t)w * channels, hgt,
-                               hipMemcpyHostToDevice, c->stream));
-    rc = hv::launch_ingest(c, 1, nullptr, slot, c->d_ingest_stage, 0, st, channels, camera);
+    hv::Stage s(c);
+    const auto o_img = s.take<uint8_t>((size_t)st * hgt);
+    rc = s.reserve();
+    if (rc != HV_OK) return rc;
+    HV_HIP(c, hipMemcpy2DAsync(s.at(o_img), st, image_host, stride_bytes, (size_t)w * channels, hgt, hipMemcpyHostToDevice, c->stream));
+    rc = hv::launch_ingest(c, 1, nullptr, slot, s.at(o_img), 0, st, channels, camera);
     if (rc != HV_OK) return rc;
     return hv::build_levels_of_slot(c, slot);
 }

@@ -731,30 +731,27 @@ int hv_ransac5(hv_ctx *h, const hv_ransac5_params *p, int n, const float *c1, co
     Ctx *c = hv::ctx_of(h);
     if (!c || (n > 0 && (!c1 || !c2 || !status)) || !cam1 || !cam2) return HV_ERR_INVALID;
     const int mp = std::max(n, 1);
-    const size_t o_c1 = 0, o_c2 = o_c1 + sizeof(float) * 2 * mp, o_n = o_c2 + sizeof(float) * 2 * mp, o_st = o_n + 16;
-    const size_t o_E = (o_st + sizeof(int) * mp + 15) / 16 * 16, o_sum = o_E + sizeof(double) * 9, total = o_sum + 16;
-    if (c->r5_stage_bytes < total) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_r5_stage) (void)hipFree(c->d_r5_stage);
-        c->d_r5_stage = nullptr; c->r5_stage_bytes = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_r5_stage), total));
-        c->r5_stage_bytes = total;
-    }
-    unsigned char *d = c->d_r5_stage;
+    hv::Stage s(c);
+    const auto o_c1 = s.take<float>(2 * (size_t)mp), o_c2 = s.take<float>(2 * (size_t)mp);
+    const auto o_n = s.take<int>(1), o_st = s.take<int>(mp), o_sum = s.take<int>(4);
+    const auto o_E = s.take<double>(9);
+    int rc = s.reserve();
+    if (rc != HV_OK) return rc;
+    float *d_c1 = s.at(o_c1), *d_c2 = s.at(o_c2);
+    int *d_n = s.at(o_n), *d_st = s.at(o_st), *d_sum = s.at(o_sum);
+    double *d_E = s.at(o_E);
     if (n > 0) {
-        HV_HIP(c, hipMemcpyAsync(d + o_c1, c1, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d + o_c2, c2, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        HV_HIP(c, hipMemcpyAsync(d_c1, c1, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        HV_HIP(c, hipMemcpyAsync(d_c2, c2, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
     }
-    HV_HIP(c, hipMemcpyAsync(d + o_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    const int rc = hv_ransac5_batch_dev(h, p, 1, mp, reinterpret_cast<const int *>(d + o_n), reinterpret_cast<const float *>(d + o_c1),
-                                        reinterpret_cast<const float *>(d + o_c2), cam1, cam2, reinterpret_cast<int *>(d + o_st),
-                                        reinterpret_cast<double *>(d + o_E), reinterpret_cast<int *>(d + o_sum));
+    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    rc = hv_ransac5_batch_dev(h, p, 1, mp, d_n, d_c1, d_c2, cam1, cam2, d_st, d_E, d_sum);
     if (rc != HV_OK) return rc;
     int sm[4];
-    if (n > 0) HV_HIP(c, hipMemcpyAsync(status, d + o_st, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    if (n > 0) HV_HIP(c, hipMemcpyAsync(status, d_st, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
     double e[9];
-    HV_HIP(c, hipMemcpyAsync(e, d + o_E, sizeof(e), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(sm, d + o_sum, sizeof(sm), hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(e, d_E, sizeof(e), hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(sm, d_sum, sizeof(sm), hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     if (E) for (int i = 0; i < 9; ++i) E[i] = e[i];
     if (summary) for (int i = 0; i < 4; ++i) summary[i] = sm[i];

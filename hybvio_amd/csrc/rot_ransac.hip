@@ -469,30 +469,23 @@ int hv_rot_ransac(hv_ctx *h, int n, const float *c1, const float *c2, const hv_c
 {
     Ctx *c = hv::ctx_of(h);
     if (!c || n < 2 || n > hv::MAX_PTS || !c1 || !c2 || !pairs || !status || !cam1 || !cam2) return HV_ERR_INVALID;
-    const size_t o_c1 = 0, o_c2 = o_c1 + sizeof(float) * 2 * n, o_pairs = o_c2 + sizeof(float) * 2 * n;
-    const size_t o_n = o_pairs + sizeof(int) * 2 * hv::HYP, o_st = o_n + 16, o_R = o_st + sizeof(int) * n, o_sum = o_R + 48;
-    const size_t total = o_sum + 16;
-    if (c->ransac_stage_bytes < total) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_ransac_stage) (void)hipFree(c->d_ransac_stage);
-        c->d_ransac_stage = nullptr; c->ransac_stage_bytes = 0;
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_ransac_stage), total));
-        c->ransac_stage_bytes = total;
-    }
-    unsigned char *d = c->d_ransac_stage;
-    HV_HIP(c, hipMemcpyAsync(d + o_c1, c1, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_c2, c2, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_pairs, pairs, sizeof(int) * 2 * hv::HYP, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    int rc = hv_rot_ransac_batch_dev(h, 1, n, reinterpret_cast<const int *>(d + o_n), reinterpret_cast<const float *>(d + o_c1),
-                                     reinterpret_cast<const float *>(d + o_c2), cam1, cam2, reinterpret_cast<const int *>(d + o_pairs),
-                                     threshold_pow2, reinterpret_cast<int *>(d + o_st), reinterpret_cast<float *>(d + o_R),
-                                     reinterpret_cast<int *>(d + o_sum));
+    hv::Stage s(c);
+    const auto o_c1 = s.take<float>(2 * (size_t)n), o_c2 = s.take<float>(2 * (size_t)n), o_R = s.take<float>(9);
+    const auto o_pairs = s.take<int>(2 * hv::HYP), o_n = s.take<int>(1), o_st = s.take<int>(n), o_sum = s.take<int>(2);
+    int rc = s.reserve();
+    if (rc != HV_OK) return rc;
+    float *d_c1 = s.at(o_c1), *d_c2 = s.at(o_c2), *d_R = s.at(o_R);
+    int *d_pairs = s.at(o_pairs), *d_n = s.at(o_n), *d_st = s.at(o_st), *d_sum = s.at(o_sum);
+    HV_HIP(c, hipMemcpyAsync(d_c1, c1, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(d_c2, c2, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(d_pairs, pairs, sizeof(int) * 2 * hv::HYP, hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    rc = hv_rot_ransac_batch_dev(h, 1, n, d_n, d_c1, d_c2, cam1, cam2, d_pairs, threshold_pow2, d_st, d_R, d_sum);
     if (rc != HV_OK) return rc;
     int summary[2] = {0, 0};
-    HV_HIP(c, hipMemcpyAsync(status, d + o_st, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    if (R) HV_HIP(c, hipMemcpyAsync(R, d + o_R, sizeof(float) * 9, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(summary, d + o_sum, sizeof(summary), hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(status, d_st, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    if (R) HV_HIP(c, hipMemcpyAsync(R, d_R, sizeof(float) * 9, hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(summary, d_sum, sizeof(summary), hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     if (best_inlier_count) *best_inlier_count = summary[0];
     if (hypotheses_visited) *hypotheses_visited = summary[1];

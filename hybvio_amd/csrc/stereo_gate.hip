@@ -208,19 +208,6 @@ void fill_common(GateArgs &a, const Ctx *c, const hv_stereo_gate_params *p, int 
     a.max_points = max_points;
 }
 
-size_t align16(size_t x) { return (x + 15) / 16 * 16; }
-
-int ensure_stage(Ctx *c, size_t total)
-{
-    if (c->gate_stage_bytes >= total) return HV_OK;
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_gate_stage) (void)hipFree(c->d_gate_stage);
-    c->d_gate_stage = nullptr; c->gate_stage_bytes = 0;
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_gate_stage), total));
-    c->gate_stage_bytes = total;
-    return HV_OK;
-}
-
 }  // namespace
 }  // namespace hv
 
@@ -319,25 +306,28 @@ int hv_track_gate(hv_ctx *h, const hv_stereo_gate_params *p, int n, const float 
     if (n == 0) return HV_OK;
     const bool stereo = second_corners != nullptr;
     const size_t xy = sizeof(float) * 2 * (size_t)n, st = sizeof(int32_t) * (size_t)n;
-    const size_t o_n = 0, o_c = 16, o_s = hv::align16(o_c + xy), o_ss = hv::align16(o_s + xy), o_bl = hv::align16(o_ss + st);
-    const size_t o_ts = hv::align16(o_bl + (size_t)n), total = o_ts + st;
-    if (const int rc = hv::ensure_stage(c, total)) return rc;
-    unsigned char *d = c->d_gate_stage;
-    HV_HIP(c, hipMemcpyAsync(d + o_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_c, corners, xy, hipMemcpyHostToDevice, c->stream));
-    if (stereo) {
-        HV_HIP(c, hipMemcpyAsync(d + o_s, second_corners, xy, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d + o_ss, stereo_status, st, hipMemcpyHostToDevice, c->stream));
-    }
-    if (blacklist) HV_HIP(c, hipMemcpyAsync(d + o_bl, blacklist, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_ts, track_status, st, hipMemcpyHostToDevice, c->stream));
-    const int rc = hv_track_gate_batch_dev(h, p, 1, n, reinterpret_cast<const int *>(d + o_n), reinterpret_cast<const float *>(d + o_c),
-                                           stereo ? reinterpret_cast<const float *>(d + o_s) : nullptr,
-                                           stereo ? reinterpret_cast<const int32_t *>(d + o_ss) : nullptr,
-                                           blacklist ? reinterpret_cast<const uint8_t *>(d + o_bl) : nullptr, camera0, camera1,
-                                           reinterpret_cast<int32_t *>(d + o_ts), nullptr);
+    hv::Stage s(c);
+    const auto o_n = s.take<int>(1);
+    const auto o_c = s.take<float>(2 * (size_t)n), o_s = s.take<float>(2 * (size_t)n);
+    const auto o_ss = s.take<int32_t>(n), o_ts = s.take<int32_t>(n);
+    const auto o_bl = s.take<uint8_t>(n);
+    int rc = s.reserve();
     if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(track_status, d + o_ts, st, hipMemcpyDeviceToHost, c->stream));
+    int *d_n = s.at(o_n);
+    float *d_c = s.at(o_c), *d_s = stereo ? s.at(o_s) : nullptr;
+    int32_t *d_ss = stereo ? s.at(o_ss) : nullptr, *d_ts = s.at(o_ts);
+    uint8_t *d_bl = blacklist ? s.at(o_bl) : nullptr;
+    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(d_c, corners, xy, hipMemcpyHostToDevice, c->stream));
+    if (stereo) {
+        HV_HIP(c, hipMemcpyAsync(d_s, second_corners, xy, hipMemcpyHostToDevice, c->stream));
+        HV_HIP(c, hipMemcpyAsync(d_ss, stereo_status, st, hipMemcpyHostToDevice, c->stream));
+    }
+    if (blacklist) HV_HIP(c, hipMemcpyAsync(d_bl, blacklist, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(d_ts, track_status, st, hipMemcpyHostToDevice, c->stream));
+    rc = hv_track_gate_batch_dev(h, p, 1, n, d_n, d_c, d_s, d_ss, d_bl, camera0, camera1, d_ts, nullptr);
+    if (rc != HV_OK) return rc;
+    HV_HIP(c, hipMemcpyAsync(track_status, d_ts, st, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -354,33 +344,33 @@ int hv_detection_filter(hv_ctx *h, const hv_stereo_gate_params *p, int n, const 
     if (n == 0) { *n_out = 0; return HV_OK; }
     const bool stereo = second_corners != nullptr;
     const size_t xy = sizeof(float) * 2 * (size_t)n, st = sizeof(int32_t) * (size_t)n;
-    const size_t o_n = 0, o_no = 4, o_c = 16, o_s = hv::align16(o_c + xy), o_ss = hv::align16(o_s + xy), o_st = hv::align16(o_ss + st);
-    const size_t o_oc = hv::align16(o_st + st), o_os = hv::align16(o_oc + xy), total = o_os + xy;
-    if (const int rc = hv::ensure_stage(c, total)) return rc;
-    unsigned char *d = c->d_gate_stage;
-    HV_HIP(c, hipMemcpyAsync(d + o_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d + o_c, corners, xy, hipMemcpyHostToDevice, c->stream));
+    hv::Stage s(c);
+    const auto o_n = s.take<int>(1), o_no = s.take<int>(1);
+    const auto o_c = s.take<float>(2 * (size_t)n), o_s = s.take<float>(2 * (size_t)n);
+    const auto o_oc = s.take<float>(2 * (size_t)n), o_os = s.take<float>(2 * (size_t)n);
+    const auto o_ss = s.take<int32_t>(n), o_st = s.take<int32_t>(n);
+    int rc = s.reserve();
+    if (rc != HV_OK) return rc;
+    int *d_n = s.at(o_n), *d_no = s.at(o_no);
+    float *d_c = s.at(o_c), *d_s = stereo ? s.at(o_s) : nullptr, *d_oc = s.at(o_oc), *d_os = stereo ? s.at(o_os) : nullptr;
+    int32_t *d_ss = stereo ? s.at(o_ss) : nullptr, *d_st = s.at(o_st);
+    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(d_c, corners, xy, hipMemcpyHostToDevice, c->stream));
     if (stereo) {
-        HV_HIP(c, hipMemcpyAsync(d + o_s, second_corners, xy, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d + o_ss, stereo_status, st, hipMemcpyHostToDevice, c->stream));
+        HV_HIP(c, hipMemcpyAsync(d_s, second_corners, xy, hipMemcpyHostToDevice, c->stream));
+        HV_HIP(c, hipMemcpyAsync(d_ss, stereo_status, st, hipMemcpyHostToDevice, c->stream));
     }
-    const int rc = hv_detection_filter_batch_dev(h, p, 1, n, reinterpret_cast<const int *>(d + o_n),
-                                                 reinterpret_cast<const float *>(d + o_c),
-                                                 stereo ? reinterpret_cast<const float *>(d + o_s) : nullptr,
-                                                 stereo ? reinterpret_cast<const int32_t *>(d + o_ss) : nullptr, camera0, camera1,
-                                                 reinterpret_cast<int32_t *>(d + o_st), reinterpret_cast<float *>(d + o_oc),
-                                                 stereo ? reinterpret_cast<float *>(d + o_os) : nullptr,
-                                                 reinterpret_cast<int *>(d + o_no));
+    rc = hv_detection_filter_batch_dev(h, p, 1, n, d_n, d_c, d_s, d_ss, camera0, camera1, d_st, d_oc, d_os, d_no);
     if (rc != HV_OK) return rc;
     int cnt = 0;
-    HV_HIP(c, hipMemcpyAsync(&cnt, d + o_no, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(&cnt, d_no, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     if (cnt < 0 || cnt > n) return HV_ERR_HIP;
     if (cnt > 0) {
-        HV_HIP(c, hipMemcpyAsync(out_corners, d + o_oc, sizeof(float) * 2 * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
-        if (stereo) HV_HIP(c, hipMemcpyAsync(out_second, d + o_os, sizeof(float) * 2 * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        HV_HIP(c, hipMemcpyAsync(out_corners, d_oc, sizeof(float) * 2 * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        if (stereo) HV_HIP(c, hipMemcpyAsync(out_second, d_os, sizeof(float) * 2 * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
     }
-    if (status) HV_HIP(c, hipMemcpyAsync(status, d + o_st, st, hipMemcpyDeviceToHost, c->stream));
+    if (status) HV_HIP(c, hipMemcpyAsync(status, d_st, st, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     *n_out = cnt;
     return HV_OK;

@@ -237,20 +237,19 @@ int hv_corner_subpix(hv_ctx *ctx, const hv_subpix_params *p, int slot, int n, fl
     if (!ctx || !p || n < 0 || (n > 0 && !xy)) return HV_ERR_INVALID;
     Ctx *c = hv::ctx_of(ctx);
     if (slot < 0 || slot >= c->p.pool_size || !c->slot_used[slot]) return HV_ERR_POOL;
-    const int rc = hv::check_params(c, p);
+    int rc = hv::check_params(c, p);
     if (rc != HV_OK) return rc;
     if (n == 0) return HV_OK;
-    const size_t need = sizeof(float) * 2 * (size_t)n + sizeof(int) * (size_t)n;
-    if (c->subpix_stage_bytes < need) {
-        if (c->d_subpix_stage) { (void)hipFree(c->d_subpix_stage); c->d_subpix_stage = nullptr; c->subpix_stage_bytes = 0; }
-        HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_subpix_stage), need));
-        c->subpix_stage_bytes = need;
-    }
-    float *d_xy = reinterpret_cast<float *>(c->d_subpix_stage);
-    int *d_it = reinterpret_cast<int *>(c->d_subpix_stage + sizeof(float) * 2 * (size_t)n);
+    hv::Stage s(c);
+    const auto o_xy = s.take<float>(2 * (size_t)n);
+    const auto o_it = s.take<int>(n);
+    rc = s.reserve();
+    if (rc != HV_OK) return rc;
+    float *d_xy = s.at(o_xy);
+    int *d_it = s.at(o_it);
     HV_HIP(c, hipMemcpyAsync(d_xy, xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    const int lrc = hv::launch(c, p, 1, nullptr, slot, n, nullptr, n, d_xy, d_it);
-    if (lrc != HV_OK) return lrc;
+    rc = hv::launch(c, p, 1, nullptr, slot, n, nullptr, n, d_xy, d_it);
+    if (rc != HV_OK) return rc;
     HV_HIP(c, hipMemcpyAsync(xy, d_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (iters) HV_HIP(c, hipMemcpyAsync(iters, d_it, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));

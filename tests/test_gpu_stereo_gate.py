@@ -477,3 +477,88 @@ def test_profile_class_counts_the_launches(oracle):
         ms, n = ctx.profile_read(capi.K_STEREO_GATE)
         assert n == 4 and ms > 0
         assert ctx.profile_read(capi.K_RANSAC5)[1] == 0 and ctx.profile_read(capi.K_KLT)[1] == 0
+
+
+# ---- every synchronous host-pointer entry stages through one block per context ----
+ARENA_W, ARENA_H, ARENA_B, ARENA_TRAIL = 64, 48, 8, 20
+# (entry, point count) in call order. The counts rise from round to round; the order is chosen so that the context's staging block,
+# reserved for ONE point, grows ten times, once under every entry, and every entry also runs directly behind another entry's growth:
+# round 0 grows under subpix, gate, gftt, flow, ekf, ingest; round 1 under klt, r5; round 2 under rot, filt (16-byte sections, a block
+# that at least doubles). ekf: poses of a stereo track on ARENA_B filters; ingest: channels of the image; gftt: always 48 key points
+ARENA_ROUNDS = [
+    [("subpix", 6), ("gate", 5), ("gftt", 0), ("flow", 60), ("klt", 30), ("rot", 12), ("filt", 12), ("ekf", 2), ("ingest", 1), ("r5", 12)],
+    [("klt", 250), ("subpix", 100), ("r5", 510), ("rot", 300), ("filt", 100), ("gate", 100), ("flow", 120), ("ekf", 8), ("ingest", 3), ("gftt", 0)],
+    [("rot", 1000), ("filt", 1024), ("ekf", 20), ("subpix", 1000), ("r5", 1000), ("gate", 1000), ("flow", 1000), ("klt", 1000), ("ingest", 4), ("gftt", 0)],
+]
+
+
+def _arena_setup(ctx, left, right):
+    """three built slots (left frame 0, left frame 1, right frame 0), one acquired slot for ingest, one filter batch"""
+    slots = [ctx.acquire() for _ in range(4)]
+    for s, img in zip(slots, (left[0], left[1], right[0])):
+        ctx.build(s, img)
+    return slots, capi.EkfBatch(ctx, capi.ekf_default_params(cameraTrailLength=ARENA_TRAIL), ARENA_B)
+
+
+def _arena_call(ctx, g, slots, left, right, name, n):
+    """one host-pointer call on inputs that depend on (name, n) alone -> its outputs as a list of arrays"""
+    rng = np.random.default_rng([sorted(("klt", "flow", "gftt", "subpix", "rot", "r5", "gate", "filt", "ekf", "ingest")).index(name), n])
+    cam0 = capi.camera_model("pinhole", 60.0, 61.0, 32.0, 24.0, coeffs=(-0.25, 0.07, 0.0))
+    cam1 = capi.camera_model("pinhole", 60.0, 61.0, 32.0, 24.0, coeffs=(-0.24, 0.06, 0.0))
+    pts = rng.uniform([2, 2], [ARENA_W - 3, ARENA_H - 3], (max(n, 1), 2)).astype(np.float32)
+    moved = (pts + [-2.0, 0.3] + rng.normal(0, 0.7, pts.shape)).astype(np.float32)
+    if name == "klt":
+        return list(ctx.klt_track(slots[0], slots[1], pts))
+    if name == "flow":
+        return list(ctx.optical_flow_compute(slots[0], slots[2], pts, corners=moved))
+    if name == "gftt":
+        return [ctx.gftt_detect(slots[0], params=capi.gftt_default_params(gfttMinDistance=8.0))]
+    if name == "subpix":
+        return list(ctx.corner_subpix(slots[1], pts))
+    if name == "rot":
+        st, R, best, visited = ctx.rot_ransac(pts, moved, cam0, cam1, rng.integers(0, n, (100, 2)), 4e-4)
+        return [st, R, np.array([best, visited])]
+    if name == "r5":
+        return list(ctx.ransac5(pts, moved, cam0, cam1))
+    gp = capi.stereo_gate_default_params(partOfImageToDetectFeatures=0.9, cam0ToCam1=_transforms()["rotated_vertical"])
+    if name == "gate":
+        return [ctx.track_gate(pts, moved, rng.integers(0, 3, n), rng.choice([0, 2, 4], n), cam0, cam1, blacklist=rng.random(n) < 0.1, params=gp)]
+    if name == "filt":
+        kept, kept_second, st = ctx.detection_filter(pts, moved, rng.integers(0, 3, n), cam0, cam1, params=gp)
+        return [kept, kept_second, st]
+    if name == "ingest":
+        planes = [left[0], right[0], left[1], right[1]][:n]
+        ctx.ingest_build(slots[3], planes[0] if n == 1 else np.stack(planes, -1))
+        return list(ctx.download(slots[3], 0))
+    assert name == "ekf"
+    T1, T2, means, idx, feat = synth.visual_tracks(rng, ARENA_B, ARENA_TRAIL, n, True)
+    for b in range(ARENA_B):
+        g.set_state(b, means[b], np.eye(g.n) * 1e-4)
+    y = feat.reshape(ARENA_B, -1) + 1e-3 * rng.normal(size=(ARENA_B, feat.shape[1] * 2))
+    out = list(g.visual_track(capi.vu_default_params(imu_to_camera=T1, second_imu_to_camera=T2), idx, feat, np.zeros_like(feat), y, 1.5, 0.05))
+    return out + [a for b in range(ARENA_B) for a in g.get_state(b)]
+
+
+def test_host_pointer_entries_share_one_growing_staging_block():
+    """hv_ingest_build, hv_klt_track, hv_optical_flow_compute, hv_gftt_detect, hv_corner_subpix, hv_rot_ransac, hv_ransac5,
+    hv_track_gate, hv_detection_filter and hv_ekf_visual_track carve their device staging out of ONE block of the context that
+    grows under them. Interleaved on one context over three rounds of rising point counts (ARENA_ROUNDS), every call returns, bit
+    for bit, what the same call returns on a fresh context that has made no other staging call: a section that is mis-sized,
+    mis-aligned or reused too early would show here. No tolerance, nothing skipped."""
+    left, right, _ = synth.stereo_sequence(31, ARENA_W, ARENA_H, 2)
+    kw = dict(width=ARENA_W, height=ARENA_H, levels=1, pool_size=4, max_tracks=1)
+    assert all(sorted(e for e, _ in rnd) == sorted(e for e, _ in ARENA_ROUNDS[0]) and len(rnd) == 10 for rnd in ARENA_ROUNDS)
+    with capi.Context(**kw) as ctx:
+        slots, g = _arena_setup(ctx, left, right)
+        for r, rnd in enumerate(ARENA_ROUNDS):
+            for name, n in rnd:
+                got = _arena_call(ctx, g, slots, left, right, name, n)
+                with capi.Context(**kw) as ctx2:
+                    slots2, g2 = _arena_setup(ctx2, left, right)
+                    want = _arena_call(ctx2, g2, slots2, left, right, name, n)
+                    g2.close()
+                assert len(got) == len(want) > 0
+                for k, (a, b) in enumerate(zip(got, want)):
+                    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+                    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), (r, name, n, k)
+        g.close()
