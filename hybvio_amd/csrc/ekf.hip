@@ -1625,7 +1625,10 @@ __global__ __launch_bounds__(GATE_THREADS, 2) void ekf_gate_stream_kernel(GateAr
         double tot = 0; for (int w2 = 0; w2 < nwaves; w2++) tot += red[w2];
         tot *= a.noise_scale;
         if (a.chi2) a.chi2[b] = tot;
-        if (a.status) a.status[b] = tot > d_chi2inv95[nr] ? 3 /*CHI2*/ : 0 /*INLIER*/;
+        // (a non-positive pivot leaves NaN / inf in z: reported as CHI2, as by ekf_update_kernel phase D and the sparse gates -- the bare
+        //  comparison is false for a NaN and called such a filter an inlier)
+        const bool broken = !(tot < 1e300);
+        if (a.status) a.status[b] = (broken || tot > d_chi2inv95[nr]) ? 3 /*CHI2*/ : 0 /*INLIER*/;
     }
 }
 

@@ -331,7 +331,9 @@ struct Visit {
             if (phase == 1) return HV_OK;                      // (not a split shape: the fused launch is the gate phase)
             return hv::launch_vu_prepare(c, l_, stream);
         }
-        // (its own gate launch: the prepare launch takes neither P nor the threshold)
+        // (its own gate launch: the prepare launch takes neither P nor the threshold; the pair has no triangulation-only form, so it
+        //  is the gate phase of an interleaved one-stream visit -- launching it in both phases listed every long inlier twice)
+        if (phase == 1) return HV_OK;
         l_.fused = 2; l_.H = nullptr; l_.Hc = Hc; l_.acol = acol; l_.na_max = 7 * np + 1; l_.chi2 = chi2_dev;
         const int rc2 = hv::launch_vu_prepare(c, l_, stream);
         if (rc2 != HV_OK) return rc2;

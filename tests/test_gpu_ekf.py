@@ -120,6 +120,9 @@ def test_predict_n_samples_in_one_launch(oracle, ctx):
         np.testing.assert_allclose(g.get_dydx(0), os_[0].dydx, rtol=1e-12, atol=1e-14)
 
 
+PREDICT_CHAIN_FORMS = (2, 0)
+
+
 @pytest.mark.parametrize("B,nS,trail", [(1, 10, 20), (3, 7, 20), (3, 12, 5), (300, 10, 20), (2, 1, 20)])
 def test_predict_kernel_forms_agree_to_the_bit(oracle, ctx, B, nS, trail):
     """ekf_predict_chain_kernel (knob 2: every launch; default 1: launches of three or more samples -- the samples' mean recursion on one wavefront, F / L of up to five samples per pass) against
@@ -135,7 +138,7 @@ def test_predict_kernel_forms_agree_to_the_bit(oracle, ctx, B, nS, trail):
     d_dt, d_gy, d_ac = (torch.from_numpy(x).cuda() for x in (dt, gy, ac))
     states = [g.get_state(b) for b in range(B)]
     out = {}
-    for form in (2, 0):
+    for form in PREDICT_CHAIN_FORMS:
         for b in range(B):
             g.set_state(b, *states[b])
         ctx.set_knob("ekf_predict_chain", form)
@@ -175,9 +178,101 @@ def test_reference_der_predict_on_gpu(oracle, ctx):
 
 # (rows, columns of H): the all-in-LDS kernel with 1 / 2 / 3 row tiles incl. its 47-row limit and ragged
 # K halves (l = 41, 76, 100), the LDS + streamed-H kernel (48, 64) and the global-workspace kernel (84, 128)
-@pytest.mark.parametrize("nr,l", [(40, 160), (84, 160), (16, 76), (8, 41), (3, 160), (128, 160),
-                                  (47, 160), (48, 160), (33, 160), (64, 160), (17, 100), (32, 27)])
-def test_visual_gate_and_update_parity(oracle, ctx, nr, l):
+GATE_SHAPES = [(40, 160), (84, 160), (16, 76), (8, 41), (3, 160), (128, 160),
+               (47, 160), (48, 160), (33, 160), (64, 160), (17, 100), (32, 27)]
+# Forced gate kernels (both knobs are read at every launch). ekf_gate_kmode 1: every gate-only request that would run the all-in-LDS
+# kernel (ekf_update_kernel<2, ti>) runs the H-from-L2 kernel (<1, 0>) instead -- read in ekf_launch_update, so the host-pointer gate
+# takes it too. ekf_stream_gate 1: the gate-only DEVICE entry (hv_ekf_visual_dev, mode 0) runs ekf_gate_stream_kernel<ti> at any batch
+# size; the host-pointer gate never reads that knob.
+GATE_KNOBS = {"gate_kmode": {"ekf_gate_kmode": 1}, "stream_gate": {"ekf_stream_gate": 1}}
+
+
+def _set_knobs(ctx, knobs):
+    for k, v in (knobs or {}).items():
+        ctx.set_knob(k, v)
+        assert ctx.get_knob(k) == v
+
+
+def _stream_gate_serves(nr, l):
+    """ekf_launch_gate_stream's own admission rule (ekf.hip): at most 48 rows, and the zero-padded H area (16 ti x 16 lbk doubles) must
+    hold the 808 doubles of scratch that borrow it, within 96 KB of LDS. A declined shape falls through to the default gate kernel."""
+    ti, lbk = (nr + 15) // 16, (l + 15) // 16
+    rs = nr + 1
+    while rs % 32 not in (15, 17):
+        rs += 1
+    hs = 16 * ti * 16 * lbk
+    return nr <= 48 and hs >= 256 + 544 + 8 and 8 * (hs + rs * nr + 2) <= 96 * 1024
+
+
+def _gate_dev(g, H, v, r):
+    """hv_ekf_visual_dev mode 0 on device-resident inputs (H column-major per filter, as the kernels read it) -> chi2, status."""
+    import torch
+    B, nr, l = H.shape
+    g.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    dH = torch.from_numpy(np.ascontiguousarray(np.transpose(H, (0, 2, 1)))).cuda()
+    dv = torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    chi2 = torch.full((B,), np.nan, dtype=torch.float64, device="cuda")
+    st = torch.full((B,), -7, dtype=torch.int32, device="cuda")
+    g.visual_dev(nr, l, dH.data_ptr(), dv.data_ptr(), r, 0, chi2.data_ptr(), st.data_ptr())
+    torch.cuda.synchronize()
+    return chi2.cpu().numpy(), st.cpu().numpy()
+
+
+@pytest.mark.parametrize("knob", list(GATE_KNOBS))
+@pytest.mark.parametrize("nr,l", [s_ for s_ in GATE_SHAPES if s_[0] <= 48])
+def test_visual_gate_on_device_forced_kernels(oracle, ctx, nr, l, knob):
+    """Device-pointer twin of test_visual_gate_and_update_parity for the gate-only entry under each forced gate kernel: chi2 within
+    1e-9 relative of the oracle, the oracle's status, the filters untouched bit for bit.
+    Which kernel served: the library's profile times BOTH dense gate kernels (and the default one) as HV_K_EKF_UPDATE and only the
+    column-sparse gates as HV_K_EKF_GATE, so the counts prove exactly one dense gate launch and nothing else; the kernel behind it
+    follows from the launcher's rule, restated in _stream_gate_serves: of these shapes the streaming kernel declines 8 x 41 only (its
+    padded H area, 16 x 48 doubles, is smaller than the 808 doubles of scratch) and serves the rest with all three row-tile builds.
+    ekf_gate_kmode 1 turns every shape here (all-in-LDS by default: n = 160, nr <= 48) to the H-from-L2 kernel. As evidence, not as an
+    assertion, the test prints whether chi2 differs in the last place from the default kernel's."""
+    rng = np.random.default_rng(nr * 7 + l)
+    os_, g = make_pair(oracle, ctx, rng, batch=2)           # (the draws of the host-pointer test, in its order)
+    H = rng.normal(size=(2, nr, l))
+    f = rng.normal(size=(2, nr))
+    y = f + 0.05 * rng.normal(size=(2, nr))
+    y[1] = f[1] + 5.0 * rng.normal(size=nr)                 # filter 1: a gross outlier
+    r = 0.05
+    before = [[x.copy() for x in g.get_state(b)] for b in range(2)]
+    chi2_default, _ = _gate_dev(g, H, y - f, r)
+    _set_knobs(ctx, GATE_KNOBS[knob])
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    chi2, st = _gate_dev(g, H, y - f, r)
+    assert (ctx.profile_read(capi.K_EKF_UPDATE)[1], ctx.profile_read(capi.K_EKF_GATE)[1]) == (1, 0)
+    ctx.profile_enable(False)
+    served = _stream_gate_serves(nr, l) if knob == "stream_gate" else True
+    assert served == ((nr, l) != (8, 41) or knob != "stream_gate")
+    print(f"{knob} {nr}x{l}: {'forced kernel' if served else 'DECLINED, default kernel'} (row tiles {(nr + 15) // 16}); "
+          f"chi2 bits {'differ from' if not np.array_equal(chi2, chi2_default) else 'equal'} the default kernel's")
+    for b, o in enumerate(os_):
+        so, co = o.visual_track_outlier_check(H[b], f[b], y[b], r)
+        assert st[b] == so and abs(chi2[b] - co) <= 1e-9 * max(1.0, abs(co)), (b, chi2[b], co)
+    assert st[1] == 3
+    for b in range(2):
+        m, P = g.get_state(b)
+        assert np.array_equal(m, before[b][0]) and np.array_equal(P, before[b][1])
+
+
+def test_streaming_gate_shapes_cover_every_row_tile_build():
+    """(no launch) the shapes above that ekf_gate_stream_kernel serves reach its three instantiations, and name the one it declines."""
+    shapes = [s_ for s_ in GATE_SHAPES if s_[0] <= 48]
+    assert {(nr + 15) // 16 for nr, l in shapes if _stream_gate_serves(nr, l)} == {1, 2, 3}
+    assert [s_ for s_ in shapes if not _stream_gate_serves(*s_)] == [(8, 41)]
+
+
+@pytest.mark.parametrize("nr,l", GATE_SHAPES)
+def test_visual_gate_and_update_parity_gate_kmode(oracle, ctx, nr, l):
+    """... the host-pointer gate on the H-from-L2 kernel (the update half is not a gate-only launch: it keeps its kernel)."""
+    test_visual_gate_and_update_parity(oracle, ctx, nr, l, knobs=GATE_KNOBS["gate_kmode"])
+
+
+@pytest.mark.parametrize("nr,l", GATE_SHAPES)
+def test_visual_gate_and_update_parity(oracle, ctx, nr, l, knobs=None):
+    _set_knobs(ctx, knobs)
     rng = np.random.default_rng(nr * 7 + l)
     os_, g = make_pair(oracle, ctx, rng, batch=2)
     H = rng.normal(size=(2, nr, l))
@@ -494,7 +589,15 @@ def test_hybrid_map_state_n_above_160(oracle, ctx):
         assert check(os_, g) < 1e-9
 
 
-def test_singular_innovation_covariance_leaves_the_filter_untouched(oracle, ctx):
+@pytest.mark.parametrize("knob", list(GATE_KNOBS))
+def test_singular_innovation_covariance_under_forced_gate_kernels(oracle, ctx, knob):
+    """A non-positive pivot is where a second gate kernel is most likely to differ: the same case on the H-from-L2 kernel (host-pointer
+    gate) and on the streaming kernel (device entry: 12 x 76 is a shape it serves, _stream_gate_serves)."""
+    assert _stream_gate_serves(12, 76)
+    test_singular_innovation_covariance_leaves_the_filter_untouched(oracle, ctx, knobs=GATE_KNOBS[knob], gate_on_device=knob == "stream_gate")
+
+
+def test_singular_innovation_covariance_leaves_the_filter_untouched(oracle, ctx, knobs=None, gate_on_device=False):
     """r = 0 with a rank-deficient H makes S = H P H' singular: the blocked Cholesky meets a non-positive pivot. The filter must
     come back unchanged and flagged (status CHI2) from the gate AND from a plain update, never with NaNs in m / P (r01 advisor)."""
     rng = np.random.default_rng(8)
@@ -504,8 +607,11 @@ def test_singular_innovation_covariance_leaves_the_filter_untouched(oracle, ctx)
     H[0, 6:] = H[0, :6]                                     # filter 0: duplicated rows -> S exactly singular at r = 0
     v = 0.01 * rng.normal(size=(2, nr))
     before = [[x.copy() for x in g.get_state(b)] for b in range(2)]
-    chi2, st = g.visual_gate(H, v, 0.0)
+    _set_knobs(ctx, knobs)
+    chi2, st = _gate_dev(g, H, v, 0.0) if gate_on_device else g.visual_gate(H, v, 0.0)
     assert st[0] == 3                                       # broken pivot reported as an outlier
+    if knobs:                                               # (the gate itself touched nothing)
+        assert all(np.array_equal(x, y_) for b in range(2) for x, y_ in zip(g.get_state(b), before[b]))
     g.visual_update(H, v, 0.0)
     m0, P0 = g.get_state(0)
     assert np.isfinite(m0).all() and np.isfinite(P0).all()

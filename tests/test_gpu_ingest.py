@@ -12,6 +12,18 @@ RADIAL = [-0.28340811, 0.07395907, 0.0]
 FISH = [0.0034823894022493434, 0.0007150348452162257, -0.0020532361418706202, 0.00020293673591811182]
 
 
+# knob ingest_gather (read by launch_ingest at every call): 1 = the plain gather kernel (ingest_kernel<CH, true>) for every map; 0 = the
+# LDS-tile kernel (remap_tile_kernel) wherever the map's tiles fit its staging buffer. launch_ingest tests the knob alone, so get_knob
+# says which of the two served a map that has tiles.
+INGEST_GATHER = [0, 1]
+
+
+def _knobs(ctx, knobs):
+    for k, v in (knobs or {}).items():
+        ctx.set_knob(k, v)
+        assert ctx.get_knob(k) == v
+
+
 def _colour(gray, ch, seed):
     rng = np.random.default_rng(seed)
     h, w = gray.shape
@@ -56,10 +68,18 @@ def _cams(oracle, w, h, kind):
     return rect, cam
 
 
+@pytest.mark.parametrize("gather", INGEST_GATHER[1:])
 @pytest.mark.parametrize("shape", [(480, 752), (241, 323)])
 @pytest.mark.parametrize("kind", ["radial", "fisheye", "rotated"])
 @pytest.mark.parametrize("ch", [1, 3])
-def test_undistort_remap_bit_exact(oracle, shape, kind, ch):
+def test_undistort_remap_bit_exact_gather(oracle, shape, kind, ch, gather):
+    test_undistort_remap_bit_exact(oracle, shape, kind, ch, knobs={"ingest_gather": gather})
+
+
+@pytest.mark.parametrize("shape", [(480, 752), (241, 323)])
+@pytest.mark.parametrize("kind", ["radial", "fisheye", "rotated"])
+@pytest.mark.parametrize("ch", [1, 3])
+def test_undistort_remap_bit_exact(oracle, shape, kind, ch, knobs=None):
     h, w = shape
     base = synth.stereo_sequence(13, w, h, 1)[0][0]
     img = base if ch == 1 else _colour(base, ch, 3)
@@ -69,6 +89,7 @@ def test_undistort_remap_bit_exact(oracle, shape, kind, ch):
     want = oracle.undistort_apply(gray, pix, valid)
     assert (want == 0).mean() < 0.9
     with capi.Context(width=w, height=h) as ctx:
+        _knobs(ctx, knobs)
         ctx.ingest_set_undistort_map(1, pix, valid)
         s = ctx.acquire()
         ctx.ingest_build(s, img, camera=1)
@@ -81,7 +102,12 @@ def test_undistort_remap_bit_exact(oracle, shape, kind, ch):
             ctx.ingest_build(s, img, camera=0)
 
 
-def test_edge_taps_and_invalid_pixels(oracle):
+@pytest.mark.parametrize("gather", INGEST_GATHER[1:])
+def test_edge_taps_and_invalid_pixels_gather(oracle, gather):
+    test_edge_taps_and_invalid_pixels(oracle, knobs={"ingest_gather": gather})
+
+
+def test_edge_taps_and_invalid_pixels(oracle, knobs=None):
     """Source positions in the last column / row (the unchecked at() of undistorter.cpp:99) and failed camera calls."""
     h, w = 120, 172
     rng = np.random.default_rng(2)
@@ -93,6 +119,7 @@ def test_edge_taps_and_invalid_pixels(oracle):
     want = oracle.undistort_apply(img, pix, valid)
     assert want[5, 7] == want[6, 7] == want[7, 7] == want[8, 7] == 0 and (want[20:30, 40:50] == 0).all()
     with capi.Context(width=w, height=h) as ctx:
+        _knobs(ctx, knobs)
         ctx.ingest_set_undistort_map(0, pix, valid)
         s = ctx.acquire()
         ctx.ingest_build(s, img, camera=0)
@@ -119,8 +146,14 @@ def test_maps_whose_tiles_do_not_fit_the_staging_buffer(oracle, ch):
             assert np.array_equal(ctx.download(s, 0)[0], oracle.undistort_apply(gray, pix, np.ones((h, w), np.uint8)))
 
 
+@pytest.mark.parametrize("gather", INGEST_GATHER[1:])
+@pytest.mark.parametrize("ch,camera", [(4, 0), (1, 1)])          # (the cases with a remap: without a camera the knob is not read)
+def test_batch_dev_with_padded_rows_gather(oracle, ch, camera, gather):
+    test_batch_dev_with_padded_rows(oracle, ch, camera, knobs={"ingest_gather": gather})
+
+
 @pytest.mark.parametrize("ch,camera", [(1, -1), (3, -1), (4, 0), (1, 1)])
-def test_batch_dev_with_padded_rows(oracle, ch, camera):
+def test_batch_dev_with_padded_rows(oracle, ch, camera, knobs=None):
     import torch
     h, w, n = 250, 330, 3
     frames = synth.stereo_sequence(17, w, h, n)[0]
@@ -132,6 +165,7 @@ def test_batch_dev_with_padded_rows(oracle, ch, camera):
     rect, cam = _cams(oracle, w, h, "radial")
     pix, valid = oracle.undistort_map(rect, cam, w, h)
     with capi.Context(width=w, height=h, pool_size=4) as ctx:
+        _knobs(ctx, knobs)
         if camera >= 0:
             ctx.ingest_set_undistort_map(camera, pix, valid)
         slots = [ctx.acquire() for _ in range(n)]

@@ -186,17 +186,32 @@ def problems4(oracle):
     return [_problem(oracle, 9100 + i, B=64) for i in range(4)]
 
 
-@pytest.mark.parametrize("mode", ["concurrent_eager", "concurrent_graph_replay"])
-def test_four_lanes_of_64_distinct_ragged_filters(problems4, mode):
+# knobs beside the sorted schedule: none, or the interleaved one-stream launch order 2 (T long, T short, G long, G short) of the split form
+LANE_DEFAULTS = {"ekf_side_stream": 5}            # what hv_lanes_create sets: the fork, but never inside a stream capture
+LANE_ORDERS = {"order0": {}, "order2_split": {"ekf_long_first": 2, "ekf_split_tri": 2}}
+
+
+@pytest.mark.parametrize("mode,order", [pytest.param("concurrent_eager", "order0", id="concurrent_eager"),
+                                        pytest.param("concurrent_graph_replay", "order0", id="concurrent_graph_replay"),
+                                        pytest.param("concurrent_eager", "order2_split", id="concurrent_eager-order2_split"),
+                                        pytest.param("concurrent_graph_replay", "order2_split", id="concurrent_graph_replay-order2_split")])
+def test_four_lanes_of_64_distinct_ragged_filters(problems4, mode, order):
     """The benchmark's default lane count: four lanes in flight at once (eager: each forks onto its own second stream; captured: one
-    stream per lane), the sorted two-class schedule forced at 64 filters per lane (knob ekf_visit_order 2), every filter vs the oracle."""
+    stream per lane), the sorted two-class schedule forced at 64 filters per lane (knob ekf_visit_order 2), every filter vs the oracle.
+    order2_split: a lane under capture is the one place where the default configuration reaches the one-stream launch orders (knob
+    ekf_side_stream 5 does not fork while its stream is being captured, so `order` in visual_track_dev_impl is the knob's value; the
+    split form -- what more than 256 filters per lane run -- is forced at 64 so that the order really interleaves four launches). Eagerly
+    the same lanes fork and the order knob is not read: that half runs the forced split form under four concurrent forks."""
     import torch
     with capi.Lanes(4, width=64, height=64) as lanes:
         assert len({c.get_stream() for c in lanes.ctx}) == 4
         L = [_Lane(lanes.ctx[i], problems4[i]) for i in range(4)]
         for l in L:
             l.ctx.set_knob("ekf_visit_order", 2)
-            assert l.ctx.get_knob("ekf_side_stream") == 5
+            for k_, v_ in LANE_ORDERS[order].items():
+                l.ctx.set_knob(k_, v_)
+                assert l.ctx.get_knob(k_) == v_
+            assert all(l.ctx.get_knob(k_) == v_ for k_, v_ in LANE_DEFAULTS.items())
             l.reset()
         torch.cuda.synchronize()
         if mode == "concurrent_eager":
@@ -227,7 +242,7 @@ def test_four_lanes_of_64_distinct_ragged_filters(problems4, mode):
                 torch.cuda.synchronize()
             del graphs
         for i, l in enumerate(L):
-            l.check(f"{mode} lane {i} of 4")
+            l.check(f"{mode} {order} lane {i} of 4")
         for l in L:
             l.g.close()
 

@@ -70,10 +70,34 @@ def test_pyramids_and_lk_over_640_slots_and_320_pairs(oracle):
         assert 0 < lost < D * NPTS // 4
 
 
-@pytest.mark.parametrize("n_sets,threads", [(80, 0), (80, 1024), (7, 256), (300, 0), (80, 25)])       # 25: the split form, 2000 workgroups
-def test_rot_ransac_both_instantiations(oracle, n_sets, threads):
-    """rot_ransac_kernel<256> (what more than 64 sets -- the benchmark's 1024 -- run) and <1024>, each forced at both batch sizes."""
+def _rot_ransac_form(n_sets, threads, num_cus):
+    """launch_rot_ransac's choice restated (rot_ransac.hip): the split form (25 workgroups per set) runs only while the launch fits the
+    context's split records -- max(16, num_cus / 25) sets, so 16 on a 256-CU part -- whether the knob forces it (25) or auto picks it
+    (every workgroup gets a CU); beyond that a forced 25 is NOT served: the launch takes the 1024-thread form up to 64 sets and the
+    256-thread form above, like auto."""
+    cap = max(16, num_cus // 25)
+    if n_sets <= cap and (threads == 25 or (threads == 0 and 25 * n_sets <= num_cus)):
+        return "split"
+    if threads == 1024 or (threads != 256 and n_sets <= 64):
+        return "1024"
+    return "256"
+
+
+ROT_RANSAC_THREADS = [0, 25, 256, 1024]
+# (sets, knob, the form that serves the launch on a 256-CU part). 80 sets with the knob at 25 used to pass under the name of the split
+# form: it runs the 256-thread one. The split form forced: at its record limit (16 sets, 400 workgroups) and below it.
+ROT_RANSAC_CASES = [pytest.param(80, 0, "256", id="80-0"), pytest.param(80, 1024, "1024", id="80-1024"), pytest.param(7, 256, "256", id="7-256"),
+                    pytest.param(300, 0, "256", id="300-0"), pytest.param(80, 25, "256", id="80-25-not_served_runs_256_threads"),
+                    pytest.param(16, 25, "split", id="16-25-split_at_its_record_limit"), pytest.param(12, 25, "split", id="12-25-split")]
+
+
+@pytest.mark.parametrize("n_sets,threads,form", ROT_RANSAC_CASES)
+def test_rot_ransac_both_instantiations(oracle, n_sets, threads, form):
+    """rot_ransac_kernel<256> (what more than 64 sets -- the benchmark's 1024 -- run) and <1024>, each forced at both batch sizes, and
+    the split form forced where it is served. `form` names the kernel the launch rule picks for the case (asserted against the rule
+    with the device's CU count; the profile has one class for all three forms, so the rule is the evidence)."""
     import torch
+    assert _rot_ransac_form(n_sets, threads, torch.cuda.get_device_properties(0).multi_processor_count) == form
     from test_gpu_rot_ransac import _cams, _scene, _pairs, THR
     ocam, gcam = _cams(oracle, "pinhole")
     rng = np.random.default_rng(1000 + n_sets)
@@ -98,6 +122,7 @@ def test_rot_ransac_both_instantiations(oracle, n_sets, threads):
     with capi.Context(width=W, height=H) as ctx:
         if threads:
             ctx.set_knob("rot_ransac_threads", threads)
+        assert ctx.get_knob("rot_ransac_threads") == threads
         dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
         d_n, d_c1, d_c2, d_pairs = dev(sizes.astype(np.int32)), dev(c1), dev(c2), dev(pairs)
         st = torch.full((n_sets, M), -5, dtype=torch.int32, device="cuda")
@@ -121,7 +146,8 @@ def _filters(oracle, rng, B, trail_len, npose, stereo):
     return T1, T2, means
 
 
-@pytest.mark.parametrize("variant", ["default", "dense", "gate_own_launch"])
+# (ekf_stream_gate 0: the dense visit loop never takes the streaming gate -- the same launches as `dense`, with the knob off instead of auto)
+@pytest.mark.parametrize("variant", ["default", "dense", "gate_own_launch", "dense_no_stream_gate"])
 def test_frame_of_320_distinct_filters(oracle, variant):
     """hv_ekf_visual_frame_dev over 320 DISTINCT filters (sequential visit loop: 320 x 8 > 256), 10-pose stereo tracks = the
     benchmark's 40-row shape, followed by symmetrise, the Joseph-form augmentation with per-filter discard slots and 10 predicts in
@@ -145,6 +171,7 @@ def test_frame_of_320_distinct_filters(oracle, variant):
     with capi.Context(width=64, height=64) as ctx:
         for k_, v_ in VARIANTS[variant].items():
             ctx.set_knob(k_, v_)
+            assert ctx.get_knob(k_) == v_
         g = capi.EkfBatch(ctx, capi.ekf_default_params(cameraTrailLength=trail_len), B)
         filters = []
         for b in range(B):
@@ -203,14 +230,27 @@ def test_frame_of_320_distinct_filters(oracle, variant):
         g.close()
 
 
+NO_STREAM_GATE = {"ekf_stream_gate": 0}
+
+
 @pytest.mark.parametrize("rows", [40, 16, 8])
-def test_gate_only_and_gated_update_over_320_filters(oracle, rows):
+def test_gate_only_over_320_filters_without_the_streaming_kernel(oracle, rows):
+    """knob ekf_stream_gate 0: the gate-only entry keeps ekf_update_kernel (mode 0) above 256 filters too, where auto takes
+    ekf_gate_stream_kernel (hv_ekf_visual_dev reads the knob at every call)."""
+    test_gate_only_and_gated_update_over_320_filters(oracle, rows, knobs=NO_STREAM_GATE)
+
+
+@pytest.mark.parametrize("rows", [40, 16, 8])
+def test_gate_only_and_gated_update_over_320_filters(oracle, rows, knobs=None):
     """hv_ekf_visual_dev at a batch that selects ekf_gate_stream_kernel (mode 0, > 256 filters) and runs ekf_update_kernel in more than
     one round (mode 2: update where the gate passes), dense random Jacobians, distinct filters."""
     import torch
     rng = np.random.default_rng(77 + rows)
     B = 320
     with capi.Context(width=64, height=64) as ctx:
+        for k_, v_ in (knobs or {}).items():
+            ctx.set_knob(k_, v_)
+            assert ctx.get_knob(k_) == v_
         g = capi.EkfBatch(ctx, capi.ekf_default_params(), B)
         n = g.n
         Hs = rng.normal(size=(B, rows, n)); Hs[:, :, 100:] *= (rng.uniform(size=(B, 1, 1)) < 0.5)       # some truncated Jacobians

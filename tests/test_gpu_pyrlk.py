@@ -16,8 +16,23 @@ POS_TOL = 1e-3
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "pyrlk_golden.npz")
 
 
-def _ctx(w, h, **kw):
-    return capi.Context(width=w, height=h, **kw)
+# Kernel variants forced per test (both knobs are read at every launch, so hv_debug_set_knob selects them; launch_klt and
+# launch_pyramid_levels dispatch on the knob's value alone wherever the variant exists, so get_knob says what ran):
+#   klt_tile 1      klt_kernel<40, 36, 2, 1, 4> (the 4-waves-per-SIMD build) instead of the default's <.., 5>. The ragged batch entry
+#                   (pts_in_pair_dev) ignores the knob -- one build -- so forcing it there would test nothing: not parametrized.
+#   pyr_l0_tiled 1  the pure down-sample levels (no stored gradient plane: levels 0 and 1 by default) through the LDS-tile kernel
+#                   pyr_level_kernel instead of pyr_down_l0_kernel.
+KLT_TILES = [5, 1]
+PYR_L0_TILED = [0, 1]
+PYR_TAIL = {"fused": 1, "per_level": 0}     # HV_PYR_TAIL, read in hv_create
+
+
+def _ctx(w, h, knobs=None, **kw):
+    ctx = capi.Context(width=w, height=h, **kw)
+    for k, v in (knobs or {}).items():
+        ctx.set_knob(k, v)
+        assert ctx.get_knob(k) == v
+    return ctx
 
 
 def _check_pyramid(ctx, oracle, img, slot):
@@ -30,14 +45,17 @@ def _check_pyramid(ctx, oracle, img, slot):
     return ref
 
 
+PYRAMID_SHAPES = [(480, 752), (720, 1280), (479, 641), (70, 101), (33, 65), (97, 64), (256, 260)]
+
+
 @pytest.mark.parametrize("tail", ["fused", "per_level"])
-@pytest.mark.parametrize("shape", [(480, 752), (720, 1280), (479, 641), (70, 101), (33, 65), (97, 64), (256, 260)])
-def test_pyramid_bit_exact(oracle, shape, tail, monkeypatch):
+@pytest.mark.parametrize("shape", PYRAMID_SHAPES)
+def test_pyramid_bit_exact(oracle, shape, tail, monkeypatch, knobs=None):
     # levels >= 2 are built by one LDS-resident launch for large batches and by per-level launches otherwise: force each
-    monkeypatch.setenv("HV_PYR_TAIL", "1" if tail == "fused" else "0")
+    monkeypatch.setenv("HV_PYR_TAIL", str(PYR_TAIL[tail]))
     rng = np.random.default_rng(shape[0] * 7 + shape[1])
     img = rng.integers(0, 256, shape, dtype=np.uint8)
-    with _ctx(shape[1], shape[0]) as ctx:
+    with _ctx(shape[1], shape[0], knobs) as ctx:
         s = ctx.acquire()
         ctx.build(s, img)
         _check_pyramid(ctx, oracle, img, s)
@@ -49,6 +67,14 @@ def test_pyramid_bit_exact(oracle, shape, tail, monkeypatch):
         assert rc == 0
         ctx.synchronize()
         _check_pyramid(ctx, oracle, np.ascontiguousarray(img[::-1]), s2)
+
+
+@pytest.mark.parametrize("l0_tiled", PYR_L0_TILED[1:])
+@pytest.mark.parametrize("tail", ["fused", "per_level"])
+@pytest.mark.parametrize("shape", PYRAMID_SHAPES)
+def test_pyramid_bit_exact_l0_tiled(oracle, shape, tail, l0_tiled, monkeypatch):
+    """... with the down-sample levels on pyr_level_kernel (level widths 641, 101, 65, 33: no multiple of any tile)."""
+    test_pyramid_bit_exact(oracle, shape, tail, monkeypatch, knobs={"pyr_l0_tiled": l0_tiled})
 
 
 def test_pool_grows_on_demand_like_the_reference_allocator(oracle, seq752):
@@ -76,10 +102,15 @@ def test_pool_grows_on_demand_like_the_reference_allocator(oracle, seq752):
         np.testing.assert_array_equal(xy[st > 0], oxy[ost > 0])
 
 
-def test_pyramid_extreme_images(oracle):
+@pytest.mark.parametrize("l0_tiled", PYR_L0_TILED[1:])
+def test_pyramid_extreme_images_l0_tiled(oracle, l0_tiled):
+    test_pyramid_extreme_images(oracle, knobs={"pyr_l0_tiled": l0_tiled})
+
+
+def test_pyramid_extreme_images(oracle, knobs=None):
     for img in (np.zeros((480, 752), np.uint8), np.full((480, 752), 255, np.uint8),
                 (np.indices((480, 752)).sum(0) % 2 * 255).astype(np.uint8)):    # checkerboard: max |gradient|
-        with _ctx(752, 480) as ctx:
+        with _ctx(752, 480, knobs) as ctx:
             s = ctx.acquire()
             ctx.build(s, img)
             _check_pyramid(ctx, oracle, img, s)
@@ -127,10 +158,10 @@ def _compare_klt(ctx, oracle, refp, refn, sp, sn, pts, guess=None, **kw):
     return g_xy, g_st
 
 
-def test_klt_parity_752_temporal_and_stereo(oracle, seq752):
+def test_klt_parity_752_temporal_and_stereo(oracle, seq752, knobs=None):
     left, right, warps = seq752
     pts = synth.grid_points(752, 480, 200)
-    with _ctx(752, 480) as ctx:
+    with _ctx(752, 480, knobs) as ctx:
         s0, s1, sr = ctx.acquire(), ctx.acquire(), ctx.acquire()
         ctx.build(s0, left[0]); ctx.build(s1, left[1]); ctx.build(sr, right[1])
         r0, r1, rr = oracle.Pyramid(left[0]), oracle.Pyramid(left[1]), oracle.Pyramid(right[1])
@@ -143,10 +174,20 @@ def test_klt_parity_752_temporal_and_stereo(oracle, seq752):
         _compare_klt(ctx, oracle, r0, r1, s0, s1, pts, max_iter_override=3)
 
 
-def test_klt_parity_borders_failures_and_ragged_counts(oracle, seq752):
+@pytest.mark.parametrize("klt_tile", KLT_TILES[1:])
+def test_klt_parity_752_temporal_and_stereo_forced_tile(oracle, seq752, klt_tile):
+    test_klt_parity_752_temporal_and_stereo(oracle, seq752, knobs={"klt_tile": klt_tile})
+
+
+@pytest.mark.parametrize("klt_tile", KLT_TILES[1:])
+def test_klt_parity_borders_failures_and_ragged_counts_forced_tile(oracle, seq752, klt_tile):
+    test_klt_parity_borders_failures_and_ragged_counts(oracle, seq752, knobs={"klt_tile": klt_tile})
+
+
+def test_klt_parity_borders_failures_and_ragged_counts(oracle, seq752, knobs=None):
     left, _, _ = seq752
     rng = np.random.default_rng(11)
-    with _ctx(752, 480) as ctx:
+    with _ctx(752, 480, knobs) as ctx:
         s0, s2, sf = ctx.acquire(), ctx.acquire(), ctx.acquire()
         flat = np.full((480, 752), 128, np.uint8)
         ctx.build(s0, left[0]); ctx.build(s2, left[2]); ctx.build(sf, flat)
@@ -174,15 +215,24 @@ def test_klt_parity_borders_failures_and_ragged_counts(oracle, seq752):
         assert e_xy.shape == (0, 2) and e_fs.shape == (0,)
 
 
-@pytest.mark.parametrize("shape", [(720, 1280), (150, 200), (70, 101)])
-def test_klt_parity_other_sizes(oracle, shape):
+KLT_OTHER_SIZES = [(720, 1280), (150, 200), (70, 101)]
+
+
+@pytest.mark.parametrize("klt_tile", KLT_TILES[1:])
+@pytest.mark.parametrize("shape", KLT_OTHER_SIZES)
+def test_klt_parity_other_sizes_forced_tile(oracle, shape, klt_tile):
+    test_klt_parity_other_sizes(oracle, shape, knobs={"klt_tile": klt_tile})
+
+
+@pytest.mark.parametrize("shape", KLT_OTHER_SIZES)
+def test_klt_parity_other_sizes(oracle, shape, knobs=None):
     h, w = shape
     tex = synth.Texture.make(5)
     a = synth.render(tex, w, h, synth.Warp.make(0, 0, 0, w / 2, h / 2))
     b = synth.render(tex, w, h, synth.Warp.make(0.5, 2.2, -1.4, w / 2, h / 2), noise_seed=3, noise_sigma=2.0)
     n = 400 if w == 1280 else 64
     pts = synth.grid_points(w, h, n, margin=6, seed=2)
-    with _ctx(w, h, max_tracks=n) as ctx:
+    with _ctx(w, h, knobs, max_tracks=n) as ctx:
         sa, sb = ctx.acquire(), ctx.acquire()
         ctx.build(sa, a); ctx.build(sb, b)
         _, st = _compare_klt(ctx, oracle, oracle.Pyramid(a), oracle.Pyramid(b), sa, sb, pts)
@@ -270,8 +320,14 @@ def test_full_size_property_identity_tracking(oracle, seq752):
         assert np.abs(xy - pts).max() < 1e-4
 
 
+@pytest.mark.parametrize("klt_tile", KLT_TILES[1:])
 @pytest.mark.parametrize("seed", range(12))
-def test_randomised_shapes_motions_and_points(oracle, seed):
+def test_randomised_shapes_motions_and_points_forced_tile(oracle, seed, klt_tile):
+    test_randomised_shapes_motions_and_points(oracle, seed, knobs={"klt_tile": klt_tile})
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_randomised_shapes_motions_and_points(oracle, seed, knobs=None):
     """Seeded sweep over image sizes (odd / tiny / non-multiple-of-4 strides -> every border and unaligned path),
     textures from noise to smooth, motions up to several pixels, points anywhere incl. far outside, with and
     without an initial guess and with iteration caps: pyramid bit-exact, LK status and positions identical."""
@@ -288,7 +344,7 @@ def test_randomised_shapes_motions_and_points(oracle, seed):
     n = int(rng.integers(1, 150))
     pts = rng.uniform([-40, -40], [w + 40, h + 40], (n, 2)).astype(np.float32)
     pts[: n // 2] = rng.uniform([0, 0], [w, h], (n // 2, 2)).astype(np.float32)
-    with _ctx(w, h) as ctx:
+    with _ctx(w, h, knobs) as ctx:
         sa, sb = ctx.acquire(), ctx.acquire()
         ctx.build(sa, a); ctx.build(sb, b)
         ra = _check_pyramid(ctx, oracle, a, sa)
@@ -319,7 +375,12 @@ def test_tracker_parameters_other_than_the_defaults(oracle, seq752, levels, max_
         np.testing.assert_array_equal(g_err, o_err)
 
 
-def test_level0_used_in_place_with_a_padded_row_stride(oracle, seq752):
+@pytest.mark.parametrize("l0_tiled", PYR_L0_TILED[1:])
+def test_level0_used_in_place_with_a_padded_row_stride_l0_tiled(oracle, seq752, l0_tiled):
+    test_level0_used_in_place_with_a_padded_row_stride(oracle, seq752, knobs={"pyr_l0_tiled": l0_tiled})
+
+
+def test_level0_used_in_place_with_a_padded_row_stride(oracle, seq752, knobs=None):
     """hv_pyramid_build_batch_dev uses the caller's images as level 0 without copying them: row stride > width
     (and an image stride that is not the packed size) must reach the pyramid, LK and GFTT kernels alike."""
     import torch
@@ -329,7 +390,7 @@ def test_level0_used_in_place_with_a_padded_row_stride(oracle, seq752):
     buf = np.full((3, pitch), 213, np.uint8)
     for i in range(3):
         buf[i, :800 * 480].reshape(480, 800)[:, :752] = imgs[i]
-    with _ctx(752, 480, pool_size=4) as ctx:
+    with _ctx(752, 480, knobs, pool_size=4) as ctx:
         ctx.set_stream(torch.cuda.current_stream().cuda_stream)
         d_buf = torch.from_numpy(buf).cuda()
         slots = [ctx.acquire() for _ in range(3)]

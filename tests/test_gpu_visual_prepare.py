@@ -49,6 +49,47 @@ VARIANTS = {
     # (the split form's short class ends at 12 stereo poses = 48 rows; 11 = the fused builds' boundary)
     "split_tri_short11": {"ekf_split_tri": 2, "ekf_visit_order": 2, "ekf_short_np": 11},
 }
+# Launch orders of a ONE-STREAM sorted ragged visit (knob ekf_long_first, ekf_visit.hip: `order`): 1 = long class first, 2 .. 4 = both
+# triangulations in front of both gates. The knob is only read when the visit is presorted (ekf_visit_order 2 at these batch sizes) and
+# does not fork (ekf_side_stream 0) -- what a lane runs under capture. Three forms of every order: r06's split kernels, r05's fused kernels
+# (ekf_split_tri 0: the triangulation phase is a no-op, the gate phase the whole launch) and r03's two-launch long class (ekf_long_fused 0:
+# prepare + gate are both the gate phase; the interleaved orders used to issue the pair in BOTH phases and applied every long inlier twice).
+_ONE_STREAM = {"ekf_side_stream": 0, "ekf_visit_order": 2}
+for _k in (1, 2, 3, 4):
+    VARIANTS[f"order{_k}"] = {"ekf_long_first": _k, **_ONE_STREAM, "ekf_split_tri": 2}
+    VARIANTS[f"order{_k}_fused_front"] = {"ekf_long_first": _k, **_ONE_STREAM, "ekf_split_tri": 0}
+    VARIANTS[f"order{_k}_long_two_launches"] = {"ekf_long_first": _k, **_ONE_STREAM, "ekf_split_tri": 2, "ekf_long_fused": 0}
+VARIANTS["order2_short11"] = {"ekf_long_first": 2, **_ONE_STREAM, "ekf_split_tri": 2, "ekf_short_np": 11}
+# The triangulation front at every width (knob vu_tri_threads: vu_tri_kernel / _x2 / _x4). Auto only ever picks 128 for the short class and
+# 256 for the long one. launch_vu_tri takes a forced width for every shape: the LDS plan (TriLds) depends on the pose count alone, the body
+# strides every loop by its width and its widest fixed lane group (63 pose-0 sums) fits one wavefront -- so the split form's launch counts
+# below plus get_knob say which kernel ran.
+# the dense visit loop (ekf_fused_gate 0) with the streaming gate kernel + the register-resident update instead of its one-launch gate +
+# update (ekf_stream_gate 1, read in visual_track_dev_impl for uniform visits), and with the knob off instead of auto
+VARIANTS["dense_stream_gate"] = {"ekf_fused_gate": 0, "ekf_stream_gate": 1}
+VARIANTS["dense_no_stream_gate"] = {"ekf_fused_gate": 0, "ekf_stream_gate": 0}
+# ekf_split_tri 3 (profiles/r06/split_short_class_only.txt): the split form for the short class only -- which needs more than 256 filters,
+# as with the default 1 -- while the long class keeps vu_gate_long_kernel
+VARIANTS["tri_short_class_only"] = {"ekf_split_tri": 3, "ekf_visit_order": 2}
+for _w in (64, 128, 256):
+    VARIANTS[f"tri{_w}"] = {"vu_tri_threads": _w, "ekf_split_tri": 2, "ekf_visit_order": 2}
+
+
+def _visit_launches(knobs, B):
+    """(HV_K_VU_TRI, HV_K_VU_PREPARE, HV_K_EKF_GATE) launches of ONE two-class ragged visit, from the schedule in ekf_visit.hip
+    (visual_track_dev_impl, Visit::split_launch / long_prepare_gate):
+      short class: split form (ekf_split_tri 2, or 1 above 256 filters) = vu_tri launch + record-fed gate (timed as VU_PREPARE);
+                   otherwise one fused prepare + gate launch (VU_PREPARE);
+      long class:  ekf_long_fused 1 = the same two forms; ekf_long_fused 0 = vu_compact_kernel (VU_PREPARE) + ekf_sparse_gate_big_kernel
+                   (EKF_GATE), no triangulation launch of its own.
+    The launch ORDER (ekf_long_first) moves launches, it never adds one: a count above these is a launch issued twice."""
+    st = knobs.get("ekf_split_tri", 1)
+    split = st == 2 or (st in (1, 3) and B > 256)
+    long_fused = knobs.get("ekf_long_fused", 1) != 0
+    return (int(split) + int(split and long_fused and st != 3), 2, 0 if long_fused else 1)
+
+
+SEQUENTIAL_LOOP = {"ekf_no_speculation": 1}      # the device's own sequential visit loop (reference run of the contention test)
 
 
 def _well_conditioned(diag):
@@ -271,7 +312,9 @@ def test_parameters_reach_the_kernel(oracle):
                                            # vu_compact_kernel + ekf_sparse_gate_big_kernel; `dense`: r02's H-from-L2 / global-workspace kernels
                                            ("default", 13), ("default", 16), ("default", 17), ("default", 20), ("default", 21), ("dense", 21), ("default", 12),
                                            ("long_two_launches", 13), ("long_two_launches", 20), ("long_two_launches", 21),
-                                           ("jacobian_in_front_of_the_gate", 13), ("jacobian_in_front_of_the_gate", 21)])
+                                           ("jacobian_in_front_of_the_gate", 13), ("jacobian_in_front_of_the_gate", 21),
+                                           # the dense loop's streaming gate + update launches: 36 rows and its 48-row limit
+                                           ("dense_stream_gate", 9), ("dense_stream_gate", 12)])
 def test_visual_track_dev_prepare_gate_update_equals_the_reference_sequence(oracle, variant, npose):
     """hv_ekf_visual_track_dev = backend.cpp:1063-1185 for one track per filter: prepare from the device mean, gate with
     trackChiTestOutlierR, update with visualR only where triangulation, prepare and gate pass. Filters that fail stay
@@ -303,9 +346,17 @@ def test_visual_track_dev_prepare_gate_update_equals_the_reference_sequence(orac
         chi = torch.zeros((B,), dtype=torch.float64, device="cuda")
         pf = torch.zeros((B, 3), dtype=torch.float64, device="cuda")
         ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        if variant == "dense_stream_gate":
+            ctx.profile_enable(True)
+            ctx.profile_reset()
         g.visual_track_dev(vp, npose, d_idx.data_ptr(), d_feat.data_ptr(), d_vel.data_ptr(), d_y.data_ptr(), r_gate, r_update,
                            st.data_ptr(), gs.data_ptr(), chi.data_ptr(), pf.data_ptr())
         torch.cuda.synchronize()
+        if variant == "dense_stream_gate":
+            # dense prepare, then the streaming gate and the update as TWO launches of the update class; `dense` runs these shapes (up to
+            # 48 rows, n = 160) as ONE gate + update launch (mode 3), so two launches say that the streaming kernel took the gate
+            assert [ctx.profile_read(kid)[1] for kid in (capi.K_VU_PREPARE, capi.K_EKF_UPDATE, capi.K_EKF_GATE)] == [1, 2, 0]
+            ctx.profile_enable(False)
         st, gs, chi = st.cpu().numpy(), gs.cpu().numpy(), chi.cpu().numpy()
         outcomes = set()
         for b, o in enumerate(filters):
@@ -332,7 +383,8 @@ def test_visual_track_dev_prepare_gate_update_equals_the_reference_sequence(orac
         g.close()
 
 
-@pytest.mark.parametrize("variant,npose", [("default", 13), ("default", 17), ("default", 21), ("long_two_launches", 21), ("default", 9)])
+@pytest.mark.parametrize("variant,npose", [("default", 13), ("default", 17), ("default", 21), ("long_two_launches", 21), ("default", 9)]
+                         + [(f"tri{w}", n) for w in (64, 128, 256) for n in (13, 21)])     # every width of the split form's front
 def test_long_gate_chi2_with_time_shift_cross_covariance(oracle, variant, npose):
     """r04 advisor: structured_S (the factor form of the long class's gate, ekf_device.hpp) left W(:, sft) * dpf/dt out of WF = W F4'.
     The term only shows when P couples the IMU-camera time shift (state 19) with the poses -- here strongly -- and the track has a
@@ -366,9 +418,16 @@ def test_long_gate_chi2_with_time_shift_cross_covariance(oracle, variant, npose)
         chi = torch.zeros((B,), dtype=torch.float64, device="cuda")
         pf = torch.zeros((B, 3), dtype=torch.float64, device="cuda")
         ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        split = variant.startswith("tri")
+        if split:
+            ctx.profile_enable(True)
+            ctx.profile_reset()
         g.visual_track_dev(vp, npose, d_idx.data_ptr(), d_feat.data_ptr(), d_vel.data_ptr(), d_y.data_ptr(), 1.5, 0.05,
                            st.data_ptr(), gs.data_ptr(), chi.data_ptr(), pf.data_ptr())
         torch.cuda.synchronize()
+        if split:      # a uniform long visit in split form (Visit::split_launch): one vu_tri launch + one record-fed gate (VU_PREPARE)
+            assert [ctx.profile_read(kid)[1] for kid in (capi.K_VU_TRI, capi.K_VU_PREPARE, capi.K_EKF_GATE)] == [1, 1, 0]
+            ctx.profile_enable(False)
         st, gs, chi = st.cpu().numpy(), gs.cpu().numpy(), chi.cpu().numpy()
         compared, coupled = 0, 0
         for b, o in enumerate(filters):
@@ -389,7 +448,10 @@ def test_long_gate_chi2_with_time_shift_cross_covariance(oracle, variant, npose)
 
 
 @pytest.mark.parametrize("variant,npose,B", [("default", 10, 64), ("vu384", 11, 300), ("gate_own_launch", 9, 64), ("default", 21, 64),
-                                             ("long_two_launches", 17, 64)])
+                                             ("long_two_launches", 17, 64)]
+                         # r06's record-fed gates behind every width of the triangulation front, a short and a long shape each (the
+                         # claim is per width; whether two widths agree to the bit is promised nowhere and not asserted)
+                         + [(f"tri{w}", n, 64) for w in (64, 128, 256) for n in (10, 21)])
 def test_gate_is_reproducible_to_the_bit(oracle, variant, npose, B):
     """r05: the partial sums of S = Hc P(a, a) Hc' meet in LDS in a fixed order (ekf_device.hpp sparse_gate: a turn counter per column
     tile; the long build's factor form never used atomics), so chi2 -- and with it the gate status -- is the same bit pattern every time
@@ -414,6 +476,10 @@ def test_gate_is_reproducible_to_the_bit(oracle, variant, npose, B):
         ctx.set_stream(torch.cuda.current_stream().cuda_stream)
         runs = []
         busy = torch.zeros(1 << 22, device="cuda")
+        split = variant.startswith("tri")
+        if split:
+            ctx.profile_enable(True)
+            ctx.profile_reset()
         for rep in range(6):
             for b in range(B):
                 g.set_state(b, means[b], Ps[b])
@@ -428,13 +494,18 @@ def test_gate_is_reproducible_to_the_bit(oracle, variant, npose, B):
                                st.data_ptr(), gs.data_ptr(), chi.data_ptr(), pf.data_ptr())
             torch.cuda.synchronize()
             runs.append((chi.cpu().numpy().view(np.uint64).copy(), gs.cpu().numpy().copy()))
+        if split:      # six uniform visits in split form: one vu_tri launch + one record-fed gate (VU_PREPARE) each, short or long class
+            assert [ctx.profile_read(kid)[1] for kid in (capi.K_VU_TRI, capi.K_VU_PREPARE, capi.K_EKF_GATE)] == [6, 6, 0]
+            ctx.profile_enable(False)
+        import zlib
+        print(f"{variant} np={npose} B={B}: crc32 of the chi2 bit patterns {zlib.crc32(runs[0][0].tobytes()):08x}")
         assert (runs[0][1] == 0).sum() + (runs[0][1] == 3).sum() >= B // 2           # gated tracks
         for chi_bits, gs_ in runs[1:]:
             assert np.array_equal(chi_bits, runs[0][0]) and np.array_equal(gs_, runs[0][1])
         g.close()
 
 
-@pytest.mark.parametrize("variant", ["default", "vu384", "dense", "gate_own_launch_vu384"])
+@pytest.mark.parametrize("variant", ["default", "vu384", "dense", "gate_own_launch_vu384", "dense_stream_gate"])
 def test_frame_loop_with_the_successful_update_quota(oracle, variant):
     """A frame's visual-update loop for a batch (backend.cpp:1012-1240): K tracks per filter, visited in order, each seeing the
     mean the previous one left; a filter stops being visited once maxSuccessfulVisualUpdates updates were applied."""
@@ -462,6 +533,9 @@ def test_frame_loop_with_the_successful_update_quota(oracle, variant):
         dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
         counter = torch.zeros((B,), dtype=torch.int32, device="cuda")
         ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        if variant == "dense_stream_gate":
+            ctx.profile_enable(True)
+            ctx.profile_reset()
         got = []
         for k in range(K):
             idx, feat, vel = tracks[k]
@@ -471,6 +545,9 @@ def test_frame_loop_with_the_successful_update_quota(oracle, variant):
                                        st.data_ptr(), gs.data_ptr(), counter.data_ptr(), quota)
             torch.cuda.synchronize()
             got.append((st.cpu().numpy(), gs.cpu().numpy()))
+        if variant == "dense_stream_gate":     # per visit: dense prepare, streaming gate, update (`dense`: one gate + update launch per visit)
+            assert [ctx.profile_read(kid)[1] for kid in (capi.K_VU_PREPARE, capi.K_EKF_UPDATE, capi.K_EKF_GATE)] == [K, 2 * K, 0]
+            ctx.profile_enable(False)
         counts = counter.cpu().numpy()
         reached = 0
         for b, o in enumerate(filters):
@@ -624,7 +701,7 @@ def test_speculative_frame_loop_under_contention(oracle, variant, npose):
             g.close()
             return out
 
-    ref = run({"ekf_no_speculation": 1}, False)
+    ref = run(dict(SEQUENTIAL_LOOP), False)
     got = run(dict(VARIANTS[variant]), True)
     if got[4] != 0:                                           # loud failure of the hand-shake form: allowed, a silent difference is not
         assert variant == "spec3"
@@ -681,7 +758,14 @@ def test_speculative_frame_loop_under_contention(oracle, variant, npose):
     # ... the class boundary: 12 poses (48 rows) are the record-fed short gate's longest track, 13 the long class's shortest
     (48, False, True, "split_tri", 12), (48, False, True, "split_tri", 13), (300, False, True, "split_tri_short11", 21), (300, False, True, "default", 12),
     # r06: the headline's grid -- 1024 distinct ragged filters in one frame loop, every one against the oracle
-    (1024, False, True, "default", 21)])
+    (1024, False, True, "default", 21)]
+    # every launch order of the one-stream sorted visit in its three forms; 2 .. 4 also above one filter per CU (what captured lanes run)
+    + [(48, False, True, f"order{k}{form}", 21) for form in ("", "_fused_front", "_long_two_launches") for k in (1, 2, 3, 4)]
+    + [(300, False, True, f"order{k}", 21) for k in (2, 3, 4)]
+    + [(48, False, True, "order2_short11", 21)]
+    # every width of the triangulation front over both length classes of one visit (tracks of 2 .. 12 and 13 .. 21 poses)
+    + [(48, False, True, "tri64", 21), (48, False, True, "tri128", 21), (48, False, True, "tri256", 21), (300, False, True, "tri64", 21)]
+    + [(300, False, True, "tri_short_class_only", 21)])
 def test_whole_frame_loop_with_ragged_track_lengths(oracle, B, speculative, stereo, variant, np_max):
     """hv_ekf_visual_frame_ragged_dev: the sequences of a batch do not share track lengths -- every (visit, filter) record has its own
     pose count (2 .. n_poses_max, 0 = this filter has no candidate at this visit), padded to the longest. Result = the reference's
@@ -724,9 +808,20 @@ def test_whole_frame_loop_with_ragged_track_lengths(oracle, B, speculative, ster
         st = torch.full((K, B, 2), -9, dtype=torch.int32, device="cuda"); gs = torch.full((K, B), -9, dtype=torch.int32, device="cuda")
         counter = torch.full((B,), 77, dtype=torch.int32, device="cuda")
         ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        # the forced launch orders / triangulation widths: count the launches of the frame (the timers only record events around the
+        # launches they see, on the stream each launch goes to: the schedule is the unprofiled one)
+        counted = variant.startswith(("order", "tri"))
+        if counted:
+            ctx.profile_enable(True)
+            ctx.profile_reset()
         g.visual_frame_ragged_dev(vp, K, np_max, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
                                   r_gate, r_update, st.data_ptr(), gs.data_ptr(), counter.data_ptr(), quota)
         torch.cuda.synchronize()
+        if counted:
+            # B * K > 256 records: the sequential loop, K visits, each of them two-class (np_max 21 stereo poses), whatever the order
+            got_launches = tuple(ctx.profile_read(kid)[1] for kid in (capi.K_VU_TRI, capi.K_VU_PREPARE, capi.K_EKF_GATE))
+            ctx.profile_enable(False)
+            print(f"{variant} B={B}: vu_tri / vu_prepare / ekf_gate launches {got_launches}")       # (asserted behind the state comparison)
         st, gs, counts = st.cpu().numpy(), gs.cpu().numpy(), counter.cpu().numpy()
         applied, rejected, lengths_applied, ties = 0, 0, set(), 0
         for b, o in enumerate(filters):
@@ -768,6 +863,8 @@ def test_whole_frame_loop_with_ragged_track_lengths(oracle, B, speculative, ster
         assert ties <= 1 + B * K // 1000, ties
         if np_max > 12 and B >= 10:
             assert max(lengths_applied) > 12 and min(lengths_applied) < 12, lengths_applied
+        if counted:                                            # the intended schedule ran, and no launch of it twice
+            assert got_launches == tuple(K * n for n in _visit_launches(VARIANTS[variant], B)), (variant, got_launches)
         g.close()
 
 
