@@ -515,6 +515,13 @@ class Context:
         self._chk(lib().hv_gftt_keypoints_batch_dev(self._h, C.byref(gp), n_images, C.c_void_p(slots_dev),
                                                     C.c_void_p(kp_dev)), "hv_gftt_keypoints_batch_dev")
 
+    def gftt_sqrt_dev(self, x_dev: int, y_dev: int, n: int, wide: bool = False):
+        """y[i] = the detector's correctly rounded square root of x[i], binary32 device arrays (hv_debug_gftt_sqrt: a debug export
+        outside the header, for the tests of the helper); wide: the four-at-once form of the marching kernel."""
+        fn = lib().hv_debug_gftt_sqrt
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int]
+        self._chk(fn(self._h, C.c_void_p(x_dev), C.c_void_p(y_dev), int(n), int(bool(wide))), "hv_debug_gftt_sqrt")
+
     # -- sub-pixel corner refinement --
     def corner_subpix(self, slot: int, xy, params: "SubpixParams" = None):
         """SubPixelAdjuster::adjust on the level-0 image of a built pyramid slot -> (refined xy [n, 2], position updates [n])."""

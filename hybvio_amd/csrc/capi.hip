@@ -297,7 +297,8 @@ static int create_ctx(const hv_params *params, int high_priority, hv_ctx **out)
         p.max_iter < 0 || p.max_tracks < 1)
         return HV_ERR_INVALID;
     if (p.win != 31) return HV_ERR_UNSUPPORTED;   // lane layout of the LK kernel is built for 31x31
-    if (p.width <= p.win || p.height <= p.win) return HV_ERR_UNSUPPORTED;
+    // (an image not larger than the window gets a context of one level: pyramid build, detector and sub-pixel refinement read
+    // through clamped reflection and serve it; the LK entries answer HV_ERR_UNSUPPORTED, launch_klt)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p.device < 0 || p.device >= ndev)
         return HV_ERR_NO_DEVICE;

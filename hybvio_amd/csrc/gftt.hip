@@ -39,6 +39,64 @@ __device__ __forceinline__ bool better(float ra, int ia, float rb, int ib) { ret
 
 typedef float float4v __attribute__((ext_vector_type(4)));
 
+// sqrtf for the response, correctly rounded as the oracle's. With contraction off the compiler's own expansion also scales
+// arguments below 2^-96 and tests the class of the input, about 16 instructions; the detector's arguments are sums of squares
+// and almost never that small. Here 0 and everything from 2^-96 up take the hardware approximation (1 ulp) and the choice
+// between it and its two neighbours by the sign of their residuals x - n * s, each one explicit fma (a single rounding, not a
+// contraction): from 2^-96 up the lowest bit of n * s is at least 2^-142, so a non-zero residual never rounds to zero. For 0
+// the lower neighbour is a NaN and the upper one leaves a residual of -0: both comparisons fail and 0 stays. Arguments in
+// (0, 2^-96) -- the square of a one-ulp difference of two sums near 2^-25 is exactly 2^-96, so they can occur -- take sqrtf.
+__device__ __forceinline__ bool sqrt_arg_tiny(float x) { return __float_as_uint(x) - 1u < 0x0F800000u - 1u; }   // 0 < x < 2^-96
+__device__ __forceinline__ float sqrt_rn_normal(float x)
+{
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float lo = __uint_as_float(__float_as_uint(s) - 1u), hi = __uint_as_float(__float_as_uint(s) + 1u);
+    const float res_lo = __builtin_fmaf(-lo, s, x), res_hi = __builtin_fmaf(-hi, s, x);
+    float r = res_lo <= 0.f ? lo : s;
+    r = res_hi > 0.f ? hi : r;
+    return r;
+}
+__device__ __forceinline__ float sqrt_rn(float x)
+{
+    if (__builtin_expect(sqrt_arg_tiny(x), 0)) return sqrtf(x);
+    return sqrt_rn_normal(x);
+}
+// four at once, straight-line: the rare arguments are redone behind one wave-uniform branch per row step of a strip
+__device__ __forceinline__ float4v sqrt_rn4(float4v x)
+{
+    float4v r;
+#pragma unroll
+    for (int k = 0; k < 4; k++) r[k] = sqrt_rn_normal(x[k]);
+    const bool tiny = sqrt_arg_tiny(x[0]) || sqrt_arg_tiny(x[1]) || sqrt_arg_tiny(x[2]) || sqrt_arg_tiny(x[3]);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(tiny) != 0, 0)) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = sqrt_arg_tiny(x[k]) ? sqrtf(x[k]) : r[k];
+    }
+    return r;
+}
+
+// Arg-max of a block without the raster scan: a thread keeps, per column it owns, the running maximum of the response and its
+// row under strict '>' (the earliest row of equal values), visiting rows in ascending order. Merging columns, lanes and waves
+// with better() (ties to the lower raster index) then yields the first maximum in raster order, and the min_response test is
+// made once on that winner: the accepted set is a threshold on the very value the maximum is taken of, and a NaN passes neither
+// form. The response is compared before its gain of 16 (exact and strictly monotonic), which the winner alone receives.
+struct ColMax {
+    float r = -__builtin_inff();
+    int row = 0;
+    __device__ __forceinline__ void take(float resp, int y) { if (resp > r) { r = resp; row = y; } }
+};
+
+// the block's winner (unscaled response, raster index) -> the key point, or the reference's "no corner" (0, 0, -1e10)
+template <int BS>
+__device__ __forceinline__ void write_keypoint(float *o, float best_r, int best_i, int x0, int y0, float min_response)
+{
+    const float r16 = best_r * 16.0f;                                // CpuCornerResponse::GAIN
+    const bool found = r16 > -1e10f && r16 > min_response;
+    o[0] = found ? (float)(x0 + best_i % BS) : 0.f;
+    o[1] = found ? (float)(y0 + best_i / BS) : 0.f;
+    o[2] = found ? r16 : -1e10f;
+}
+
 // Two register-tiled passes over LDS instead of one LDS round trip per stencil stage:
 //   pass 1  task (tile row ty in [-1, BS], strip of 4 columns): 3 rows x 8 gray values -> the products of
 //           6 columns -> the 3 row sums of 4 columns (12 floats, three 16-byte LDS stores)
@@ -139,9 +197,8 @@ __global__ __launch_bounds__(256) void gftt_block_kernel(GfttArgs a)
     }
     __syncthreads();
 
-    // ---- pass 2: column sums, min eigenvalue, arg-max in raster order ----
-    float best_r = -1e10f;
-    int best_i = 0;
+    // ---- pass 2: column sums, min eigenvalue, arg-max by column (256 is a multiple of NS: a thread keeps its strip) ----
+    ColMax cm[4];
     for (int task = t; task < BS * NS; task += 256) {
         const int y = task / NS, sx = task - y * NS;
         float4v s[3];
@@ -155,12 +212,17 @@ __global__ __launch_bounds__(256) void gftt_block_kernel(GfttArgs a)
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const float aa = s[0][k] * 0.5f, bb = s[1][k], cc = s[2][k] * 0.5f, amc = aa - cc;
-            const float resp = (aa + cc) - sqrtf(amc * amc + bb * bb);
-            const float r16 = resp * 16.0f;                          // CpuCornerResponse::GAIN
-            if (r16 > best_r && r16 > a.min_response) { best_r = r16; best_i = y * BS + 4 * sx + k; }
+            cm[k].take((aa + cc) - sqrt_rn(amc * amc + bb * bb), y);
         }
     }
-    // threads without a candidate keep (-1e10, 0): index 0 / response -1e10 is also the reference's "no corner"
+    float best_r = cm[0].r;
+    int best_i = cm[0].row * BS + 4 * (t % NS);
+#pragma unroll
+    for (int k = 1; k < 4; k++) {
+        const int ik = cm[k].row * BS + 4 * (t % NS) + k;
+        if (better(cm[k].r, ik, best_r, best_i)) { best_r = cm[k].r; best_i = ik; }
+    }
+    // threads without a task keep (-inf, row 0) and lose every merge
     for (int o = 32; o > 0; o >>= 1) {
         const float ro = __shfl_down(best_r, o);
         const int io = __shfl_down(best_i, o);
@@ -170,11 +232,7 @@ __global__ __launch_bounds__(256) void gftt_block_kernel(GfttArgs a)
     __syncthreads();
     if (t == 0) {
         for (int k = 1; k < 4; k++) if (better(red_r[k], red_i[k], best_r, best_i)) { best_r = red_r[k]; best_i = red_i[k]; }
-        const bool found = best_r > -1e10f;
-        float *o = a.kp + ((size_t)img * blocks + bi) * 3;
-        o[0] = found ? (float)(x0 + best_i % BS) : 0.f;
-        o[1] = found ? (float)(y0 + best_i / BS) : 0.f;
-        o[2] = best_r;
+        write_keypoint<BS>(a.kp + ((size_t)img * blocks + bi) * 3, best_r, best_i, x0, y0, a.min_response);
     }
 }
 
@@ -246,7 +304,7 @@ __global__ __launch_bounds__(256) void gftt_box_kernel(GfttArgs a, int hb)
             sm[ch] = s_;
         }
         const float aa = sm[0] * 0.5f, bb = sm[1], cc = sm[2] * 0.5f, amc = aa - cc;
-        const float resp = (aa + cc) - sqrtf(amc * amc + bb * bb);
+        const float resp = (aa + cc) - sqrt_rn(amc * amc + bb * bb);
         const float r16 = resp * 16.0f;                          // CpuCornerResponse::GAIN
         if (r16 > best_r && r16 > a.min_response) { best_r = r16; best_i = i; }
     }
@@ -268,7 +326,7 @@ __global__ __launch_bounds__(256) void gftt_box_kernel(GfttArgs a, int hb)
 }
 
 #ifndef GFTT_MARCH_UNROLL
-#define GFTT_MARCH_UNROLL 2   // 6 removes the window moves but needs 147 VGPRs (3 waves per SIMD): 0.93 ms against 0.84
+#define GFTT_MARCH_UNROLL 2   // 1, 2 and 6 (no window moves left, 198 VGPRs) ran within 1 % of each other: profiles/gftt_march
 #endif
 
 // ---- r02: the same arithmetic without LDS or barriers. A thread owns a strip of 4 columns of one arg-max block and marches
@@ -277,8 +335,17 @@ __global__ __launch_bounds__(256) void gftt_box_kernel(GfttArgs a, int hb)
 // gray row is loaded once per strip (8 bytes, next row requested one step ahead) and every intermediate is computed once
 // (the tiled kernel above re-forms the horizontal pieces three times and moves 72 bytes of LDS per pixel: 105 VALU
 // instructions per pixel measured, and it is VALU-issue bound). The NS = BS / 4 strips of a block are consecutive lanes: the
-// block arg-max is a 3-step lane exchange. Blocks on the first / last image rows evaluate each product row at its mirrored
-// centre with three fresh gray rows (no sliding); columns outside the image mirror inside the strip, as above.
+// block arg-max is a 3-step lane exchange.
+//
+// Every lane runs the same straight-line march, the image borders included:
+//   columns  the 8-byte segment is loaded at the nearest in-bounds column and a per-lane byte selector (identity inside the
+//            image) puts the BORDER_REFLECT_101 columns in place: two byte permutes per row, no per-byte loads;
+//   rows     the window slides over reflected GRAY rows, which is what a product row inside the image reads. The two product
+//            rows outside it (-1 above a first block, h below a last block that ends at h) are mirrors of product rows 1 and
+//            h - 2; the reflected gray rows give those with `up` and `dn` exchanged: vx = k0 mid.d + k1 (up.d + dn.d) is the
+//            same number, vy = dn.s - up.s changes its sign and nothing else, so vx vx and vy vy are the mirror's and the row
+//            sum of vx vy is the mirror's negated (rounding is symmetric): its sign is flipped back in those two steps.
+// Product columns outside the image mirror inside the strip, as above.
 template <int BS>
 __global__ __launch_bounds__(256) void gftt_march_kernel(GfttArgs a)
 {
@@ -295,35 +362,32 @@ __global__ __launch_bounds__(256) void gftt_march_kernel(GfttArgs a)
     const int yb = bi / a.nbx, xb = bi - yb * a.nbx;
     const int x0 = xb * BS, y0 = yb * BS, w = a.w, h = a.h;
     const int slot = a.slots ? a.slots[img] : a.slot0;
-    const uint8_t *src = a.l0_ptr[slot];
     const int stride = a.l0_stride[slot];
     const float k0 = a.k0, k1 = a.k1;
 
-    const int xs = x0 - 2 + 4 * sx;                                   // image column of byte 0 of this strip's 8-byte row segment
-    const bool col_in = xs >= 0 && xs + 8 <= w;
-    int cxr[8];
+    // columns xs .. xs + 7 of a row; xs + 2 .. xs + 5 are the strip's own, so -2 <= xs and xs + 7 <= w + 1: every reflected
+    // column lies in the 8 bytes at xc (launch() sends widths below 8 to the tiled kernel)
+    const int xs = x0 - 2 + 4 * sx;
+    const int xc = min(max(xs, 0), w - 8);
+    uint32_t sel_lo = 0, sel_hi = 0;
 #pragma unroll
-    for (int k = 0; k < 8; k++) cxr[k] = reflect101(xs + k, w);
-    auto load_row = [&](int gr) -> uint2 {                            // gray row gr (inside the image), columns xs .. xs + 7
-        const uint8_t *row = src + (size_t)gr * stride;
+    for (int k = 0; k < 4; k++) {
+        sel_lo |= (uint32_t)(reflect101(xs + k, w) - xc) << (8 * k);
+        sel_hi |= (uint32_t)(reflect101(xs + 4 + k, w) - xc) << (8 * k);
+    }
+    const uint8_t *src = a.l0_ptr[slot] + xc;
+    auto load_row = [&](int gr) -> uint2 {                            // gray row gr (inside the image), bytes xc .. xc + 7
         uint2 v;
-        if (col_in) {
-            __builtin_memcpy(&v, row + xs, 8);
-        } else {
-            v.x = v.y = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                v.x |= (uint32_t)row[cxr[k]] << (8 * k);
-                v.y |= (uint32_t)row[cxr[4 + k]] << (8 * k);
-            }
-        }
+        __builtin_memcpy(&v, src + (size_t)gr * stride, 8);
         return v;
     };
+    auto row_below = [&](int j) { return min(j, 2 * h - 2 - j); };    // reflect101 of a row j >= 0 (h >= 3, j <= h + 1)
     struct HRow { float d[6], s[6]; };
-    auto hrow = [&](uint2 v) -> HRow {
+    auto hrow = [&](uint2 raw) -> HRow {
+        const uint32_t lo = __builtin_amdgcn_perm(raw.y, raw.x, sel_lo), hi = __builtin_amdgcn_perm(raw.y, raw.x, sel_hi);
         float g[8];
 #pragma unroll
-        for (int k = 0; k < 4; k++) { g[k] = (float)((v.x >> (8 * k)) & 0xFFu); g[4 + k] = (float)((v.y >> (8 * k)) & 0xFFu); }
+        for (int k = 0; k < 4; k++) { g[k] = (float)((lo >> (8 * k)) & 0xFFu); g[4 + k] = (float)((hi >> (8 * k)) & 0xFFu); }
         HRow o;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -332,31 +396,9 @@ __global__ __launch_bounds__(256) void gftt_march_kernel(GfttArgs a)
         }
         return o;
     };
-
-    // rows y0 - 2 .. y0 + BS + 1 all exist: consecutive centres, the window slides
-    const bool slide = y0 >= 2 && y0 + BS + 1 <= h - 1;
     const bool mirror_l = sx == 0 && x0 == 0, mirror_r = sx == NS - 1 && x0 + BS == w;
-    HRow up, mid, dn;
-    float4v rsA[3], rsB[3];                                          // row sums of product rows ry - 2, ry - 1
-    float best_r = -1e10f;
-    int best_i = 0;
-    uint2 nxt = make_uint2(0, 0);
-    if (slide) {
-        up = hrow(load_row(y0 - 2));
-        mid = hrow(load_row(y0 - 1));
-        nxt = load_row(y0);
-    }
-#pragma unroll GFTT_MARCH_UNROLL
-    for (int ry = -1; ry <= BS; ++ry) {
-        if (slide) {
-            if (ry > -1) { up = mid; mid = dn; }
-            dn = hrow(nxt);
-            if (ry < BS) nxt = load_row(y0 + ry + 2);                 // the row the next step appends
-        } else {
-            const int cy = reflect101(y0 + ry, h);
-            const uint2 ru = load_row(reflect101(cy - 1, h)), rm = load_row(cy), rd = load_row(reflect101(cy + 1, h));
-            up = hrow(ru); mid = hrow(rm); dn = hrow(rd);
-        }
+    // row sums of the three product images at the product row whose (reflected) gray rows are up, mid, dn
+    auto row_sums = [&](const HRow &up, const HRow &mid, const HRow &dn, float4v (&r)[3]) {
         float c0[6], c1[6], c2[6];
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -366,28 +408,80 @@ __global__ __launch_bounds__(256) void gftt_march_kernel(GfttArgs a)
         }
         if (mirror_l) { c0[0] = c0[2]; c1[0] = c1[2]; c2[0] = c2[2]; }
         if (mirror_r) { c0[5] = c0[3]; c1[5] = c1[3]; c2[5] = c2[3]; }
-        float4v r[3];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             r[0][k] = (c0[k] + c0[k + 1]) + c0[k + 2];
             r[1][k] = (c1[k] + c1[k + 1]) + c1[k + 2];
             r[2][k] = (c2[k] + c2[k + 1]) + c2[k + 2];
         }
-        if (ry >= 1) {
-            const int y = ry - 1;
-            float4v sm[3];
+    };
+    auto flip_sign = [](float4v &v, uint32_t sign) {
 #pragma unroll
-            for (int ch = 0; ch < 3; ch++) sm[ch] = (rsA[ch] + rsB[ch]) + r[ch];
+        for (int k = 0; k < 4; k++) v[k] = __uint_as_float(__float_as_uint(v[k]) ^ sign);
+    };
+    ColMax cm[4];
+    auto respond = [&](const float4v (&rsA)[3], const float4v (&rsB)[3], const float4v (&r)[3], int y) {
+        float4v sm[3], arg, sum;
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float aa = sm[0][k] * 0.5f, bb = sm[1][k], cc = sm[2][k] * 0.5f, amc = aa - cc;
-                const float resp = (aa + cc) - sqrtf(amc * amc + bb * bb);
-                const float r16 = resp * 16.0f;                          // CpuCornerResponse::GAIN
-                if (r16 > best_r && r16 > a.min_response) { best_r = r16; best_i = y * BS + 4 * sx + k; }
-            }
+        for (int ch = 0; ch < 3; ch++) sm[ch] = (rsA[ch] + rsB[ch]) + r[ch];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float aa = sm[0][k] * 0.5f, bb = sm[1][k], cc = sm[2][k] * 0.5f, amc = aa - cc;
+            sum[k] = aa + cc;
+            arg[k] = amc * amc + bb * bb;
         }
+        const float4v root = sqrt_rn4(arg);
+#pragma unroll
+        for (int k = 0; k < 4; k++) cm[k].take(sum[k] - root[k], y);
+    };
+
+    HRow up = hrow(load_row(reflect101(y0 - 2, h))), mid = hrow(load_row(reflect101(y0 - 1, h))), dn;
+    uint2 nxt = load_row(y0);
+    float4v rsA[3], rsB[3], r[3];                                    // row sums of product rows ry - 2, ry - 1, ry
+    // (the steps are written out: with the step in a lambda the same loop comes out 6 % slower, 625 against 588 us)
+    // product rows y0 - 1 and y0: row sums only
+#pragma unroll
+    for (int ry = -1; ry <= 0; ++ry) {
+        dn = hrow(nxt);
+        nxt = load_row(row_below(y0 + ry + 2));                      // the row the next step appends
+        row_sums(up, mid, dn, r);
+        if (ry == -1) flip_sign(r[1], y0 == 0 ? 0x80000000u : 0u);
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) { rsA[ch] = rsB[ch]; rsB[ch] = r[ch]; }
+        up = mid; mid = dn;
+    }
+    // BS - 2 steps, an even count: a loop that holds a convergent operation (the ballot of sqrt_rn4) is unrolled by a
+    // factor only if no remainder is left, and in full otherwise (450 VGPRs)
+#pragma unroll GFTT_MARCH_UNROLL
+    for (int ry = 1; ry < BS - 1; ++ry) {
+        dn = hrow(nxt);
+        nxt = load_row(row_below(y0 + ry + 2));
+        row_sums(up, mid, dn, r);
+        respond(rsA, rsB, r, ry - 1);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) { rsA[ch] = rsB[ch]; rsB[ch] = r[ch]; }
+        up = mid; mid = dn;
+    }
+    {                                                                // product row y0 + BS - 1
+        dn = hrow(nxt);
+        nxt = load_row(row_below(y0 + BS + 1));
+        row_sums(up, mid, dn, r);
+        respond(rsA, rsB, r, BS - 2);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) { rsA[ch] = rsB[ch]; rsB[ch] = r[ch]; }
+        up = mid; mid = dn;
+    }
+    dn = hrow(nxt);                                                  // product row y0 + BS: nothing left to load
+    row_sums(up, mid, dn, r);
+    flip_sign(r[1], y0 + BS == h ? 0x80000000u : 0u);
+    respond(rsA, rsB, r, BS - 1);
+
+    float best_r = cm[0].r;
+    int best_i = cm[0].row * BS + 4 * sx;
+#pragma unroll
+    for (int k = 1; k < 4; k++) {
+        const int ik = cm[k].row * BS + 4 * sx + k;
+        if (better(cm[k].r, ik, best_r, best_i)) { best_r = cm[k].r; best_i = ik; }
     }
     // the NS strips of a block are NS consecutive lanes (NS divides 64): butterfly over them
 #pragma unroll
@@ -396,13 +490,23 @@ __global__ __launch_bounds__(256) void gftt_march_kernel(GfttArgs a)
         const int io = __shfl_xor(best_i, o);
         if (better(ro, io, best_r, best_i)) { best_r = ro; best_i = io; }
     }
-    if (live && sx == 0) {
-        const bool found = best_r > -1e10f;
-        float *o = a.kp + ((size_t)img * blocks + bi) * 3;
-        o[0] = found ? (float)(x0 + best_i % BS) : 0.f;
-        o[1] = found ? (float)(y0 + best_i / BS) : 0.f;
-        o[2] = best_r;
+    if (live && sx == 0) write_keypoint<BS>(a.kp + ((size_t)img * blocks + bi) * 3, best_r, best_i, x0, y0, a.min_response);
+}
+
+// the helper over an array (hv_debug_gftt_sqrt: tests): one argument per thread through sqrt_rn, or four through sqrt_rn4
+__global__ void gftt_sqrt_kernel(const float *x, float *y, long long n, int wide)
+{
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (wide ? 4 : 1);
+    if (!wide) {
+        if (i < n) y[i] = sqrt_rn(x[i]);
+        return;
     }
+    float4v v;                                                       // (whole waves reach the ballot of sqrt_rn4)
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = i + k < n ? x[i + k] : 1.f;
+    v = sqrt_rn4(v);
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (i + k < n) y[i + k] = v[k];
 }
 
 int launch(Ctx *c, int n_images, const int *slots_dev, int slot0, int bs, float min_response, int block_size, float *kp_dev)
@@ -432,7 +536,7 @@ int launch(Ctx *c, int n_images, const int *slots_dev, int slot0, int bs, float 
     // knob gftt_tiled (tests / experiments only): 1 / 0 forces the tiled / the marching kernel.
     const int force_tiled = c->knob.gftt_tiled;
     const bool tiled = force_tiled >= 0 ? force_tiled != 0 : n_images < 128;
-    if (!tiled && a.w >= 8 && a.h >= 3) {
+    if (!tiled && a.w >= 8 && a.h >= 3) {                        // 8-byte row segments, rows reflected once
         const long long threads = (long long)grid * (bs / 4);
         const unsigned wgs = (unsigned)((threads + 255) / 256);
         if (bs == 32)      hipLaunchKernelGGL(gftt_march_kernel<32>, dim3(wgs), dim3(256), 0, c->stream, a);
@@ -469,6 +573,19 @@ int hv_gftt_block_size(const hv_gftt_params *p)
     if (!p) return HV_ERR_INVALID;
     const int target = (int)p->gfttMinDistance;                  // feature_detector.cpp:428-436
     return target >= 32 ? 32 : target >= 16 ? 16 : 8;
+}
+
+// debug export outside the header: y[i] = the detector's square root of x[i], device arrays; wide != 0 takes the four-at-once
+// form of the marching kernel, 0 the scalar form of the other two
+int hv_debug_gftt_sqrt(hv_ctx *ctx, const float *x_dev, float *y_dev, long long n, int wide)
+{
+    if (!ctx || n < 0 || (n > 0 && (!x_dev || !y_dev))) return HV_ERR_INVALID;
+    Ctx *c = hv::ctx_of(ctx);
+    if (n == 0) return HV_OK;
+    const long long threads = wide ? (n + 3) / 4 : n;
+    hipLaunchKernelGGL(hv::gftt_sqrt_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream, x_dev, y_dev, n, wide);
+    HV_HIP(c, hipGetLastError());
+    return HV_OK;
 }
 
 int hv_gftt_keypoint_count(hv_ctx *ctx, const hv_gftt_params *p)

@@ -758,6 +758,8 @@ int launch_klt(Ctx *c, int n_pairs, const int *prev_slots_dev, const int *next_s
                uint8_t *status, float *err, int use_initial_flow, int max_iter, const int *pts_in_pair_dev)
 {
     (void)n_pairs;
+    // reflect101 is exact, and the tile staging laid out, for levels larger than the window only
+    if (c->L.w[0] <= WIN || c->L.h[0] <= WIN) return HV_ERR_UNSUPPORTED;
     if (n_points <= 0) return HV_OK;
     KltArgs a{};
     a.L = c->L;

@@ -66,6 +66,9 @@ int hv_debug_set_knob(hv_ctx *ctx, const char *name, int value);
 int hv_debug_get_knob(hv_ctx *ctx, const char *name, int *value);
 
 /* ---- context ---------------------------------------------------------------------------- */
+/* Any positive image size. An image not larger than the LK window in either direction gets a pyramid of one level that the
+ * pyramid build, the detector and the sub-pixel refinement serve; every LK entry (hv_klt_track, hv_optical_flow_compute,
+ * hv_klt_track_batch_dev, hv_klt_track_batch_ragged_dev and the fused entries that track) returns HV_ERR_UNSUPPORTED on it. */
 int hv_create(const hv_params *params, hv_ctx **out);
 void hv_destroy(hv_ctx *ctx);
 const char *hv_last_error(hv_ctx *ctx);               /* text of the last HV_ERR_HIP           */
