@@ -30,7 +30,7 @@ f64p = C.POINTER(C.c_double)
 
 HV_MAX_LEVELS = 6
 (K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI,
- K_SUBPIX, K_RANSAC5, K_STEREO_GATE) = range(15)
+ K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL) = range(16)
 RANSAC5_MAX_ITERS = 75
 # RansacResult::Type as reported by hv_hybrid_ransac_lk_batch_dev
 R5_TYPE_SKIPPED, R5_TYPE_R2, R5_TYPE_R5 = 0, 1, 3
@@ -40,6 +40,7 @@ SUBPIX_MAX_WIN = 16
 ST_TRACKED, ST_NEW, ST_FAILED_FLOW, ST_RANSAC_OUTLIER, ST_FLOW_OUT_OF_RANGE = 0, 1, 2, 3, 4
 ST_OUT_OF_RANGE, ST_FAILED_EPIPOLAR_CHECK, ST_CULLED, ST_BLACKLISTED = 5, 6, 7, 8
 DETECTION_FILTER_MAX_POINTS = 1024
+DETECT_TAIL_MAX_KEYPOINTS, DETECT_TAIL_MAX_CORNERS, DETECT_TAIL_MAX_PREV, DETECT_TAIL_MAX_TRACKS = 16384, 32768, 4096, 4096
 
 
 class Params(C.Structure):
@@ -172,6 +173,12 @@ PROTOTYPES = {
     "hv_gftt_detect": (C.c_int, [C.c_void_p, C.POINTER(GfttParams), C.c_int, f32p, C.c_int, C.c_int, f32p, C.c_int,
                                  C.POINTER(C.c_int)]),
     "hv_gftt_keypoints_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(GfttParams), C.c_int, C.c_void_p, C.c_void_p]),
+    "hv_apply_min_distance_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_int, C.c_void_p]),
+    "hv_gftt_corners_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(GfttParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hv_gftt_detect_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(GfttParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hv_apply_min_distance": (None, [f32p, C.POINTER(C.c_int), f32p, C.c_int, C.c_int, C.c_int]),
     "hv_subpix_default_params": (None, [C.POINTER(SubpixParams)]),
     "hv_corner_subpix": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_int, f32p, i32p]),
@@ -514,6 +521,32 @@ class Context:
         gp = params if params is not None else gftt_default_params()
         self._chk(lib().hv_gftt_keypoints_batch_dev(self._h, C.byref(gp), n_images, C.c_void_p(slots_dev),
                                                     C.c_void_p(kp_dev)), "hv_gftt_keypoints_batch_dev")
+
+    def apply_min_distance_batch_dev(self, n_sets, max_corners, n_corners_dev, corners_dev, max_prev, n_prev_dev, prev_dev, radius_dev,
+                                     max_tracks, n_out_dev):
+        """hv_apply_min_distance_batch_dev: corners_dev [n_sets][max_corners][2] filtered in place, counts in n_out_dev."""
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_apply_min_distance_batch_dev(self._h, n_sets, max_corners, p(n_corners_dev), p(corners_dev), max_prev,
+                                                        p(n_prev_dev), p(prev_dev), p(radius_dev), int(max_tracks), p(n_out_dev)),
+                  "hv_apply_min_distance_batch_dev")
+
+    def gftt_corners_batch_dev(self, n_images, kp_dev, max_prev, n_prev_dev, prev_dev, mask_radius_dev, max_corners, corners_dev,
+                               n_out_dev, params: "GfttParams" = None):
+        """hv_gftt_corners_batch_dev: the tail of detect() on the key points of gftt_keypoints_batch_dev."""
+        gp = params if params is not None else gftt_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_gftt_corners_batch_dev(self._h, C.byref(gp), n_images, p(kp_dev), max_prev, p(n_prev_dev), p(prev_dev),
+                                                  p(mask_radius_dev), max_corners, p(corners_dev), p(n_out_dev)),
+                  "hv_gftt_corners_batch_dev")
+
+    def gftt_detect_batch_dev(self, n_images, slots_dev, kp_dev, max_prev, n_prev_dev, prev_dev, mask_radius_dev, max_corners,
+                              corners_dev, n_out_dev, params: "GfttParams" = None):
+        """hv_gftt_detect_batch_dev: gftt_keypoints_batch_dev + gftt_corners_batch_dev on the context stream."""
+        gp = params if params is not None else gftt_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_gftt_detect_batch_dev(self._h, C.byref(gp), n_images, p(slots_dev), p(kp_dev), max_prev, p(n_prev_dev),
+                                                 p(prev_dev), p(mask_radius_dev), max_corners, p(corners_dev), p(n_out_dev)),
+                  "hv_gftt_detect_batch_dev")
 
     def gftt_sqrt_dev(self, x_dev: int, y_dev: int, n: int, wide: bool = False):
         """y[i] = the detector's correctly rounded square root of x[i], binary32 device arrays (hv_debug_gftt_sqrt: a debug export

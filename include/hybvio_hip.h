@@ -426,6 +426,46 @@ int hv_gftt_keypoints_batch_dev(hv_ctx *ctx, const hv_gftt_params *p, int n_imag
 void hv_apply_min_distance(float *corners_xy, int *n_inout, const float *prev_xy, int n_prev, int r,
                            int max_tracks);
 
+/* ---- device tail of detect(): stable sort, zero prefix, min-distance filter and track cap (added within ABI 4) ----------
+ * The batched, asynchronous forms of the host tail above: n_sets independent sets, one workgroup each, on the context stream
+ * with no allocation or synchronisation inside (capturable in a HIP graph). Bit-identical to hv_gftt_detect /
+ * hv_apply_min_distance: the same points in the same order with the same count (the distance test is the reference's binary32
+ * `dx*dx + dy*dy < (float)(r*r)`, two rounded products and one rounded sum, never contracted).
+ * Layouts: set s has n_*_dev[s] entries (clamped to [0, max_*]) at s * max_* of its array; the radius is per set
+ * (TrackerImplementation::maskRadius depends on the tracker's adaptive maskScale, tracker.cpp:569-576).
+ * Checks made before the context is looked at: HV_ERR_INVALID for NULL required arrays or parameters, negative sizes or
+ * max_tracks < 1; HV_ERR_UNSUPPORTED for n_sets > 65535, max_prev > HV_DETECT_TAIL_MAX_PREV, max_tracks >
+ * HV_DETECT_TAIL_MAX_TRACKS or max_corners > HV_DETECT_TAIL_MAX_CORNERS; with the context,
+ * HV_ERR_UNSUPPORTED for more than HV_DETECT_TAIL_MAX_KEYPOINTS key points per image. */
+#define HV_DETECT_TAIL_MAX_KEYPOINTS 16384   /* per image: 1280 x 720 at block edge 8 has 14 400 */
+#define HV_DETECT_TAIL_MAX_CORNERS   32768   /* max_corners of every entry: 2 * HV_DETECT_TAIL_MAX_KEYPOINTS */
+#define HV_DETECT_TAIL_MAX_PREV      4096    /* live tracks per set */
+#define HV_DETECT_TAIL_MAX_TRACKS    4096    /* maxTracks / max_tracks */
+/* FeatureDetector::applyMinDistance (feature_detector_legacy.cpp:177-213) on arbitrary lists, the second branch of
+ * findKeypoints (image.cpp:77: pending corners against the current mask): corners_dev [n_sets][max_corners][2] is filtered in
+ * place against prev_dev [n_sets][max_prev][2] (NULL, with n_prev_dev, allowed when max_prev == 0) and the corners kept so far,
+ * stopped at max_tracks; n_out_dev[s] = the kept count, entries at and beyond it are unspecified. radius_dev[s] <= 0: the first
+ * min(n, max_tracks) corners are kept. */
+int hv_apply_min_distance_batch_dev(hv_ctx *ctx, int n_sets, int max_corners, const int *n_corners_dev, float *corners_dev,
+                                    int max_prev, const int *n_prev_dev, const float *prev_dev, const int *radius_dev,
+                                    int max_tracks, int *n_out_dev);
+/* The tail of FeatureDetectorImplementation::detect (feature_detector.cpp:624-633) on the key points of
+ * hv_gftt_keypoints_batch_dev, kp_dev [n_images][hv_gftt_keypoint_count()][3]: stable sort by descending response (equal
+ * responses, -0.0 and +0.0 among them, keep block raster order), one (0, 0) point in front per key point (:629-631),
+ * applyMinDistance with mask_radius_dev[s] against the image's live tracks, stopped at p->maxTracks. corners_dev
+ * [n_images][max_corners][2], n_out_dev[s] = the corner count. Capacity: max_corners >= min(maxTracks, 2 nk) is required
+ * (HV_ERR_INVALID below it), which holds every result of a radius > 0. A set with radius <= 0 has all 2 nk points as its
+ * result, uncapped, exactly as hv_gftt_detect returns them: where max_corners < 2 nk such a set writes no corner and reports
+ * n_out_dev[s] = -1 (the radii are device data, so the host cannot refuse it). */
+int hv_gftt_corners_batch_dev(hv_ctx *ctx, const hv_gftt_params *p, int n_images, const float *kp_dev, int max_prev,
+                              const int *n_prev_dev, const float *prev_dev, const int *mask_radius_dev, int max_corners,
+                              float *corners_dev, int *n_out_dev);
+/* hv_gftt_keypoints_batch_dev followed by hv_gftt_corners_batch_dev on the context stream: FeatureDetector::detect of
+ * n_images pyramid slots (slots_dev [n_images]) with no host step. kp_dev [n_images][nk][3] is workspace and by-product. */
+int hv_gftt_detect_batch_dev(hv_ctx *ctx, const hv_gftt_params *p, int n_images, const int *slots_dev, float *kp_dev,
+                             int max_prev, const int *n_prev_dev, const float *prev_dev, const int *mask_radius_dev,
+                             int max_corners, float *corners_dev, int *n_out_dev);
+
 /* ---- sub-pixel corner refinement (added within ABI 4) ----------------------------------------
  * Replaces tracker::SubPixelAdjuster::adjust (src/tracker/subpixel_adjuster.cpp:18-42): cv::cornerSubPix(image, corners,
  * Size(win, win), Size(-1, -1), TermCriteria(COUNT | EPS, maxIter, epsilon)) on the level-0 image of a pyramid slot, then
@@ -637,7 +677,8 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_SUBPIX = 12 /* added within ABI 4: hv_corner_subpix* */,
        HV_K_RANSAC5 = 13 /* added within ABI 4: hv_ransac5*, hv_hybrid_ransac_lk_batch_dev */,
        HV_K_STEREO_GATE = 14 /* added within ABI 4: hv_flow_status_batch_dev, hv_track_gate*, hv_detection_filter* */,
-       HV_K_COUNT = 15 };
+       HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
+       HV_K_COUNT = 16 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
 /* Synchronizes, then returns accumulated device milliseconds and launch count of a kernel class. */
