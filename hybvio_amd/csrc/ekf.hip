@@ -23,10 +23,14 @@
 //     +-1 matrix visAugH into a rank-14 correction (4 MFMA k-steps per 16 x 16 tile) of the shifted
 //     matrix A P A' + Q, which is a gather of P and never materialised; mirrored tile pairs meet
 //     through an in-wave LDS transpose for the fused (P+P')/2, and the result goes to the second of
-//     two ping-pong buffers: one read and one write of P per augmentation.
+//     two ping-pong buffers: one read and one write of P per augmentation. The 14 rows and columns
+//     visAugH touches are then rewritten from the Joseph form itself (W = T P1 times the rows of T,
+//     formed first): the expansion cancels the slot's 1e8 prior against itself there and loses seven
+//     to eight digits of entries of size 1e-6, which a whole-matrix norm never sees.
 #include <limits.h>
 #include <math.h>
 
+#include <algorithm>
 #include <utility>
 
 #include <stdlib.h>
@@ -1768,6 +1772,16 @@ __device__ __forceinline__ int aug_src(int i, int dropped, int n)   // visAugA[d
 }
 __device__ __forceinline__ int augh_plus(int i) { return i < 3 ? POS + i : ORI + (i - 3); }   // visAugH (ekf.cpp:267-278)
 __device__ __forceinline__ int augh_minus(int i) { return CAM + i; }
+// the 14 state indices visAugH touches (POS, ORI, trail slot 0) in the order [plus(0..6); minus(0..6)], and the inverse (-1: none)
+constexpr int AUGJ = 2 * POSE;
+__device__ __forceinline__ int augj_index(int jj) { return jj < POSE ? augh_plus(jj) : augh_minus(jj - POSE); }
+__device__ __forceinline__ int augj_slot(int i)
+{
+    if (i < POS + 3) return i - POS;
+    if (i >= ORI && i < ORI + 4) return 3 + (i - ORI);
+    if (i >= CAM && i < CAM + POSE) return POSE + (i - CAM);
+    return -1;
+}
 
 constexpr int AUG_THREADS = 1024;
 
@@ -1931,6 +1945,42 @@ __global__ __launch_bounds__(AUG_THREADS) void ekf_augment_kernel(AugmentArgs a)
         }
     }
     __syncthreads();
+    // 5. The 14 columns visAugH touches (POS, ORI, trail slot 0) and, by symmetry, the same 14 rows, in the Joseph form itself.
+    // There step 4's expansion subtracts numbers the size of the slot's prior (1e8) to leave a variance of 1e-6: exact algebra,
+    // seven to eight digits lost in every entry of those rows on its own scale (profiles/ekf_accuracy). With W = P1 - K HP = T P1 and
+    // the rows of T = I - K H formed FIRST on their support (those same 14 columns), 1 + K(cam, .) is a small number with a small
+    // absolute error, and P(:, j) = W T(j, :)' + rd K K(j, :)' carries W's cancellation error times that small number only.
+    // Wc (n x 14) and T14 borrow the transpose scratch, which step 4 is done with.
+    {
+        double *Wc = scr_all, *T14 = Wc + AUGJ * n;
+        for (int e = t; e < AUGJ * n; e += AUG_THREADS) {
+            const int cc = e / n, i = e % n, jc = augj_index(cc);
+            double w = p1(i, jc);
+            for (int k = 0; k < POSE; k++) w -= K[k * n + i] * HP[k * n + jc];
+            Wc[e] = w;
+        }
+        if (t < AUGJ * AUGJ) {
+            const int jj = t / AUGJ, cc = t % AUGJ;
+            const double kv = K[(cc < POSE ? cc : cc - POSE) * n + augj_index(jj)];      // H(k, J[cc]) = +1 (k = cc) / -1 (k = cc - 7)
+            T14[t] = (jj == cc ? 1.0 : 0.0) + (cc < POSE ? -kv : kv);
+        }
+        __syncthreads();
+        auto column = [&](int i, int jj) -> double {                     // (W T' + rd K K')(i, J[jj])
+            const int j = augj_index(jj);
+            double s = 0.0, kk = 0.0;
+            for (int cc = 0; cc < AUGJ; cc++) s += Wc[cc * n + i] * T14[jj * AUGJ + cc];
+            for (int k = 0; k < POSE; k++) kk += K[k * n + i] * K[k * n + j];
+            return s + a.rd * kk;
+        };
+        for (int e = t; e < AUGJ * n; e += AUG_THREADS) {
+            const int jj = e / n, i = e % n, j = augj_index(jj), ii = augj_slot(i);
+            if (ii > jj) continue;                                       // inside the 14 x 14 block one thread writes both mirrors
+            double v = column(i, jj);
+            if (ii >= 0) v = 0.5 * (v + column(j, ii));
+            Pout[(size_t)j * n + i] = v;
+            Pout[(size_t)i * n + j] = v;
+        }
+    }
     const int nq = 1 + (n - a.map_dim - CAM) / POSE;
     if (t < nq) normalize4(m + (t == 0 ? ORI : CAM + POSE * (t - 1) + 3));
 }
@@ -2645,7 +2695,8 @@ static size_t augment_fill(const Ekf *e, hv::AugmentArgs &a)
     a.q_pos = e->par.noiseInitialPosTrail * e->par.noiseInitialPosTrail * e->noise_scale;
     a.q_ori = e->par.noiseInitialOriTrail * e->par.noiseInitialOriTrail * e->noise_scale;
     a.rd = e->par.augmentR * e->noise_scale;
-    return sizeof(double) * (3 * hv::POSE * e->n + 2 * hv::POSE * hv::POSE + hv::POSE + 1 + (hv::AUG_THREADS / 64) * 16 * 17);
+    const int scratch = std::max((hv::AUG_THREADS / 64) * 16 * 17, hv::AUGJ * e->n + hv::AUGJ * hv::AUGJ);   // transposes, then Wc + T14
+    return sizeof(double) * (3 * hv::POSE * e->n + 2 * hv::POSE * hv::POSE + hv::POSE + 1 + scratch);
 }
 
 int hv_ekf_augment(hv_ekf *h, const int *discarded, const unsigned char *active)

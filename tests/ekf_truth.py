@@ -1,0 +1,362 @@
+"""Extended-precision restatement of the EKF covariance algebra (src/odometry/ekf.cpp as oracle/ekf_oracle.c documents it): the
+visual update (ekf.cpp:760-844), the pose augmentation with its Joseph form (ekf.cpp:35-50, 848-885), the undo shift (888-903)
+and the covariance half of predict (504-508), in np.longdouble (x87 extended, eps 1.08e-19), plus the scale-aware error
+metrics the accuracy tests use and a generator of covariances as a running filter holds them.
+
+Test infrastructure only (not collected, imported by the tests; nothing under hybvio_amd/ uses it). Plain numpy: no LAPACK
+exists in extended precision, so the Cholesky factor and the triangular solves are loops over rows, and every product is
+numpy's own longdouble matmul. The expressions are the reference's, in its order (HP, S, S^-1 HP, P -= K HP; T = I - K H
+formed first, then T P T' + K R K'): in extended precision that is accurate to about 1e-19 of every entry's own scale, which
+the restructured forms of the same algebra are not (P1 - K HP subtracts 1e8 from 1e8 to leave 1e-6).
+
+The numbers both implementations take as inputs stay binary64: the state, H, the residual, and the products of parameters
+(augmentR * noiseScale^2, the trail priors), which the oracle and the device both round to binary64 before use.
+"""
+from __future__ import annotations
+
+import os
+import re
+
+import numpy as np
+
+LD = np.longdouble
+assert np.finfo(LD).eps < 2e-19, (
+    "tests/ekf_truth.py needs an extended-precision np.longdouble (eps < 2e-19, x87 80-bit or wider); on this host it has "
+    f"eps = {np.finfo(LD).eps}, no wider than binary64, so it cannot serve as the truth for binary64 kernels")
+
+EPS64 = float(np.finfo(np.float64).eps)
+POS, VEL, ORI, BGA, BAA, BAT, SFT, CAM, POSE = 0, 3, 6, 10, 13, 16, 19, 20, 7
+INLIER, CHI2 = 0, 3
+HANOI = [19, 16, 17, 16, 18, 16, 17, 16]
+REGIMES = ("a", "b", "c", "d", "e")
+
+
+def chi2inv95():
+    """The gate's thresholds, read from the table the oracle compiles in (oracle/chi2inv95.h: numbers only)."""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "chi2inv95.h")
+    body = open(path).read().split("HV_CHI2INV95_VALUES", 1)[1].split("static", 1)[0]
+    return np.array([float(x) for x in re.findall(r"[0-9]+(?:\.[0-9]+)?", body)])
+
+
+# ---- helpers ----
+
+def chol(S):
+    """Lower Cholesky factor of the lower triangle of S, column by column."""
+    S = np.asarray(S, LD)
+    n = S.shape[0]
+    L = np.zeros((n, n), LD)
+    for c in range(n):
+        d = S[c, c] - L[c, :c] @ L[c, :c]
+        if not d > 0:
+            raise np.linalg.LinAlgError(f"pivot {c} is {d}")
+        L[c, c] = np.sqrt(d)
+        L[c + 1:, c] = (S[c + 1:, c] - L[c + 1:, :c] @ L[c, :c]) / L[c, c]
+    return L
+
+
+def forward_subst(L, B):
+    X = np.array(B, LD)
+    for i in range(L.shape[0]):
+        X[i] = (X[i] - L[i, :i] @ X[:i]) / L[i, i]
+    return X
+
+
+def back_subst(U, B):
+    X = np.array(B, LD)
+    for i in range(U.shape[0] - 1, -1, -1):
+        X[i] = (X[i] - U[i, i + 1:] @ X[i + 1:]) / U[i, i]
+    return X
+
+
+def spd_solve(L, B):
+    return back_subst(L.T, forward_subst(L, B))
+
+
+def _ratio(num, den):
+    """num / den entrywise; 0 / 0 counts as no error, x / 0 as an infinite one."""
+    num, den = np.asarray(num, LD), np.asarray(den, LD)
+    out = np.where(num == 0, LD(0), LD(np.inf))
+    np.divide(num, den, out=out, where=den > 0)
+    return out
+
+
+def scaled_err(P, T) -> float:
+    """max_ij |P_ij - T_ij| / sqrt(T_ii T_jj): every entry on the scale of its own row and column."""
+    T = np.asarray(T, LD)
+    d = np.sqrt(np.diag(T))
+    return float(_ratio(np.abs(np.asarray(P, LD) - T), np.outer(d, d)).max())
+
+
+def scaled_err_m(m, Tm, T) -> float:
+    """max_i |m_i - Tm_i| / sqrt(T_ii): the mean's error in standard deviations."""
+    return float(_ratio(np.abs(np.asarray(m, LD) - np.asarray(Tm, LD)), np.sqrt(np.diag(np.asarray(T, LD)))).max())
+
+
+def frob_err(P, T) -> float:
+    """The whole-matrix figure the parity tests use."""
+    T = np.asarray(T, LD)
+    return float(np.sqrt(((np.asarray(P, LD) - T) ** 2).sum() / (T ** 2).sum()))
+
+
+def corr_min_eig(P) -> float:
+    """Smallest eigenvalue of the correlation matrix sym(P) / sqrt(d d'), in binary64."""
+    P = np.asarray(P, np.float64)
+    P = 0.5 * (P + P.T)
+    d = np.sqrt(np.diag(P))
+    return float(np.linalg.eigvalsh(P / np.outer(d, d))[0])
+
+
+def _normalize_quaternions(m, trail):
+    for o in [ORI] + [CAM + POSE * c + 3 for c in range(trail)]:
+        nn = np.sqrt(m[o:o + 4] @ m[o:o + 4])
+        if nn > 0:
+            m[o:o + 4] /= nn
+
+
+# ---- operations ----
+
+def visual_update(m, P, H, v, rd, trail, ns=1.0):
+    """updateVisualTrack + the gate's statistic on the same inputs. H is nr x l (the leading l columns of the state), v the
+    residual y - f, rd the diagonal of R (r^2 * noiseScale^2). Returns m, P after the update and chi2 = ns v' S^-1 v."""
+    m, P, H, v = np.array(m, LD), np.array(P, LD), np.asarray(H, LD), np.asarray(v, LD)
+    nr, l = H.shape
+    HP = H @ P[:l, :]
+    S = HP[:, :l] @ H.T
+    S[np.diag_indices(nr)] += LD(rd)
+    L = chol(S)
+    X = spd_solve(L, HP)                              # S^-1 HP = K'
+    chi2 = LD(ns) * (v @ spd_solve(L, v))
+    m = m + X.T @ v
+    P = P - X.T @ HP
+    _normalize_quaternions(m, trail)
+    return m, P, float(chi2)
+
+
+def aug_src(n, dropped):
+    """visAugA[dropped] as an index map: row i of A m takes m[src[i]], -1 a zero row."""
+    src = np.full(n, -1)
+    src[:CAM] = np.arange(CAM)
+    i = np.arange(CAM, CAM + dropped * POSE)
+    src[i + POSE] = i
+    i = np.arange(CAM + (dropped + 1) * POSE, n)
+    src[i] = i
+    return src
+
+
+def undo_src(n, map_dim):
+    """visUnaugmentA: the trail moves one slot towards the front, the last slot and its covariance become zero."""
+    trail_end = n - map_dim
+    src = np.full(n, -1)
+    src[:CAM] = np.arange(CAM)
+    i = np.arange(CAM, trail_end - POSE)
+    src[i] = i + POSE
+    i = np.arange(trail_end, n)
+    src[i] = i
+    return src
+
+
+def shift(m, P, src):
+    """m = A m, P = A P A' for an index map: exact in any precision."""
+    ok = src >= 0
+    s = np.where(ok, src, 0)
+    return np.where(ok, m[s], 0), np.where(np.outer(ok, ok), P[np.ix_(s, s)], 0)
+
+
+def aug_H(n):
+    H = np.zeros((POSE, n), LD)
+    for i in range(3):
+        H[i, POS + i], H[i, CAM + i] = 1, -1
+    for i in range(4):
+        H[3 + i, ORI + i], H[3 + i, CAM + 3 + i] = 1, -1
+    return H
+
+
+def augment(m, P, k, params, dense=False):
+    """updateVisualPoseAugmentation(k): shift, + visAugQ, the update with visAugH in Joseph form, symmetrise, normalise.
+    T = I - K H is the identity outside the 14 columns visAugH touches, so T P1 T' is evaluated as the dense products with
+    their structurally zero terms left out (the diagonal of T times P1, plus those 14 columns' terms): the same sums, a
+    hundredth of the time. dense=True runs the two full n^3 products instead (test_ekf_truth.py compares the two)."""
+    m, P = np.asarray(m, LD), np.asarray(P, LD)
+    n, trail = len(m), params.cameraTrailLength
+    ns = params.noiseScale * params.noiseScale                      # binary64 products, as both implementations form them
+    q_pos, q_ori, rd = params.noiseInitialPosTrail ** 2 * ns, params.noiseInitialOriTrail ** 2 * ns, params.augmentR * ns
+    m1, P1 = shift(m, P, aug_src(n, trail - 1 if k == -1 else k))
+    P1 = P1.copy()
+    for i in range(POSE):
+        P1[CAM + i, CAM + i] += LD(q_pos if i < 3 else q_ori)
+    H = aug_H(n)
+    HP = H @ P1
+    S = HP @ H.T
+    S[np.diag_indices(POSE)] += LD(rd)
+    K = spd_solve(chol(S), HP).T
+    m1 = m1 + K @ (-(H @ m1))
+    T = -(K @ H)
+    T[np.diag_indices(n)] += 1                                      # formed first: 1 + K(cam, .) is small, with a small error
+    if dense:
+        TPT = (T @ P1) @ T.T
+    else:
+        cols = np.flatnonzero(np.abs(H).sum(0))
+        d = np.diag(T).copy()
+        Toff = T[:, cols].copy()
+        Toff[cols, np.arange(len(cols))] = 0
+        TP = d[:, None] * P1 + Toff @ P1[cols, :]
+        TPT = TP * d[None, :] + TP[:, cols] @ Toff.T
+    P1 = TPT + LD(rd) * (K @ K.T)
+    P1 = (P1 + P1.T) / 2
+    _normalize_quaternions(m1, trail)
+    return m1, P1
+
+
+def undo_augment(m, P, params):
+    m, P = np.asarray(m, LD), np.asarray(P, LD)
+    return shift(m, P, undo_src(len(m), 3 * params.hybridMapSize))
+
+
+def predict_cov(P, F20, Qd):
+    """One sample of predict's covariance: F P F' + Qd with F = blockdiag(F20, I). F20 is the oracle's dydx and Qd = L Q L', the
+    covariance the oracle's own predict leaves when started from P = 0 with the same mean and inputs."""
+    P, F, Qd = np.array(P, LD), np.asarray(F20, LD), np.asarray(Qd, LD)
+    P[:CAM, :] = F @ P[:CAM, :]
+    P[:, :CAM] = P[:, :CAM] @ F.T
+    P[:CAM, :CAM] += Qd
+    return P
+
+
+def oracle_predict_terms(oracle, params, m, t0, t1, gyro, acc):
+    """(m after, F20, Qd) of one oracle predict from mean m: run on a filter whose covariance is zero."""
+    o = oracle.Ekf(params)
+    o.set_state(m)
+    o.set_cov(np.zeros((o.n, o.n)))
+    o.set_first_sample_time(t0)
+    o.predict(t1, gyro, acc)
+    return o.m.copy(), o.dydx.copy(), o.P[:CAM, :CAM].copy()
+
+
+# ---- covariances as a running filter holds them ----
+
+def structured_H(rng, nr, l, trail, n_poses=None, map_cols=None):
+    """A visual-track Jacobian's support with random entries: 4 rows per chosen pose in that pose's 7 columns, a rank-3 coupling
+    (the triangulated point) across all chosen poses, and the POS / ORI / SFT columns. Columns 3-5 and 10-18 (velocity, biases)
+    stay exactly zero, as real Jacobians do (test_jacobian_structure.py). map_cols: 3 more columns coupled through the point."""
+    avail = min(trail, (l - CAM) // POSE)
+    n_poses = min(avail, n_poses or (nr + 3) // 4)
+    chosen = np.sort(rng.choice(avail, size=n_poses, replace=False))
+    H = np.zeros((nr, l))
+    cols = np.concatenate([np.arange(CAM + POSE * c, CAM + POSE * c + POSE) for c in chosen])
+    for i in range(nr):
+        c = chosen[(i // 4) % n_poses]
+        H[i, CAM + POSE * c: CAM + POSE * c + POSE] = rng.normal(size=POSE)
+    U = rng.normal(size=(nr, 3))
+    H[:, cols] += U @ rng.normal(size=(3, len(cols))) / np.sqrt(3.0)
+    for c0, w in ((POS, 3), (ORI, 4), (SFT, 1)):
+        H[:, c0:c0 + w] = rng.normal(size=(nr, w))
+    if map_cols is not None:
+        H[:, map_cols:map_cols + 3] = U @ rng.normal(size=(3, 3))
+    return H
+
+
+def regime_frames(trail):
+    """Frames whose pre-augmentation state is a snapshot of each regime (the issue's frame numbers at trail 20, the same
+    points of the trail's life at other lengths)."""
+    return {"a": [0, 1, 2], "b": [trail // 2], "c": [trail - 1, trail, trail + 1], "d": [trail + 4], "e": [2 * trail, 2 * trail + 1]}
+
+
+def discard_index(frame, trail):
+    """-1 while the trail fills, then the Hanoi pattern (counted from the trail's end, so it serves every length)."""
+    return trail - 1 - (19 - HANOI[frame % 8]) if frame >= trail else -1
+
+
+def closed_loop_inputs(rng, acc0):
+    return rng.normal(0, 0.05, 3), acc0 + rng.normal(0, 0.05, 3)
+
+
+def realistic_filters(oracle, rng, trail=20, hybrid_map=0, frames=None):
+    """The oracle's closed loop from the constructor state: initialize_orientation, then per frame 10 predicts, from frame
+    trail + 4 on up to 6 gated visual updates with structured H and a symmetrisation, and one augmentation. Returns
+    (params, {regime: [(frame, m, P), ...]}): the state of each regime's frames after the predicts, before the updates and the
+    augmentation of that frame. hybrid_map > 0: map points inserted at scale 1e-2 and tied in by the tracks' map columns."""
+    params = oracle.ekf_default_params(cameraTrailLength=trail, hybridMapSize=hybrid_map)
+    o = oracle.Ekf(params)
+    n = o.n
+    acc0 = np.array([0.2, -0.1, 9.8])
+    o.initialize_orientation(acc0)
+    o.set_first_sample_time(0.0)
+    if hybrid_map:
+        P = o.P.copy()
+        for j in range(hybrid_map):
+            P[n - 3 * hybrid_map + 3 * j + np.arange(3), n - 3 * hybrid_map + 3 * j + np.arange(3)] = 1e-2 * (1 + rng.random(3))
+        o.set_cov(P)
+    want = regime_frames(trail)
+    last = max(max(v) for v in want.values()) if frames is None else frames - 1
+    snaps = {r: [] for r in REGIMES}
+    t = 0.0
+    for frame in range(last + 1):
+        for _ in range(10):
+            t += 0.005
+            o.predict(t, *closed_loop_inputs(rng, acc0))
+        for r in REGIMES:
+            if frame in want[r]:
+                snaps[r].append((frame, o.m.copy(), o.P.copy()))
+        if frame >= trail + 4:
+            for _ in range(6):
+                poses = int(rng.integers(4, 11))
+                l = CAM + POSE * int(rng.integers(min(poses, trail), trail + 1))
+                mc = None
+                if hybrid_map and rng.random() < 0.5:
+                    mc, l = n - 3 * hybrid_map + 3 * int(rng.integers(hybrid_map)), n
+                H = structured_H(rng, 4 * poses, l, trail, map_cols=mc)
+                v = rng.normal(size=4 * poses) * (0.5 if rng.random() < 0.25 else 0.02)
+                if o.visual_track_outlier_check(H, np.zeros(len(v)), v, 0.05)[0] == INLIER:
+                    o.update_visual_track(H, np.zeros(len(v)), v, 0.05)
+            o.maintain_psd()
+        o.update_visual_pose_augmentation(discard_index(frame, trail))
+    return params, snaps
+
+
+# ---- the cases the truth-pinning test and the GPU accuracy test share ----
+
+R_VISUAL = 0.05                                                       # visualR of the loop above: rd = r^2 * noiseScale^2
+UPDATE_SHAPES = {20: [(16, 76), (40, 160), (84, 160)], 5: [(16, 55)]}  # rows x columns of H (one-, three-row-tile, workspace builds)
+UPDATE_REGIMES = ("c", "d", "e")                                      # the trail must be filled: a track needs real poses
+
+
+def filled(snapshots, trail):
+    return [s for s in snapshots if s[0] >= trail]
+
+
+def update_inputs(regime, trail, nr, l, count):
+    """Per filter a structured H and an inlier-sized residual, seeded by the case."""
+    rng = np.random.default_rng([ord(regime), trail, nr, l])
+    return [(structured_H(rng, nr, l, trail), 0.02 * rng.normal(size=nr)) for _ in range(count)]
+
+
+def oracle_filter(oracle, params, m, P, t0=None):
+    o = oracle.Ekf(params)
+    o.set_state(m)
+    o.set_cov(P)
+    if t0 is not None:
+        o.set_first_sample_time(t0)
+    return o
+
+
+def visual_rd(params):
+    return R_VISUAL * R_VISUAL * (params.noiseScale * params.noiseScale)
+
+
+def predict_inputs(regime, trail, count, n_samples=5):
+    rng = np.random.default_rng([ord(regime), trail, 77])
+    acc0 = np.array([0.2, -0.1, 9.8])
+    return rng.normal(0, 0.05, (n_samples, count, 3)), acc0 + rng.normal(0, 0.05, (n_samples, count, 3))
+
+
+def predict_truth(oracle, params, m, P, gyro, acc, dt=0.005):
+    """The oracle's predicts of one filter and the truth's covariance alongside: (oracle filter after, truth P). Each sample's
+    F20 is the oracle's dydx and Qd what its predict leaves from P = 0 at the same mean."""
+    o = oracle_filter(oracle, params, m, P, 0.0)
+    T = np.asarray(P, LD)
+    for s in range(len(gyro)):
+        _, F, Qd = oracle_predict_terms(oracle, params, o.m.copy(), s * dt, (s + 1) * dt, gyro[s], acc[s])
+        o.predict((s + 1) * dt, gyro[s], acc[s])
+        assert np.array_equal(F, o.dydx)
+        T = predict_cov(T, F, Qd)
+    return o, T
