@@ -333,6 +333,8 @@ static int create_ctx(const hv_params *params, int high_priority, hv_ctx **out)
         if (rc == HV_OK) rc = hv::pyramid_init(c);
         if (rc == HV_OK) rc = hv::ransac5_init(c);
         if (rc == HV_OK) rc = hv::detect_tail_init(c);
+        if (rc == HV_OK) rc = hv::ekf_kernels_init(c);
+        if (rc == HV_OK) rc = hv::vu_prepare_init(c);
     } while (0);
     if (rc != HV_OK) { hv_destroy(h); return rc; }
     *out = h;

@@ -939,26 +939,25 @@ __device__ __forceinline__ void ekf_update_body(const UpdateArgs &a, const int b
         }
         if (nr < 1 || nr > a.nr) return;
         Rfull = nr + n + 1; R = Rfull;
-        if (USE_LDS) while ((R & 31) != 15 && (R & 31) != 17) R++;
+        if (USE_LDS) R = lds_stride(R);
     }
     double *m = a.m + (size_t)b * n, *P = a.P + (size_t)b * n * n;
     const double *H = a.H + (size_t)e * a.h_stride;        // record stride: the launch's row count x columns; leading dimension: nr
     const double rd = a.rdiag ? a.rdiag[b] : a.rd0;
     // Tall matrix T (a.R rows x nr columns, column-major with stride R >= a.R: T(r, c) = T[c * R + r]; in LDS
-    // the stride is padded to 15 or 17 mod 32 doubles, see ekf_launch_update):
+    // the stride is padded to lds_stride):
     //   rows 0 .. nr-1   S = H P H' + R            -> L           (S = L L')
     //   row  nr          v'                        -> z' = (L^-1 v)'
     //   rows nr+1 ..     (H P)'  (n rows)          -> Y' = (L^-1 H P)'
     // One blocked Cholesky pass over T does the factorisation and both triangular solves. The gate
-    // only needs rows 0 .. nr. All LDS comes from the dynamic region (keeps the base 16-byte aligned):
-    // [T] W[256] col[320] red[16] flag. USE_LDS is a template parameter so that the common case compiles to
+    // only needs rows 0 .. nr. All LDS comes from the dynamic region (keeps the base 16-byte aligned), carved as UpdateLds
+    // says for this record's shape. USE_LDS is a template parameter so that the common case compiles to
     // ds_read / ds_write (a run-time select would turn every access into a flat load).
-    double *T = USE_LDS ? smem : a.ws + (size_t)b * a.Rs * a.nr;
-    double *W = USE_LDS ? smem + (((size_t)R * nr + 1) & ~(size_t)1) : smem;   // inverse of the current diagonal block
-    double *col = W + 256;                                                      // column broadcast buffer of the diagonal factor
-    double *red = col + 544;                                                    // col[256 .. 527] is the dump area of factor_diag_block's branch-free stores
-    int *s_stop = reinterpret_cast<int *>(red + nwaves);
-    double *Hs = red + nwaves + 2;                // MODE 2: H zero-padded to (16 TI) x (16 lb), column-major, stride nrp
+    const UpdateLds L = update_lds(R, nr, nwaves, USE_LDS, 0);
+    double *T = USE_LDS ? smem + L.T : a.ws + (size_t)b * a.Rs * a.nr;
+    double *W = smem + L.chol + CHOL_W, *col = smem + L.chol + CHOL_COL, *red = smem + L.red;
+    int *s_stop = reinterpret_cast<int *>(smem + L.flag);
+    double *Hs = smem + L.Hs;                     // MODE 2: H zero-padded to (16 TI) x (16 lb), column-major, stride nrp
     constexpr int nrp = 16 * (TI > 0 ? TI : 1);
     const bool gate_only = a.mode == 0;
     const int rv = nr, ry = nr + 1;
@@ -1508,7 +1507,8 @@ __global__ __launch_bounds__(GATE_THREADS, 2) void ekf_gate_stream_kernel(GateAr
     const double *P = a.P + (size_t)b * n * n, *H = a.H + (size_t)b * nr * l;
     const int lb = (l + 15) >> 4;
     // LDS: Hs [16 lb][nrp] (k-major, zero padded) | T [(nr + 1) x nr, stride R] ; W / col / red live in Hs once the products are done
-    double *Hs = smem, *T = smem + (size_t)nrp * 16 * lb;
+    const GateStreamLds L = gate_stream_lds(TI, lb, R, nr);
+    double *Hs = smem + L.Hs, *T = smem + L.T;
     const int kq = lane >> 4, cl = lane & 15;
     // ---- stage H (zero padded) and zero T ----
     for (int i = t; i < nrp * 16 * lb; i += GATE_THREADS) {
@@ -1587,7 +1587,7 @@ __global__ __launch_bounds__(GATE_THREADS, 2) void ekf_gate_stream_kernel(GateAr
         __syncthreads();
     }
     for (int i = t; i < nr; i += GATE_THREADS) { T[(size_t)i * R + i] += a.rd; T[(size_t)i * R + nr] = a.v[(size_t)b * nr + i]; }
-    double *W = Hs, *col = Hs + 256, *red = Hs + 256 + 544;    // H is dead from here on
+    double *W = Hs + CHOL_W, *col = Hs + CHOL_COL, *red = Hs + CHOL_RED;    // H is dead from here on
     __syncthreads();
     // ---- blocked Cholesky of [S; v'] (see ekf_update_kernel phase C), rows 0 .. nr ----
     const int Rlim = nr + 1;
@@ -1652,7 +1652,7 @@ struct SparseGateArgs {
     const unsigned char *active;      // [batch]: 1 where triangulation and prepareVisualUpdate passed (written by the prepare launch)
     double rd, noise_scale;
     double *chi2; int *status;        // chi2 optional
-    int hs_doubles;                   // LDS carve: doubles reserved for the staged Hc (>= 816 + 4: it is the Cholesky scratch afterwards)
+    int hs_doubles;                   // LDS carve (SparseGateLds::T): doubles reserved for the staged Hc (it is the Cholesky scratch afterwards)
     int lds_doubles;                  // doubles available for Hc + [S; v'] together (BIG build: decides between the padded and the tight layout)
     int batch;
     const int *rec_count, *rec_list;  // this launch's records (compaction list of the long class), or null
@@ -1685,13 +1685,11 @@ __device__ __forceinline__ void sparse_gate_kernel_body(const SparseGateArgs &a,
     const int nr = __builtin_amdgcn_readfirstlane(nr_v);
     if (nr < 2 || nr > a.nr) return;
     const int n = a.n, npose = nr / (2 * a.ncam), na = 7 * npose + 1, na4 = (na + 3) & ~3;
-    const int ti = BIG ? max((nr + 15) >> 4, 4) : (nr + 15) >> 4;       // (the BIG build starts at the 4-tile instantiation)
-    int Rs = nr + 1;
-    while ((Rs & 31) != 15 && (Rs & 31) != 17) Rs++;
-    const bool tight = BIG && (size_t)na4 * 16 * ti + (size_t)Rs * nr > (size_t)a.lds_doubles;    // (uniform) does the padded layout fit?
-    if (tight) Rs = nr + 1 + ((nr + 1) & 1 ? 0 : 1);            // an odd stride is all the LDS budget allows
+    const int ti = BIG ? max((nr + 15) >> 4, 4) : (nr + 15) >> 4;       // (the BIG build starts at the 4-tile instantiation; chooses the sparse_gate instantiation below)
+    const SparseGateShape shape = sparse_gate_shape(BIG, nr, na4, (size_t)a.lds_doubles);    // (uniform) does the padded layout fit?
+    const bool tight = shape.tight;
+    const int Rs = shape.Rs, nrp = shape.nrp;
     if (tight && nr > HV_GATE_TIGHT_ROWS) return;              // (the launcher sizes LDS for <= 84 rows: never taken)
-    const int nrp = tight ? HV_GATE_TIGHT_ROWS : 16 * ti;
     double *Hs = smem, *T = smem + a.hs_doubles;
     int *s_acol = reinterpret_cast<int *>(T + (size_t)Rs * nr);
     const double *Hc = a.Hc + (size_t)b * a.nr * a.na_max;
@@ -1830,9 +1828,11 @@ __global__ __launch_bounds__(AUG_THREADS) void ekf_augment_kernel(AugmentArgs a)
     if (dropped < 0) dropped = a.cam_poses - 1;
     // [HP | K | G]: 7 x n each, row-major [k * n + j] and contiguous: rows 0..13 are the MFMA A operand
     // (HP; K), rows 7..20 the B operand (K; G) of step 4
-    double *HP = smem, *K = HP + POSE * n, *G = K + POSE * n;
-    double *S0 = G + POSE * n, *Lc = S0 + POSE * POSE, *vres = Lc + POSE * POSE;
-    double *scr_all = vres + POSE + 1;                                // 16 waves x 16 x 17 transpose scratch
+    static_assert(AUG_POSE == POSE && AUG_J == AUGJ, "AugmentLds is written for the pose block of this state layout");
+    const AugmentLds L = augment_lds(n, AUG_THREADS / 64);
+    double *HP = smem + L.HP, *K = smem + L.K, *G = smem + L.G;
+    double *S0 = smem + L.S0, *Lc = smem + L.Lc, *vres = smem + L.vres;
+    double *scr_all = smem + L.scratch;                               // 16 waves x 16 x 17 transpose scratch
 
     // P1 = A P A' + Q as a function (ekf.cpp:230-248, 848-871)
     auto p1 = [&](int i, int j) -> double {
@@ -1952,7 +1952,7 @@ __global__ __launch_bounds__(AUG_THREADS) void ekf_augment_kernel(AugmentArgs a)
     // absolute error, and P(:, j) = W T(j, :)' + rd K K(j, :)' carries W's cancellation error times that small number only.
     // Wc (n x 14) and T14 borrow the transpose scratch, which step 4 is done with.
     {
-        double *Wc = scr_all, *T14 = Wc + AUGJ * n;
+        double *Wc = scr_all, *T14 = smem + L.T14;
         for (int e = t; e < AUGJ * n; e += AUG_THREADS) {
             const int cc = e / n, i = e % n, jc = augj_index(cc);
             double w = p1(i, jc);
@@ -2120,7 +2120,7 @@ __global__ __launch_bounds__(256) void ekf_transform_kernel(TransformArgs a)
 // host side
 // ---------------------------------------------------------------------------------------------
 // an update launch prepared but not issued (UpdateRequest::defer): two of them can share one grid (ekf_launch_update_dual)
-struct UpdateLaunch { UpdateArgs a; size_t base_bytes = 0; int kmode = -1, ti = 0, lbk = 0; };
+struct UpdateLaunch { UpdateArgs a; int kmode = -1, ti = 0, lbk = 0; };
 
 int ekf_launch_update(Ekf *e, const UpdateRequest &rq)
 {
@@ -2133,12 +2133,8 @@ int ekf_launch_update(Ekf *e, const UpdateRequest &rq)
     if (!generic && mode != 1 && nr >= HV_CHI2INV95_N) return HV_ERR_INVALID;
     UpdateArgs a{};
     a.n = e->n; a.nr = nr; a.l = l; a.R = nr + e->n + 1;
-    // LDS stride of T: 15 or 17 mod 32 doubles. Odd keeps the 16 lanes of a row-strided operand read (S = HP H')
-    // in distinct banks; 2 Rs = 30 or 34 mod 64 dwords puts the k-groups of a column-strided read (the
-    // Cholesky panels, Y'Y) half a bank array apart.
-    int r_pad = a.R;
-    while ((r_pad & 31) != 15 && (r_pad & 31) != 17) r_pad++;
-    a.Rs = r_pad;
+    const UpdateShape shape = update_shape(e->n, nr, l, UPD_THREADS / 64);
+    a.Rs = shape.Rs;                                     // (lds_stride; unpadded where T lives in the global workspace)
     a.mode = mode; a.generic = generic; a.normalize_all = rq.normalize_all; a.map_dim = e->map_dim;
     a.m = e->m; a.P = e->P; a.H = rq.H_dev; a.v = rq.v_dev; a.rdiag = rq.rdiag_dev; a.rd0 = rq.rd0; a.rd1 = rq.rd1; a.noise_scale = e->noise_scale;
     a.ws = e->ws; a.chi2 = rq.chi2_dev; a.status = rq.status_dev; a.active = rq.active_dev; a.require_inlier = rq.require_inlier_dev; a.success_counter = rq.success_counter_dev;
@@ -2155,42 +2151,29 @@ int ekf_launch_update(Ekf *e, const UpdateRequest &rq)
         a.half_auto = compact->half_auto; a.sel_io = compact->sel_io; a.epoch = compact->epoch;
         if (a.half_auto && (spec != 2 || !a.half || !a.sel_io || !a.dm_out == !a.dm_in)) return HV_ERR_INVALID;
     }
-    size_t tall = (((size_t)a.Rs * nr + 1) & ~(size_t)1) * sizeof(double);
-    const size_t small = (size_t)(256 + 544 + UPD_THREADS / 64 + 2) * sizeof(double);           // W + col (incl. dump area) + red + flag
-    const int ti = (nr + 15) / 16, lbk = (l + 15) / 16;
-    const size_t hbytes = (size_t)(16 * ti) * (16 * lbk) * sizeof(double);                      // zero-padded H
-    const size_t lds_cap = 160 * 1024;                       // the whole LDS of a CU: T alone reaches 154 KB at 80 rows (20 stereo poses)
-    a.use_lds = tall + small <= lds_cap;
-    if (!a.use_lds) { a.Rs = a.R; tall = (((size_t)a.R * nr + 1) & ~(size_t)1) * sizeof(double); }   // global workspace: no padding
-    int kmode = !a.use_lds ? 0 : (e->n <= 160 && nr <= 48 && tall + small + hbytes <= lds_cap) ? 2 : 1;
+    const int ti = shape.ti, lbk = shape.lbk;
+    int kmode = shape.kmode;
+    a.use_lds = kmode != 0;
     // HV_EKF_GATE_KMODE (environment, experiments only): kernel variant for gate-only launches (1 = H streamed from L2, 2 WGs / CU)
     if (c->knob.ekf_gate_kmode == 1 && mode == 0 && !spec && kmode == 2) kmode = 1;
     if (a.acol && kmode != 2) return HV_ERR_UNSUPPORTED; // compact H is staged by the LDS-resident kernel only (vu_fused_supported)
     if (mode == 3) {                                     // gate (rd0) + update (rd1) in one launch: MODE 2 kernels only
-        const bool can = kmode == 2 && ((size_t)(nr + 1) * nr + 256) * sizeof(double) <= hbytes;
+        const bool can = kmode == 2 && shape.two_r;
         if (rq.two_r_done) *rq.two_r_done = can;
         if (!can) return HV_OK;                          // the caller falls back to two launches
     }
     if (spec && kmode != 2) return HV_ERR_UNSUPPORTED;   // the speculative loop keeps every record in the LDS-resident kernel
-    const size_t shmem = kmode == 2 ? tall + small + hbytes : kmode == 1 ? tall + small : small;
+    const size_t shmem = lds_bytes(update_lds(shape.Rs, nr, UPD_THREADS / 64, kmode != 0, kmode == 2 ? shape.hs : 0));
     a.batch = e->batch;
     if (UpdateLaunch *defer = rq.defer) {
         if (mode == 3 || spec) return HV_ERR_INVALID;
-        defer->a = a; defer->base_bytes = tall + small; defer->kmode = kmode; defer->ti = ti; defer->lbk = lbk;
+        defer->a = a; defer->kmode = kmode; defer->ti = ti; defer->lbk = lbk;
         return HV_OK;
     }
     using Kern = void (*)(UpdateArgs);
     if (a.half_auto && (kmode != 2 || ti != 3)) return HV_ERR_INVALID;
     const Kern kern = a.half_auto ? (Kern)ekf_update_spec_long_kernel : kmode == 0 ? (Kern)ekf_update_kernel<0, 0> : kmode == 1 ? (Kern)ekf_update_kernel<1, 0>
                     : ti == 1 ? (Kern)ekf_update_kernel<2, 1> : ti == 2 ? (Kern)ekf_update_kernel<2, 2> : (Kern)ekf_update_kernel<2, 3>;
-    // the attribute is per device: one flag per device ordinal (several contexts / devices may live in one process)
-    static bool attr_set_dev[64] = {};
-    bool &attr_set = attr_set_dev[c->p.device & 63];
-    if (!attr_set) {
-        for (Kern k : { (Kern)ekf_update_kernel<1, 0>, (Kern)ekf_update_kernel<2, 1>, (Kern)ekf_update_kernel<2, 2>, (Kern)ekf_update_kernel<2, 3>, (Kern)ekf_update_spec_long_kernel })
-            HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
     ScopedKernelTime tm(c, HV_K_EKF_UPDATE);
     hipLaunchKernelGGL(kern, dim3(e->batch, (spec == 1 || spec == 3) ? rq.n_tracks : 1), dim3(UPD_THREADS), shmem, c->stream, a);
     HV_HIP(c, hipGetLastError());
@@ -2206,15 +2189,9 @@ static int ekf_launch_update_dual(Ekf *e, const UpdateLaunch &A, const UpdateLau
     if (A.kmode != 2 || B.kmode != 2 || !A.a.rec_list || !B.a.rec_list || !A.a.rec_count || !B.a.rec_count) return HV_OK;
     const int ti = A.ti > B.ti ? A.ti : B.ti;
     if (ti != 3) return HV_OK;                                     // (the only pairing the visit loop produces: 44 + 42 rows)
-    const size_t sa = A.base_bytes + (size_t)(16 * ti) * (16 * A.lbk) * sizeof(double), sb = B.base_bytes + (size_t)(16 * ti) * (16 * B.lbk) * sizeof(double);
-    const size_t shmem = sa > sb ? sa : sb;
-    if (shmem > 160 * 1024) return HV_OK;
-    static bool attr_set_dev[64] = {};
-    bool &attr_set = attr_set_dev[c->p.device & 63];
-    if (!attr_set) {
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(ekf_update_dual_kernel<2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
+    const auto bytes = [ti](const UpdateLaunch &u) { return lds_bytes(update_lds(u.a.Rs, u.a.nr, UPD_THREADS / 64, true, (size_t)(16 * ti) * (16 * u.lbk))); };
+    const size_t sa = bytes(A), sb = bytes(B), shmem = sa > sb ? sa : sb;
+    if (shmem > LDS_UPDATE_LIMIT) return HV_OK;
     ScopedKernelTime tm(c, HV_K_EKF_UPDATE);
     UpdatePair pair;
     pair.a[0] = A.a; pair.a[1] = B.a;
@@ -2249,26 +2226,16 @@ int ekf_launch_gate_stream(Ekf *e, const GateStreamRequest &rq)
     if (nr < 1 || nr > 48 || nr >= HV_CHI2INV95_N || l < 1 || l > e->n) return HV_OK;        // the caller keeps its other route
     GateArgs a{};
     a.n = e->n; a.nr = nr; a.l = l;
-    int r_pad = nr + 1;
-    while ((r_pad & 31) != 15 && (r_pad & 31) != 17) r_pad++;
-    a.Rs = r_pad;
+    a.Rs = lds_stride(nr + 1);
     a.P = e->P; a.H = rq.H_dev; a.v = rq.v_dev; a.rd = rq.rd; a.noise_scale = e->noise_scale; a.chi2 = rq.chi2_dev; a.status = rq.status_dev;
     a.active = rq.active_dev; a.success_counter = rq.success_counter_dev; a.max_successful = rq.max_successful;
-    const int ti = (nr + 15) / 16, lbk = (l + 15) / 16;
-    const size_t hs = (size_t)(16 * ti) * (16 * lbk), shmem = sizeof(double) * (hs + (size_t)a.Rs * nr + 2);
-    if (hs < 256 + 544 + 8) return HV_OK;                          // W / col / red borrow the H area
+    const int ti = tiles16(nr);
+    const GateStreamLds L = gate_stream_lds(ti, tiles16(l), a.Rs, nr);
+    if (!gate_stream_admitted(L)) return HV_OK;                               // W / col / red borrow the H area; the gate limit
     using Kern = void (*)(GateArgs);
     const Kern kern = ti == 1 ? (Kern)ekf_gate_stream_kernel<1> : ti == 2 ? (Kern)ekf_gate_stream_kernel<2> : (Kern)ekf_gate_stream_kernel<3>;
-    static bool attr_set_dev[64] = {};
-    bool &attr_set = attr_set_dev[c->p.device & 63];
-    if (!attr_set) {
-        for (Kern k : { (Kern)ekf_gate_stream_kernel<1>, (Kern)ekf_gate_stream_kernel<2>, (Kern)ekf_gate_stream_kernel<3> })
-            HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_set = true;
-    }
-    if (shmem > 96 * 1024) return HV_OK;
     ScopedKernelTime tm(c, HV_K_EKF_UPDATE);
-    hipLaunchKernelGGL(kern, dim3(e->batch), dim3(GATE_THREADS), shmem, c->stream, a);
+    hipLaunchKernelGGL(kern, dim3(e->batch), dim3(GATE_THREADS), lds_bytes(L), c->stream, a);
     HV_HIP(c, hipGetLastError());
     *done = true;
     return HV_OK;
@@ -2279,41 +2246,38 @@ int ekf_launch_sparse_gate(Ekf *e, const SparseGateRequest &rq)
     Ctx *c = e->c;
     const int np = rq.np, ncam = rq.ncam;
     const hipStream_t stream = rq.stream ? rq.stream : c->stream;
-    const int nr = 2 * np * ncam, na_max = 7 * np + 1, na4 = (na_max + 3) & ~3, nrp = 16 * ((nr + 15) / 16);
+    const int nr = 2 * np * ncam, na_max = 7 * np + 1;
     if (nr < 2 || nr > 96 || nr >= HV_CHI2INV95_N || !rq.active_dev || !rq.status_dev) return HV_ERR_INVALID;
-    const bool big = nr > 48;
+    const SparseGateLds L = sparse_gate_lds(np, ncam);      // sized for the launch's longest record
+    if (!L.supported) return HV_ERR_UNSUPPORTED;
     SparseGateArgs a{};
     a.n = e->n; a.nr = nr; a.ncam = ncam; a.na_max = na_max; a.P = e->P; a.Hc = rq.Hc_dev; a.v = rq.v_dev; a.acol = rq.acol_dev; a.nr_rec = rq.nr_rec_dev;
     a.active = rq.active_dev; a.rd = rq.rd; a.noise_scale = e->noise_scale; a.chi2 = rq.chi2_dev; a.status = rq.status_dev;
-    int Rs = nr + 1;
-    while ((Rs & 31) != 15 && (Rs & 31) != 17) Rs++;
-    // LDS: Hc staged [na4][nrp] + [S; v'] (Rs x nr) + the column list. The launch is sized for its longest record; in the big build a
-    // record whose padded layout does not fit (84 rows) uses the tight one (nrp = 84, odd Rs) inside the same carve.
-    size_t hs = (size_t)na4 * nrp, tt = (size_t)Rs * nr;
-    // (the gate's turn counters are 32 bytes of STATIC LDS: the dynamic part of the big build ends 64 bytes below the CU's 160 KB)
-    constexpr size_t BIG_CAP = 160 * 1024 - 64;
-    const size_t cap = big ? BIG_CAP : (size_t)96 * 1024, ints = sizeof(int) * (size_t)(na_max + 2);
-    if (big && sizeof(double) * (hs + tt) + ints > cap) {
-        if (nr > HV_GATE_TIGHT_ROWS) return HV_ERR_UNSUPPORTED;
-        hs = (size_t)na4 * HV_GATE_TIGHT_ROWS; tt = (size_t)(nr + 2) * nr;
-    }
-    if (hs < 824) hs = 824;
-    a.hs_doubles = (int)hs; a.lds_doubles = (int)(hs + tt);
-    const size_t shmem = sizeof(double) * (hs + tt) + ints;
-    if (shmem > cap) return HV_ERR_UNSUPPORTED;
-    static bool attr_set_dev[64] = {};
-    bool &attr_set = attr_set_dev[c->p.device & 63];
-    if (!attr_set) {
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(ekf_sparse_gate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(ekf_sparse_gate_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BIG_CAP));
-        attr_set = true;
-    }
+    a.hs_doubles = (int)(L.T - L.Hs); a.lds_doubles = (int)(L.acol - L.Hs);
     ScopedKernelTime tm(c, HV_K_EKF_GATE, stream);
     a.rec_count = rq.rec_count; a.rec_list = rq.rec_list; a.inl_count = rq.inl_count; a.inl_list = rq.inl_list;
     a.batch = e->batch;
-    if (big) hipLaunchKernelGGL(ekf_sparse_gate_big_kernel, dim3((unsigned)e->batch), dim3(SGATE_BIG_THREADS), shmem, stream, a);
-    else     hipLaunchKernelGGL(ekf_sparse_gate_kernel, dim3(e->batch), dim3(SGATE_THREADS), shmem, stream, a);
+    if (L.big) hipLaunchKernelGGL(ekf_sparse_gate_big_kernel, dim3((unsigned)e->batch), dim3(SGATE_BIG_THREADS), L.bytes, stream, a);
+    else       hipLaunchKernelGGL(ekf_sparse_gate_kernel, dim3(e->batch), dim3(SGATE_THREADS), L.bytes, stream, a);
     HV_HIP(c, hipGetLastError());
+    return HV_OK;
+}
+
+// the kernels' dynamic-LDS limits, set once per context (hv_create; never inside a launch that may be under capture)
+int ekf_kernels_init(Ctx *c)
+{
+    HV_HIP(c, set_lds_limit(ekf_update_kernel<1, 0>, LDS_UPDATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_update_kernel<2, 1>, LDS_UPDATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_update_kernel<2, 2>, LDS_UPDATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_update_kernel<2, 3>, LDS_UPDATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_update_spec_long_kernel, LDS_UPDATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_update_dual_kernel<2, 3>, LDS_UPDATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_gate_stream_kernel<1>, LDS_GATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_gate_stream_kernel<2>, LDS_GATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_gate_stream_kernel<3>, LDS_GATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_sparse_gate_kernel, LDS_GATE_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_sparse_gate_big_kernel, LDS_SGATE_BIG_LIMIT));
+    HV_HIP(c, set_lds_limit(ekf_augment_kernel<false>, LDS_AUGMENT_LIMIT));      // (<true>, the device-pointer entries' folded form, stays at LDS_DEFAULT_LIMIT)
     return HV_OK;
 }
 
@@ -2694,8 +2658,7 @@ static size_t augment_fill(const Ekf *e, hv::AugmentArgs &a)
     a.q_pos = e->par.noiseInitialPosTrail * e->par.noiseInitialPosTrail * e->noise_scale;
     a.q_ori = e->par.noiseInitialOriTrail * e->par.noiseInitialOriTrail * e->noise_scale;
     a.rd = e->par.augmentR * e->noise_scale;
-    const int scratch = std::max((hv::AUG_THREADS / 64) * 16 * 17, hv::AUGJ * e->n + hv::AUGJ * hv::AUGJ);   // transposes, then Wc + T14
-    return sizeof(double) * (3 * hv::POSE * e->n + 2 * hv::POSE * hv::POSE + hv::POSE + 1 + scratch);
+    return hv::lds_bytes(hv::augment_lds(e->n, hv::AUG_THREADS / 64));
 }
 
 int hv_ekf_augment(hv_ekf *h, const int *discarded, const unsigned char *active)
@@ -2709,15 +2672,7 @@ int hv_ekf_augment(hv_ekf *h, const int *discarded, const unsigned char *active)
         else { HV_HIP(c, hipMemcpyAsync(e->sdrop, discarded, sizeof(int) * e->batch, hipMemcpyHostToDevice, c->stream)); a.dropped = e->sdrop; }
     }
     if (active) { HV_HIP(c, hipMemcpyAsync(e->sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); a.active = e->sactive; }
-    if (shmem > 64 * 1024) {                 // state vectors with map points (n > ~190): beyond the default dynamic-LDS limit
-        if (shmem > 158 * 1024) return HV_ERR_UNSUPPORTED;
-        static bool aug_attr_set_dev[64] = {};
-        bool &aug_attr_set = aug_attr_set_dev[c->p.device & 63];
-        if (!aug_attr_set) {
-            HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(hv::ekf_augment_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-            aug_attr_set = true;
-        }
-    }
+    if (shmem > hv::LDS_AUGMENT_LIMIT) return HV_ERR_UNSUPPORTED;      // (state vectors with map points, n > ~190, need more than the default limit)
     hv::ScopedKernelTime tm(c, HV_K_EKF_AUGMENT);
     hipLaunchKernelGGL(hv::ekf_augment_kernel<false>, dim3(e->batch), dim3(hv::AUG_THREADS), shmem, c->stream, a);
     HV_HIP(c, hipGetLastError());
@@ -2732,7 +2687,7 @@ static int augment_dev_impl(hv_ekf *h, const int *discarded_dev, const unsigned 
     hv::AugmentArgs a;
     const size_t shmem = augment_fill(e, a);
     a.dropped = discarded_dev; a.active = active_dev;
-    if (shmem > 64 * 1024) return HV_ERR_UNSUPPORTED;        // map-point states: use hv_ekf_augment (it raises the LDS limit)
+    if (shmem > hv::LDS_DEFAULT_LIMIT) return HV_ERR_UNSUPPORTED;     // map-point states: use hv_ekf_augment (only ekf_augment_kernel<false> has a raised LDS limit)
     hv::ScopedKernelTime tm(c, HV_K_EKF_AUGMENT);
     if (sym_input) hipLaunchKernelGGL(hv::ekf_augment_kernel<true>, dim3(e->batch), dim3(hv::AUG_THREADS), shmem, c->stream, a);
     else           hipLaunchKernelGGL(hv::ekf_augment_kernel<false>, dim3(e->batch), dim3(hv::AUG_THREADS), shmem, c->stream, a);

@@ -5,6 +5,7 @@
 #include <type_traits>
 #include "chi2inv95.h"
 #include "hv_internal.hpp"
+#include "lds_layout.hpp"
 
 // (both including translation units select fused multiply-adds for their f64 algebra; see ekf.hip)
 #pragma clang fp contract(fast)
@@ -154,7 +155,7 @@ __device__ __forceinline__ void lds_barrier()
 
 // Second half of a chi2 gate, by one workgroup of NT threads: T holds the lower triangle of H P H' (column-major, stride Rs) and v' in row
 // nr; adds R = rd I, runs the blocked Cholesky of [S; v'] and returns chi2 = noise_scale z'z in every thread (a non-positive pivot leaves
-// inf / NaN in it). work: >= 816 + NT / 64 doubles of LDS scratch. The caller has synchronised the workgroup behind its last write of T.
+// inf / NaN in it). work: chol_scratch_doubles(NT / 64) doubles of LDS scratch. The caller has synchronised the workgroup behind its last write of T.
 template <int NT>
 __device__ __forceinline__ double gate_factor_chi2(double *T, int Rs, int nr, double rd, double noise_scale, double *work, long long *stamps = nullptr)
 {
@@ -167,7 +168,7 @@ __device__ __forceinline__ double gate_factor_chi2(double *T, int Rs, int nr, do
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     constexpr int nwaves = NT / 64;
     for (int i = t; i < nr; i += NT) T[(size_t)i * Rs + i] += rd;
-    double *W = work, *col = work + 256, *red = work + 256 + 544;
+    double *W = work + CHOL_W, *col = work + CHOL_COL, *red = work + CHOL_RED;
     lds_barrier();
     // blocked Cholesky of [S; v'] (ekf_update_kernel phase C restricted to the measurement rows). The diagonal blocks are factored by ONE
     // wave (a ~340-cycle dependent chain per pivot that keeps its SIMD's issue port about half busy): the workgroups that share a CU use
@@ -426,7 +427,7 @@ __device__ __forceinline__ void structured_S(const double *P, int N, const int *
 //     S  += Hc(:, J) G_J    (A = Hc from LDS, B = the accumulator tile of the first product)
 // so neither H P nor P(a, a) is ever stored. Then the blocked Cholesky of [S; v'] and chi2 = noise_scale z'z.
 // LDS inputs: acol[na]; Hs = Hc k-major [4 ceil(na / 4)][16 TI], zero in rows >= nr and columns >= na; T = (nr + 1) x nr column-major
-// with stride Rs, ZEROED except row nr = v'. work: >= 816 + NT / 64 doubles of scratch (may alias Hs: it is used after the products).
+// with stride Rs, ZEROED except row nr = v'. work: chol_scratch_doubles(NT / 64) doubles of scratch (may alias Hs: it is used after the products).
 // Every thread returns the same chi2; a non-positive pivot leaves inf / NaN in it (the caller reports CHI2, as ekf_update_kernel does).
 // ---------------------------------------------------------------------------------------------
 // PIPE: the P values of an item rotate through one register buffer with the NEXT item's loads issued behind each MFMA (standalone gate
@@ -435,7 +436,6 @@ __device__ __forceinline__ void structured_S(const double *P, int N, const int *
 // nr .. 83 zero); the last row tile reads on into the next column instead of meeting zero padding.
 // (ONE static array for every instantiation of sparse_gate: the two-per-CU build of the fused kernel has 192 bytes of LDS to spare)
 __device__ __forceinline__ int *gate_turn_lds() { __shared__ int turn[8]; return turn; }
-constexpr int HV_GATE_TIGHT_ROWS = 84;     // rows per staged column of the TIGHT layout: 21 stereo poses, the longest track there is
 template <int TI, int NT, bool PIPE, bool TIGHT = false>
 __device__ __forceinline__ double sparse_gate(const double *P, int n, const int *acol, int na, const double *Hs, double *T, int Rs, int nr,
                                               double rd, double noise_scale, double *work, long long *stamps = nullptr)

@@ -246,9 +246,15 @@ struct VuPrepareArgs {
 };
 // doubles per factor record of vu_tri_kernel for tracks of up to np poses on ncam cameras
 inline int vu_tri_rec_stride(int np, int ncam) { return 17 * np * ncam + 21 * np + 4; }
+template <class K> inline hipError_t set_lds_limit(K kernel, size_t bytes)      // a kernel's dynamic-LDS limit (per device; the *_init functions below)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
 int ransac5_init(Ctx *c);              // ransac5.hip: the kernel's dynamic-LDS limit, set once per context
 int detect_tail_init(Ctx *c);         // detect_tail.hip: likewise
 int pyramid_init(Ctx *c);             // pyramid.hip: likewise
+int ekf_kernels_init(Ctx *c);         // ekf.hip: likewise, every EKF kernel that carves dynamic LDS (lds_layout.hpp)
+int vu_prepare_init(Ctx *c);          // vu_prepare.hip: likewise, the prepare / gate builds
 int rot_ransac_alloc_split(Ctx *c);     // rot_ransac.hip: the split form's record buffer, allocated and zeroed once per context
 int launch_vu_tri(Ctx *c, const VuPrepareArgs &a, hipStream_t stream = nullptr);       // the triangulation front of the split form
 bool vu_split_supported(const Ctx *c, const VuPrepareArgs &a, int fused);              // shapes the record-fed gate builds serve

@@ -334,7 +334,8 @@ template <int MAXP, bool LONG = false>
 struct VuLds {
     static constexpr int MAXC = MAXP * 7 + 1, MOT_STRIDE = 13;
     static constexpr int MAXPAIRS = 14 * MAXP - 7;            // motion pairs: 7 nt with a pose-0 column + 7 (nt - 1) with the pose's own column
-    static constexpr int LONG_T = 7224, LONG_HS = 12432;      // doubles: (84 + 2) x 84, 148 x 84
+    static constexpr int LONG_T = (HV_GATE_TIGHT_ROWS + 2) * HV_GATE_TIGHT_ROWS, LONG_HS = (7 * MAXNP + 1) * HV_GATE_TIGHT_ROWS;   // doubles: (84 + 2) x 84, 148 x 84
+    static_assert(LONG_T == 7224 && LONG_HS == 12432, "the long gate's areas as the kernels were measured with");
     static constexpr int TRAIL = 0, IT = TRAIL + MAXP * POSE_WORDS, DPFI = IT + MAXP * ITER_WORDS, FEAT = DPFI + 3 * MAXC,
                          SMALL = FEAT + MAXP * 4, DPF = SMALL + 64, P0 = DPF + MAXNP * 21, MOT = P0 + 7 * MAXP * 9 + 7 * 9,
                          OWN = MOT + MAXPAIRS * MOT_STRIDE, LIN = OWN + MAXC * 9, LIN_END = LIN + 3 * MAXP * 9 + 32,
@@ -346,7 +347,7 @@ struct VuLds {
     static constexpr int HS_DOUBLES = INTS - P0, T_DOUBLES = P0;
     static constexpr size_t BYTES = sizeof(double) * TOTAL;
 };
-static_assert(VuLds<42, true>::BYTES <= 160 * 1024, "the long build must fit one CU's LDS");
+static_assert(VuLds<42, true>::BYTES <= LDS_CU_BYTES, "the long build must fit one CU's LDS");
 
 // LDS layout of the RECORD-FED gate builds (r06, VuPrepareArgs::from_rec): the front has run in vu_tri_kernel, so only the gate's own
 // areas are left -- [S; v'] in [0, P0), the staged Jacobian / the factors and their products behind it -- and the record's copies (the
@@ -355,12 +356,14 @@ static_assert(VuLds<42, true>::BYTES <= 160 * 1024, "the long build must fit one
 template <int MAXP, bool LONG = false>
 struct VuRecLds {
     static constexpr int MAXC = MAXP * 7 + 1, MOT_STRIDE = 13;
-    static constexpr int LONG_T = 7224, LONG_HS = 12432;
+    static constexpr int LONG_T = VuLds<MAXP, LONG>::LONG_T, LONG_HS = VuLds<MAXP, LONG>::LONG_HS;
     static constexpr int TRAIL = 0, IT = 0, FEAT = IT + MAXP * ITER_WORDS, DPF = FEAT + MAXP * 4, DPFI = DPF + MAXP * 21, SMALL = DPFI + 4,
                          SMALL_END = SMALL + 64;
-    static constexpr int P0 = LONG ? LONG_T : 2352;                      // short class: [S; v'] of up to 48 rows at stride 49 (44 rows: 47)
+    static constexpr int SHORT_T = lds_stride(48 + 1) * 48, SHORT_HS = ((7 * (MAXP_REC / 2) + 1 + 3) & ~3) * 48;     // doubles: 49 x 48, 88 x 48
+    static_assert(SHORT_T == 2352 && SHORT_HS == 4224, "the short gate's areas as the kernels were measured with");
+    static constexpr int P0 = LONG ? LONG_T : SHORT_T;                   // short class: [S; v'] of up to 48 rows at stride 49 (44 rows: 47)
     static constexpr int MOT = P0, OWN = P0, LIN = P0;                   // (no Gauss-Newton arrays)
-    static constexpr int INTS = LONG ? LONG_T + LONG_HS : P0 + 4224;     // short class: the staged Jacobian, 88 columns x 48 rows
+    static constexpr int INTS = LONG ? LONG_T + LONG_HS : P0 + SHORT_HS; // short class: the staged Jacobian, 88 columns x 48 rows
     static constexpr int TOTAL = INTS + (MAXNP + 3 + 4 + MAXC + 1) / 2 + 1;
     static constexpr int HS_DOUBLES = INTS - P0, T_DOUBLES = P0;
     static_assert(SMALL_END <= P0, "the record's copies must fit in front of the staged Jacobian");
@@ -901,10 +904,9 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
         constexpr bool STRUCT = FUSED == 3;
         constexpr bool STAGED = FUSED == 1;                       // the compact Jacobian is also staged in LDS for the gate of this launch
         const int na = 7 * n + 1, na4 = (na + 3) & ~3, ti = (rows + 15) >> 4;
-        int Rs = rows + 1;                                        // column stride of [S; v']: 15 or 17 mod 32 doubles (bank spread)
-        while ((Rs & 31) != 15 && (Rs & 31) != 17) Rs++;
+        int Rs = lds_stride(rows + 1);                            // column stride of [S; v']
         constexpr int T_CAP = FUSED == 3 ? Lay::LONG_T : Lay::T_DOUBLES, REGION = FUSED == 3 ? Lay::LONG_HS : Lay::HS_DOUBLES;
-        if (STRUCT && Rs * rows > T_CAP) Rs = rows + 1 + (((rows + 1) & 1) ? 0 : 1);      // the longest tracks: any odd stride that fits (84 rows: 85)
+        if (STRUCT && Rs * rows > T_CAP) Rs = lds_stride_tight(rows + 1);                 // the longest tracks: any odd stride that fits (84 rows: 85)
         const int nrp = 16 * ti;                                  // (STAGED: rows per staged column)
         // region behind [S; v'] (the dead motion / linear-map arrays): the staged Jacobian, or the factors, their products and G
         double *Hs = vu_lds + (FUSED == 3 ? Lay::LONG_T : Lay::P0);
@@ -1675,12 +1677,11 @@ bool vu_fused_supported(const Ctx *c, int n_state, int np, int stereo, int batch
     if (c->knob.ekf_fused_gate == 0) return false;
     const int nt = np * (stereo ? 2 : 1), rows = 2 * nt, na4 = (7 * np + 1 + 3) & ~3, nrp = 16 * ((rows + 15) / 16);
     if (np < 2 || np > MAXNP || nt > MAXP_ALL || rows > 48 || rows >= HV_CHI2INV95_N || n_state < 1 || n_state > 160) return false;
-    int Rs = rows + 1;
-    while ((Rs & 31) != 15 && (Rs & 31) != 17) Rs++;
+    const int Rs = lds_stride(rows + 1);
     const bool small = vu_small_build(c, nt, batch);
     const int hs_cap = small ? VuLds<MAXP_SMALL>::HS_DOUBLES : VuLds<MAXP_ALL>::HS_DOUBLES;
     const int t_cap = small ? VuLds<MAXP_SMALL>::T_DOUBLES : VuLds<MAXP_ALL>::T_DOUBLES;
-    return na4 * nrp <= hs_cap && 816 + VT_LATENCY / 64 <= hs_cap && Rs * rows <= t_cap;
+    return na4 * nrp <= hs_cap && chol_scratch_doubles(VT_LATENCY / 64) <= hs_cap && Rs * rows <= t_cap;
 }
 
 // shapes the split form serves: iterative triangulation of pose-trail tracks, no speculation; the record-fed short-class gate holds
@@ -1701,12 +1702,26 @@ bool vu_split_supported(const Ctx *c, const VuPrepareArgs &a, int fused)
     if (fused == 1) {
         if (!vu_split_short_ok(c, a.n, a.stereo != 0, a.batch, a.linear != 0) || np_sel * ncam > MAXP_REC) return false;
         const int rows = 2 * np_sel * ncam, na4 = (7 * np_sel + 1 + 3) & ~3, nrp = 16 * ((rows + 15) / 16);
-        int Rs = rows + 1;
-        while ((Rs & 31) != 15 && (Rs & 31) != 17) Rs++;
+        const int Rs = lds_stride(rows + 1);
         return rows < HV_CHI2INV95_N && na4 * nrp <= VuRecLds<MAXP_REC>::HS_DOUBLES && Rs * rows <= VuRecLds<MAXP_REC>::T_DOUBLES &&
                c->knob.ekf_fused_gate != 0 && np_sel >= 2;
     }
     return fused == 3 && c->knob.ekf_split_tri != 3;        // (3: experiments -- the short class only, the long class keeps r05's fused launch)
+}
+
+// the kernels' dynamic-LDS limits (each build's whole carve: more than the default 64 KB), set once per context (hv_create)
+int vu_prepare_init(Ctx *c)
+{
+    HV_HIP(c, set_lds_limit(vu_prepare_kernel, VuLds<MAXP_ALL>::BYTES));
+    HV_HIP(c, set_lds_limit(vu_prepare_kernel_2percu, VuLds<MAXP_SMALL>::BYTES));
+    HV_HIP(c, set_lds_limit(vu_gate_kernel, VuLds<MAXP_ALL>::BYTES));
+    HV_HIP(c, set_lds_limit(vu_gate_kernel_2percu, VuLds<MAXP_SMALL>::BYTES));
+    HV_HIP(c, set_lds_limit(vu_compact_kernel, VuLds<MAXP_ALL>::BYTES));
+    HV_HIP(c, set_lds_limit(vu_compact_kernel_2percu, VuLds<MAXP_SMALL>::BYTES));
+    HV_HIP(c, set_lds_limit(vu_gate_long_kernel, VuLds<MAXP_ALL, true>::BYTES));
+    HV_HIP(c, set_lds_limit(vu_gate_long_rec_kernel, VuRecLds<MAXP_ALL, true>::BYTES));
+    HV_HIP(c, set_lds_limit(vu_prepare_map_kernel, VuLds<MAXP_ALL>::BYTES));
+    return HV_OK;
 }
 
 int launch_vu_tri(Ctx *c, const VuPrepareArgs &a, hipStream_t stream)
@@ -1751,29 +1766,9 @@ int launch_vu_prepare(Ctx *c, const VuPrepareArgs &a, hipStream_t stream)
         // (speculative frame loop, r04: grid (filters, tracks), never listed -- every pending record of whatever length on this build)
         if (!a.P || (a.spec_tracks > 0 && a.rec_list) || a.n > 160 || rows > HV_GATE_TIGHT_ROWS || rows >= HV_CHI2INV95_N) return HV_ERR_UNSUPPORTED;
     }
-    static bool attr_set_dev[64] = {};                       // per device: the kernels need more than the default 64 KB of dynamic LDS
-    bool &attr_set = attr_set_dev[c->p.device & 63];
-    if (!attr_set) {
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_prepare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VuLds<MAXP_ALL>::BYTES));
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_prepare_kernel_2percu), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VuLds<MAXP_SMALL>::BYTES));
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_gate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VuLds<MAXP_ALL>::BYTES));
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_gate_kernel_2percu), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VuLds<MAXP_SMALL>::BYTES));
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_compact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VuLds<MAXP_ALL>::BYTES));
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_compact_kernel_2percu), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VuLds<MAXP_SMALL>::BYTES));
-        constexpr int long_bytes_attr = (int)VuLds<MAXP_ALL, true>::BYTES;
-        HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_gate_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, long_bytes_attr));
-        attr_set = true;
-    }
     const dim3 grid((unsigned)a.batch, (unsigned)(a.spec_tracks > 0 ? a.spec_tracks : 1));
     if (a.from_rec) {                                        // the gate half of the split form (the caller has launched vu_tri_kernel)
         if (!a.tri_rec || !vu_split_supported(c, a, a.fused)) return HV_ERR_INVALID;
-        static bool rec_attr_dev[64] = {};
-        bool &rec_attr = rec_attr_dev[c->p.device & 63];
-        if (!rec_attr) {
-            constexpr int rec_long_attr = (int)VuRecLds<MAXP_ALL, true>::BYTES;
-            HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_gate_long_rec_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, rec_long_attr));
-            rec_attr = true;
-        }
         constexpr size_t rec_long_bytes = VuRecLds<MAXP_ALL, true>::BYTES, rec_short_bytes = VuRecLds<MAXP_REC>::BYTES;
         if (a.fused == 3) hipLaunchKernelGGL(vu_gate_long_rec_kernel, grid, dim3(VT_LATENCY), rec_long_bytes, stream, a);
         else              hipLaunchKernelGGL(vu_gate_rec_kernel, grid, dim3(VT_REC), rec_short_bytes, stream, a);
@@ -1782,12 +1777,6 @@ int launch_vu_prepare(Ctx *c, const VuPrepareArgs &a, hipStream_t stream)
     }
     if (a.map_index) {                                       // hybrid-map tracks: the dense-H build with the map branch
         if (a.fused || a.map_base < 0) return HV_ERR_INVALID;
-        static bool map_attr_dev[64] = {};
-        bool &map_attr = map_attr_dev[c->p.device & 63];
-        if (!map_attr) {
-            HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(vu_prepare_map_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VuLds<MAXP_ALL>::BYTES));
-            map_attr = true;
-        }
         hipLaunchKernelGGL(vu_prepare_map_kernel, grid, dim3(VT_LATENCY), VuLds<MAXP_ALL>::BYTES, stream, a);
     } else
     if (a.fused == 3) {
