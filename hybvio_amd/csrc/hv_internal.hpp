@@ -244,8 +244,15 @@ struct VuPrepareArgs {
     // gate kernels launched with from_rec = 1 start from that record instead of running the front themselves, in a third of the LDS
     double *tri_rec; int tri_stride; int from_rec;
 };
-// doubles per factor record of vu_tri_kernel for tracks of up to np poses on ncam cameras
-inline int vu_tri_rec_stride(int np, int ncam) { return 17 * np * ncam + 21 * np + 4; }
+// the factor record of vu_tri_kernel for tracks of up to np poses on ncam cameras, in doubles:
+// [np * ncam][POSE] per-pose values of prepareVisualUpdate | [np][21] summed point derivatives | the time-shift column [3] | prep status
+struct VuTriRec {
+    static constexpr int POSE = 17;
+    int dpf, sft, prep, stride;        // offsets of the three tails; doubles per record
+    __host__ __device__ constexpr VuTriRec(int np, int nt) : dpf(POSE * nt), sft(dpf + 21 * np), prep(sft + 3), stride(prep + 1) {}
+};
+static_assert(VuTriRec(21, 42).stride == 17 * 21 * 2 + 21 * 21 + 4 && VuTriRec(5, 5).stride == 17 * 5 + 21 * 5 + 4, "stride(np, ncam) = 17 np ncam + 21 np + 4");
+inline int vu_tri_rec_stride(int np, int ncam) { return VuTriRec(np, np * ncam).stride; }
 template <class K> inline hipError_t set_lds_limit(K kernel, size_t bytes)      // a kernel's dynamic-LDS limit (per device; the *_init functions below)
 {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);

@@ -372,6 +372,85 @@ struct VuRecLds {
 // (LDS is handed out in granules of 1280 bytes, 128 per CU: three workgroups get 42 each; 32 bytes of static LDS ride along -- gate_turn_lds)
 static_assert(VuRecLds<MAXP_REC>::BYTES + 32 <= 42 * 1280, "three record-fed short-class gates per CU");
 
+// prepareVisualUpdate, the part per trail pose (triangulation.cpp:897-947): dip R (2x3) -> o[0..5], the own-orientation block
+// dip dRpt (2x4) -> o[6..13], f -> o[14..15], the depth class -> o[16]
+__device__ __forceinline__ void prepare_pose_part(const double *pose, const double *pfw, double *o)
+{
+    const double pt[3] = {pfw[0] - pose[0], pfw[1] - pose[1], pfw[2] - pose[2]};
+    double pfc[3], ipH[3], dip[9];
+    mv3(pose + 3, pt, pfc);
+    inverse_depth(pfc, ipH, dip);
+    o[16] = pfc[2] == 0 ? 1.0 : pfc[2] < 0 ? 2.0 : 0.0;
+    o[14] = ipH[0]; o[15] = ipH[1];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[3 * r + c] = dip[3 * r] * pose[3 + c] + dip[3 * r + 1] * pose[6 + c] + dip[3 * r + 2] * pose[9 + c];
+#pragma unroll
+    for (int jq = 0; jq < 4; ++jq) {
+        const double *dR = pose + 12 + 9 * jq;
+        double a1[3], b1[3], b2[3];
+        mv3(dR, pt, a1);
+        mTv3(dR, pose + 48, b1);
+        mv3(pose + 3, b1, b2);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) o[6 + 4 * r + jq] = dip[3 * r] * (a1[0] + b2[0]) + dip[3 * r + 1] * (a1[1] + b2[1]) + dip[3 * r + 2] * (a1[2] + b2[2]);
+    }
+}
+
+// ---- phase 1, admission: class filter, "no track", quota used, speculative cursor / epoch. true: the record is final already or
+// another launch's -- the workgroup leaves ----
+__device__ __forceinline__ bool vu_admission(const VuPrepareArgs &a, const int b, const size_t rec, const int np_rec, const bool no_track)
+{
+    const int tid = threadIdx.x;
+    const bool quota_used = a.success_counter && a.success_counter[b] >= a.max_successful;
+    if (a.spec_tracks > 0) {
+        if ((int)blockIdx.y < a.cursor[b]) return true;                               // final already
+        if (!quota_used && a.epoch[rec] == a.success_counter[b]) return true;          // prepared against the current mean
+    }
+    // The two class exits leave every output to the launch of the record's own class -- except `active`, cleared where the caller asks
+    // for it, and the long list
+    if (a.np_hi > 0 && np_rec >= 2 && np_rec <= a.np && (np_rec < a.np_lo || np_rec > a.np_hi)) {       // another length class serves this record
+        if (tid == 0) {
+            if (a.class_inactive && a.active) a.active[rec] = 0;
+            if (a.long_list && np_rec > a.np_hi) a.long_list[atomicAdd(a.long_count, 1)] = (int)rec;
+        }
+        return true;
+    }
+    if (a.np_hi > 0 && a.np_lo > 2 && no_track) {                 // "no track" records belong to the class that starts at 2 poses
+        if (a.class_inactive && a.active && tid == 0) a.active[rec] = 0;
+        return true;
+    }
+    if (quota_used) {
+        // backend.cpp:1233-1238: the frame's quota of successful visual updates is used up, the loop does not visit this track.
+        // Unlike the "no track" exit below it leaves rows_out and epoch alone: nothing was prepared, and a used-up quota stays used up
+        if (tid == 0) {
+            a.status[2 * rec] = HV_TRI_NOT_VISITED; a.status[2 * rec + 1] = HV_TRI_NOT_VISITED;
+            if (a.active) a.active[rec] = 0;
+            if (a.gate_status) a.gate_status[rec] = 1;
+            // a speculative pass may have left a gate result of an earlier (m, P) here: the sequential loop never visits this track
+            if (a.spec_tracks > 0) {
+                if (a.chi2) a.chi2[rec] = 0.0;
+                a.pf[3 * rec] = 0.0; a.pf[3 * rec + 1] = 0.0; a.pf[3 * rec + 2] = 0.0;
+            }
+        }
+        return true;
+    }
+    if (no_track) {
+        // Unlike the quota exit it leaves chi2 and pf alone (nothing of this record was ever computed) and settles rows_out and epoch:
+        // no rows, final whatever the mean becomes
+        if (tid == 0) {
+            a.status[2 * rec] = HV_TRI_NOT_VISITED; a.status[2 * rec + 1] = HV_TRI_NOT_VISITED;
+            if (a.active) a.active[rec] = 0;
+            if (a.gate_status) a.gate_status[rec] = 1;
+            if (a.rows_out) a.rows_out[rec] = 0;
+            if (a.spec_tracks > 0) a.epoch[rec] = a.success_counter[b];
+        }
+        return true;
+    }
+    return false;
+}
+
 // MAXP (camera poses the LDS arrays are sized for) is a template parameter next to VT: <768, 42> holds every track (151 KB of LDS,
 // one workgroup per CU); <384, 22> holds the common sizes in 75 KB and 6 waves of 138 VGPRs, so TWO filters share a CU and one's
 // serial sections (pose records, 3 x 3 solves, barriers: most of the kernel since r02 took the column work off the critical path)
@@ -406,7 +485,9 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
     int *s_idx = reinterpret_cast<int *>(vu_lds + Lay::INTS);      // [MAXNP + 3]
     int *s_flag = s_idx + MAXNP + 3;                               // [4]
     const int b = bx, tid = threadIdx.x;
-    // rec is computed below; a.np is the record STRIDE (the longest track of the launch) when per-record lengths are given
+    // a.np is the record STRIDE (the longest track of the launch) when per-record lengths are given
+    // rec_ is rec (below), spelt twice on purpose: with one value the compiler keeps it live across the loads in between and schedules
+    // every build differently (profiles/vu_phases/README.md)
     const size_t rec_ = a.spec_tracks > 0 ? (size_t)blockIdx.y * a.batch + bx : (size_t)bx;
     const int np_rec = a.np_rec ? a.np_rec[rec_] : a.np;
     const bool no_track = np_rec < 2 || np_rec > a.np;              // ragged batches: this filter has no (valid) track in this launch
@@ -419,46 +500,7 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
     VU_STAMP(0);
     // rec: the (track, filter) record this workgroup reads its inputs from and writes its outputs to (the filter itself without speculation)
     const size_t rec = a.spec_tracks > 0 ? (size_t)blockIdx.y * a.batch + b : (size_t)b;
-    const bool quota_used = a.success_counter && a.success_counter[b] >= a.max_successful;
-    if (a.spec_tracks > 0) {
-        if ((int)blockIdx.y < a.cursor[b]) return;                               // final already
-        if (!quota_used && a.epoch[rec] == a.success_counter[b]) return;          // prepared against the current mean
-    }
-    if (a.np_hi > 0 && np_rec >= 2 && np_rec <= a.np && (np_rec < a.np_lo || np_rec > a.np_hi)) {       // another length class serves this record
-        if (tid == 0) {
-            if (a.class_inactive && a.active) a.active[rec] = 0;
-            if (a.long_list && np_rec > a.np_hi) a.long_list[atomicAdd(a.long_count, 1)] = (int)rec;
-        }
-        return;
-    }
-    if (a.np_hi > 0 && a.np_lo > 2 && no_track) {                 // "no track" records belong to the class that starts at 2 poses
-        if (a.class_inactive && a.active && tid == 0) a.active[rec] = 0;
-        return;
-    }
-    if (quota_used) {
-        // backend.cpp:1233-1238: the frame's quota of successful visual updates is used up, the loop does not visit this track
-        if (tid == 0) {
-            a.status[2 * rec] = HV_TRI_NOT_VISITED; a.status[2 * rec + 1] = HV_TRI_NOT_VISITED;
-            if (a.active) a.active[rec] = 0;
-            if (a.gate_status) a.gate_status[rec] = 1;
-            // a speculative pass may have left a gate result of an earlier (m, P) here: the sequential loop never visits this track
-            if (a.spec_tracks > 0) {
-                if (a.chi2) a.chi2[rec] = 0.0;
-                a.pf[3 * rec] = 0.0; a.pf[3 * rec + 1] = 0.0; a.pf[3 * rec + 2] = 0.0;
-            }
-        }
-        return;
-    }
-    if (no_track) {
-        if (tid == 0) {
-            a.status[2 * rec] = HV_TRI_NOT_VISITED; a.status[2 * rec + 1] = HV_TRI_NOT_VISITED;
-            if (a.active) a.active[rec] = 0;
-            if (a.gate_status) a.gate_status[rec] = 1;
-            if (a.rows_out) a.rows_out[rec] = 0;
-            if (a.spec_tracks > 0) a.epoch[rec] = a.success_counter[b];
-        }
-        return;
-    }
+    if (vu_admission(a, b, rec, np_rec, no_track)) return;                   // 1
     if (tid == 0 && a.rows_out) a.rows_out[rec] = 2 * nt;
     if (tid < n) s_idx[tid] = a.pose_index[rec * a.np + tid];
     if (tid < nt) {
@@ -474,401 +516,375 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
     const double *p0 = s_trail;
     bool map_track = false; int map_off = 0;
     if constexpr (REC) {
-        // the record vu_tri_kernel left for this track: [nt_max][17] per-pose values, [np][21] dpf, the time-shift column, prep
+        // the record vu_tri_kernel left for this track (VuTriRec): per-pose values, dpf, the time-shift column, prep
         const double *recp = a.tri_rec + rec * (size_t)a.tri_stride;
-        const int R_DPF = 17 * nt_max, R_SFT = R_DPF + 21 * a.np;
+        const VuTriRec R(a.np, nt_max);
         status = a.status[2 * rec];
-        for (int w = tid; w < 17 * nt; w += VT) { const int i = w / 17, k = w - 17 * i; s_it[i * ITER_WORDS + k] = recp[w]; }
+        for (int w = tid; w < VuTriRec::POSE * nt; w += VT) { const int i = w / VuTriRec::POSE, k = w - VuTriRec::POSE * i; s_it[i * ITER_WORDS + k] = recp[w]; }
         if (status == HV_TRI_OK) {
-            for (int w = tid; w < 21 * n; w += VT) s_dpf[w] = recp[R_DPF + w];
-            if (tid < 3) s_dpfi[tid] = recp[R_SFT + tid];
+            for (int w = tid; w < 21 * n; w += VT) s_dpf[w] = recp[R.dpf + w];
+            if (tid < 3) s_dpfi[tid] = recp[R.sft + tid];
         }
         if (tid < 3) pfw[tid] = a.pf[3 * rec + tid];
         __syncthreads();
     } else {
-    __syncthreads();
-    // ---- extractCameraPoseTrail (triangulation.cpp:65-103): pose k of camera c from the mean ----
-    if (tid < nt) trail_pose_record(a, m, s_idx, tid, n, s_trail + tid * POSE_WORDS);
-    for (int i = tid; i < 3 * ncol; i += VT) s_dpfi[i] = 0.0;
-    __syncthreads();
-    VU_STAMP(1);
-    if constexpr (MAP) {
-        const int mi = a.map_index ? a.map_index[rec] : -1;
-        map_track = mi >= 0; map_off = a.map_base + 3 * mi;
-    }
-    if (MAP && map_track) {
-        // mapPointUpdate (backend.cpp:1075-1082): the point IS a state, nothing to triangulate, no derivative of it w.r.t. the poses
-        if (tid < 3) pfw[tid] = m[map_off + tid];
-        if (tid == 0) { s_flag[1] = HV_TRI_HYBRID; s_flag[2] = 0; }
-    } else
-    if (a.linear) {
-        // ---- useLinearTriangulation (triangulation.cpp:146-152, triangulateLinear :820-895): the point closest to every camera
-        // ray in closed form, pf = S0^-1 S1 with S0 = sum_i A_i, S1 = sum_i A_i p_i, A_i = I - vn_i vn_i', vn_i the normalised
-        // world ray R_i' (ip_i, 1); derivatives d pf / d p_i = S0^-1 A_i, d pf / d q_i through vn_i, d pf / d t through the
-        // feature velocities. World frame from the start: no inverse-depth map, no iteration, statuses OK / BEHIND only. ----
-        double *Sinv = s_small + 40;                          // the slot the iterative branch uses for M
-        if (tid < nt) {
-            const double *pose = s_trail + tid * POSE_WORDS;
-            double *o = s_it + tid * ITER_WORDS;              // vn[3] |v| A[9] (A p)[3], later the time-shift contribution in [16..18]
-            const double ipv[3] = {s_feat[4 * tid], s_feat[4 * tid + 1], 1.0};
-            double v[3], A[9], Ap[3];
-            mTv3(pose + 3, ipv, v);
-            const double nn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            const double vn[3] = {v[0] / nn, v[1] / nn, v[2] / nn};
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) A[3 * r + c] = (r == c ? 1.0 : 0.0) - vn[r] * vn[c];
-            mv3(A, pose, Ap);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { o[k] = vn[k]; o[13 + k] = Ap[k]; }
-            o[3] = nn;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) o[4 + k] = A[k];
-        }
         __syncthreads();
-        if (tid == 0) {
-            double S0[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, S1[3] = {0, 0, 0};
-            for (int i = 0; i < nt; ++i) {
-                const double *o = s_it + i * ITER_WORDS;
+        // ---- extractCameraPoseTrail (triangulation.cpp:65-103): pose k of camera c from the mean ----
+        if (tid < nt) trail_pose_record(a, m, s_idx, tid, n, s_trail + tid * POSE_WORDS);
+        for (int i = tid; i < 3 * ncol; i += VT) s_dpfi[i] = 0.0;
+        __syncthreads();
+        VU_STAMP(1);
+        if constexpr (MAP) {
+            const int mi = a.map_index ? a.map_index[rec] : -1;
+            map_track = mi >= 0; map_off = a.map_base + 3 * mi;
+        }
+        if (MAP && map_track) {
+            // mapPointUpdate (backend.cpp:1075-1082): the point IS a state, nothing to triangulate, no derivative of it w.r.t. the poses
+            if (tid < 3) pfw[tid] = m[map_off + tid];
+            if (tid == 0) { s_flag[1] = HV_TRI_HYBRID; s_flag[2] = 0; }
+        } else if (a.linear) {
+            // ---- useLinearTriangulation (triangulation.cpp:146-152, triangulateLinear :820-895): the point closest to every camera
+            // ray in closed form, pf = S0^-1 S1 with S0 = sum_i A_i, S1 = sum_i A_i p_i, A_i = I - vn_i vn_i', vn_i the normalised
+            // world ray R_i' (ip_i, 1); derivatives d pf / d p_i = S0^-1 A_i, d pf / d q_i through vn_i, d pf / d t through the
+            // feature velocities. World frame from the start: no inverse-depth map, no iteration, statuses OK / BEHIND only. ----
+            double *Sinv = s_small + 40;                          // the slot the iterative branch uses for M
+            if (tid < nt) {
+                const double *pose = s_trail + tid * POSE_WORDS;
+                double *o = s_it + tid * ITER_WORDS;              // vn[3] |v| A[9] (A p)[3], later the time-shift contribution in [16..18]
+                const double ipv[3] = {s_feat[4 * tid], s_feat[4 * tid + 1], 1.0};
+                double v[3], A[9], Ap[3];
+                mTv3(pose + 3, ipv, v);
+                const double nn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+                const double vn[3] = {v[0] / nn, v[1] / nn, v[2] / nn};
 #pragma unroll
-                for (int k = 0; k < 9; ++k) S0[k] += o[4 + k];
+                for (int r = 0; r < 3; ++r)
 #pragma unroll
-                for (int k = 0; k < 3; ++k) S1[k] += o[13 + k];
+                    for (int c = 0; c < 3; ++c) A[3 * r + c] = (r == c ? 1.0 : 0.0) - vn[r] * vn[c];
+                mv3(A, pose, Ap);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { o[k] = vn[k]; o[13 + k] = Ap[k]; }
+                o[3] = nn;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) o[4 + k] = A[k];
             }
-            // 3 x 3 inverse through the cofactors of the first column (what Eigen's fixed-size inverse does)
-            const double c0 = S0[4] * S0[8] - S0[5] * S0[7], c1 = S0[2] * S0[7] - S0[1] * S0[8], c2 = S0[1] * S0[5] - S0[2] * S0[4];
-            const double invdet = 1.0 / (c0 * S0[0] + c1 * S0[3] + c2 * S0[6]);
-            const double inv[9] = { c0 * invdet, c1 * invdet, c2 * invdet,
-                                    (S0[5] * S0[6] - S0[3] * S0[8]) * invdet, (S0[0] * S0[8] - S0[2] * S0[6]) * invdet, (S0[2] * S0[3] - S0[0] * S0[5]) * invdet,
-                                    (S0[3] * S0[7] - S0[4] * S0[6]) * invdet, (S0[1] * S0[6] - S0[0] * S0[7]) * invdet, (S0[0] * S0[4] - S0[1] * S0[3]) * invdet };
-            double pf[3];
-            mv3(inv, S1, pf);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) Sinv[k] = inv[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pfw[k] = pf[k];
-        }
-        __syncthreads();
-        // item (pose i, c): c < 3 column c of S0^-1 A_i; c = 3..6 the quaternion components; c = 7 the pose's share of d pf / d t
-        for (int w = tid; w < nt * 8; w += VT) {
-            const int i = w >> 3, c = w & 7;
-            const double *pose = s_trail + i * POSE_WORDS;
-            double *o = s_it + i * ITER_WORDS;
-            double col[3];
-            if (c < 3) {
-#pragma unroll
-                for (int r = 0; r < 3; ++r) col[r] = Sinv[3 * r] * o[4 + c] + Sinv[3 * r + 1] * o[4 + 3 + c] + Sinv[3 * r + 2] * o[4 + 6 + c];
-            } else {
-                // dv: the change of the un-normalised ray; g = d vn = A dv / |v|; d pf = S0^-1 (sum_k g_k Q_k) (pf - p_i) with
-                // Q_k x = e_k (vn . x) + vn x_k, i.e. (sum_k g_k Q_k) x = g (vn . x) + vn (g . x)
-                double dv[3];
-                if (c < 7) { const double ipv[3] = {s_feat[4 * i], s_feat[4 * i + 1], 1.0}; mTv3(pose + 12 + 9 * (c - 3), ipv, dv); }
-                else { const double vel[3] = {s_feat[4 * i + 2], s_feat[4 * i + 3], 0.0}; mTv3(pose + 3, vel, dv); }
-                double g[3];
-                mv3(o + 4, dv, g);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) g[k] /= o[3];
-                const double x[3] = {pfw[0] - pose[0], pfw[1] - pose[1], pfw[2] - pose[2]};
-                const double vx = o[0] * x[0] + o[1] * x[1] + o[2] * x[2], gx = g[0] * x[0] + g[1] * x[1] + g[2] * x[2];
-                const double u[3] = {g[0] * vx + o[0] * gx, g[1] * vx + o[1] * gx, g[2] * vx + o[2] * gx};
-                mv3(Sinv, u, col);
-            }
-            if (c < 7) {
-#pragma unroll
-                for (int r = 0; r < 3; ++r) s_dpfi[r * ncol + 7 * i + c] = col[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < 3; ++r) o[16 + r] = col[r];
-            }
-        }
-        __syncthreads();
-        if (tid < 3 && a.est_shift) {                         // d pf / d t: the poses' shares in pose order
-            double t_ = 0.0;
-            for (int i = 0; i < nt; ++i) t_ += s_it[i * ITER_WORDS + 16 + tid];
-            s_dpfi[tid * ncol + dDim] = t_;
-        }
-        if (tid == 0) s_flag[0] = 1;
-        __syncthreads();
-    } else {
-    // ---- triangulateWithTwoCameras between pose 0 and pose ind1 (triangulation.cpp:154-173, 612-716): thread j < 15
-    // owns derivative column j (p0 q0 p1 q1 t); every one of them recomputes the small shared part ----
-    const int ind1 = a.stereo ? nt / 2 - 1 : nt - 1;
-    if (tid < 15) two_camera_start(a, tid, ind1, ncol, dDim, s_trail, s_feat, s_dpfi, pfi, pfw, R0T, scal, s_flag);
-    __syncthreads();
-    // ---- Gauss-Newton with derivatives (triangulation.cpp:206-343) ----
-    // Lanes of the derivative-column phase. Every (pose i, column j) pair contributes through d(pfi)/dx_j (the plain
-    // part); a pair also moves C and t of the pose when j belongs to pose i or to pose 0 (the motion part, ~2.5x the
-    // flops). Both parts are linear in their inputs, so they are summed separately:
-    //   plain part  : G = 2 or 4 adjacent lanes per column walk the poses (stride G), no branch in the loop
-    //   motion part : the 7 (2 nt - 1) such pairs are dealt out one (or two) per lane in a single uniform step --
-    //                 lane 0 of a column's group takes the column's own pair, the other lanes take the pairs of the
-    //                 7 pose-0 columns, whose sums go through LDS in a fixed order.
-    // (With a branch inside the loop the wave holding the pose-0 columns took 16.9 k of an iteration's 19 k cycles.)
-    // The last wave (VT - 64 ..) forms ETE / Eerror / the step concurrently.
-    // The motion pairs are dealt out densely, one per lane, to as few waves as hold them -- and to waves chosen by the SIMD they
-    // sit on (wave w runs on SIMD w % 4): the column waves 0 .. 8 already load SIMD 0 with three waves of plain work, so the
-    // pairs go to the two idle waves 9, 10 first, then to waves of SIMDs 1 - 3. (r01 gave every column lane a pair, own or
-    // dummy: the motion code ran on all 9 column waves at 25 - 75 % lane use.) Pair slot ms -> pose, state component:
-    //   ms < 7 nt: pose-0 column  (i = ms / 7, comp = ms % 7, sums through s_p0);  else the own pair of column j = ms - 7 nt + 7.
-    constexpr unsigned long long WAVE_POS = VT == 768 ? 0xF10A43297658ull : 0xF42103ull;   // nibble w = position of wave w in that order
-    const int wpos = (int)((WAVE_POS >> (4 * (tid >> 6))) & 0xF);
-    const int ms = wpos * 64 + (tid & 63), npairs = 14 * nt - 7;
-    const bool m_has = wpos != 0xF && ms < npairs, m_p0pair = ms < 7 * nt;
-    const int m_col = m_p0pair ? ms : ms - 7 * nt + 7;                       // p0 pairs: u = 7 i + comp;  own pairs: the column
-    const int m_i = m_col / 7, m_comp = m_col - 7 * m_i;
-    if (m_has) {
-        double dC[9], dt[3];
-        pose_motion(s_trail, R0T, m_i, m_p0pair ? 0 : m_i, m_comp, dC, dt);
-        double *dst = s_mot + ms * MOT_STRIDE;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) dst[k] = dC[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) dst[9 + k] = dt[k];
-    }
-    VU_STAMP(2);
-    for (int it = 0; it < a.gn_iters; ++it) {
-        if (it < 6) VU_STAMP(3 + 4 * it);
-        if (tid < nt) {                                       // per-pose quantities of this iteration
-            const double *cur = s_trail + tid * POSE_WORDS;
-            double *o = s_it + tid * ITER_WORDS;
-            double C[9], t[3], d[3], h[3];
-            mm3(cur + 3, R0T, C);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) d[k] = p0[k] - cur[k];
-            mv3(cur + 3, d, t);
-            const double pfiab[3] = {pfi[0], pfi[1], 1.0};
-            mv3(C, pfiab, h);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) h[k] += pfi[2] * t[k];
-            const double ih2 = 1.0 / h[2], ih2sq = ih2 * ih2;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) o[k] = C[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { o[9 + k] = t[k]; o[12 + k] = h[k]; o[23 + k] = d[k]; }
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-#pragma unroll
-                for (int c = 0; c < 2; ++c) o[15 + 3 * r + c] = -ih2 * C[3 * r + c] + h[r] * ih2sq * C[6 + c];
-                o[15 + 3 * r + 2] = -t[r] * ih2 + h[r] * ih2sq * t[2];
-                o[21 + r] = s_feat[4 * tid + r] - h[r] * ih2;
-            }
-        }
-        __syncthreads();
-        if (it < 6) VU_STAMP(4 + 4 * it);
-        if (tid >= VT - 64) {                                 // the last wave owns no derivative column: it forms ETE (9),
-            const int k = tid - (VT - 64);                    // Eerror (3) and error2 concurrently, lane k < 13 summing entry k
-            // entry k = sum over poses of o[x0]*o[y0] + o[x0+dx]*o[y0+dy] on the pose record (E rows at 15 and 18, err at 21)
-            const int r = k / 3, c = k - 3 * r;
-            const int x0 = k < 9 ? 15 + r : k < 12 ? 15 + (k - 9) : 21, y0 = k < 9 ? 15 + c : 21;
-            const int dx = k < 12 ? 3 : 1, dy = k < 9 ? 3 : 1;
-            double acc = 0.0;
-            if (k < 13)
+            __syncthreads();
+            if (tid == 0) {
+                double S0[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, S1[3] = {0, 0, 0};
                 for (int i = 0; i < nt; ++i) {
                     const double *o = s_it + i * ITER_WORDS;
-                    acc += o[x0] * o[y0] + o[x0 + dx] * o[y0 + dy];
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) S0[k] += o[4 + k];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) S1[k] += o[13 + k];
                 }
-            double ETE[9], Ee[3];
+                // 3 x 3 inverse through the cofactors of the first column (what Eigen's fixed-size inverse does)
+                const double c0 = S0[4] * S0[8] - S0[5] * S0[7], c1 = S0[2] * S0[7] - S0[1] * S0[8], c2 = S0[1] * S0[5] - S0[2] * S0[4];
+                const double invdet = 1.0 / (c0 * S0[0] + c1 * S0[3] + c2 * S0[6]);
+                const double inv[9] = { c0 * invdet, c1 * invdet, c2 * invdet,
+                                        (S0[5] * S0[6] - S0[3] * S0[8]) * invdet, (S0[0] * S0[8] - S0[2] * S0[6]) * invdet, (S0[2] * S0[3] - S0[0] * S0[5]) * invdet,
+                                        (S0[3] * S0[7] - S0[4] * S0[6]) * invdet, (S0[1] * S0[6] - S0[0] * S0[7]) * invdet, (S0[0] * S0[4] - S0[1] * S0[3]) * invdet };
+                double pf[3];
+                mv3(inv, S1, pf);
 #pragma unroll
-            for (int q = 0; q < 9; ++q) ETE[q] = __shfl(acc, q);
+                for (int k = 0; k < 9; ++k) Sinv[k] = inv[k];
 #pragma unroll
-            for (int q = 0; q < 3; ++q) Ee[q] = __shfl(acc, 9 + q);
-            const double e2 = __shfl(acc, 12);
-            if (k == 0) {
-                double Xl[9], st[3];
-                inv3sym(ETE, Xl);
-                mv3(Xl, Ee, st);
-#pragma unroll
-                for (int q = 0; q < 9; ++q) X[q] = Xl[q];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) step[q] = st[q];
-                scal[0] = e2;
-                scal[1] = 1.0 / (norm1_3(ETE) * norm1_3(Xl));
+                for (int k = 0; k < 3; ++k) pfw[k] = pf[k];
             }
-        }
-        if (it < 6) VU_STAMP(5 + 4 * it);
-        // derivative columns: dEerror_j and dETE_j accumulated over the poses, with the OLD pfi (:236-312).
-        // PLAIN part (the change of pfi seen by every pose): dh_i = [C_i(:, 0:2) | t_i] d_j with d_j = column j of dpfi, and everything
-        // downstream of dh is linear in it -- so the sum over the poses is taken ONCE, of the linear maps, not per column:
-        //   task (pose i, unit vector u)  ->  the 3 + 6 numbers (dEe, upper dM) pair_sums gives for dh = column u of [C_i | t_i]   (3 nt lanes)
-        //   L[u][9] = sum over the poses                                                                                         (27 lanes)
-        //   column j:  (dEe_j, dM_j) = L' d_j   (+ the velocity term c_t for the time-shift column)                             (27 FMAs)
-        // r01 walked the poses per column: nt x ~90 f64 instructions in each of 9 waves, the critical path of the kernel.
-        if (tid >= 64 && tid < 64 + 3 * nt) {
-            const int task = tid - 64, i = task / 3, u = task - 3 * i;
-            const double *o = s_it + i * ITER_WORDS;
-            const double dh[3] = {u < 2 ? o[u] : o[9], u < 2 ? o[3 + u] : o[10], u < 2 ? o[6 + u] : o[11]};
-            double e3[3] = {0, 0, 0}, m9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            pair_sums<0>(o, dh, nullptr, nullptr, 0.0, 0.0, e3, m9);
-            double *dst = s_lin + task * 9;
-            dst[0] = e3[0]; dst[1] = e3[1]; dst[2] = e3[2];
-            dst[3] = m9[0]; dst[4] = m9[1]; dst[5] = m9[2]; dst[6] = m9[4]; dst[7] = m9[5]; dst[8] = m9[8];
-        }
-        if (m_has) {                                                                    // motion part: one pair per lane, one code path
-            const double *o = s_it + m_i * ITER_WORDS;
-            double dC[9], dt[3], dh[3], e3[3] = {0, 0, 0}, m9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            const double *mot = s_mot + ms * MOT_STRIDE;
+            __syncthreads();
+            // item (pose i, c): c < 3 column c of S0^-1 A_i; c = 3..6 the quaternion components; c = 7 the pose's share of d pf / d t
+            for (int w = tid; w < nt * 8; w += VT) {
+                const int i = w >> 3, c = w & 7;
+                const double *pose = s_trail + i * POSE_WORDS;
+                double *o = s_it + i * ITER_WORDS;
+                double col[3];
+                if (c < 3) {
 #pragma unroll
-            for (int k = 0; k < 9; ++k) dC[k] = mot[k];
+                    for (int r = 0; r < 3; ++r) col[r] = Sinv[3 * r] * o[4 + c] + Sinv[3 * r + 1] * o[4 + 3 + c] + Sinv[3 * r + 2] * o[4 + 6 + c];
+                } else {
+                    // dv: the change of the un-normalised ray; g = d vn = A dv / |v|; d pf = S0^-1 (sum_k g_k Q_k) (pf - p_i) with
+                    // Q_k x = e_k (vn . x) + vn x_k, i.e. (sum_k g_k Q_k) x = g (vn . x) + vn (g . x)
+                    double dv[3];
+                    if (c < 7) { const double ipv[3] = {s_feat[4 * i], s_feat[4 * i + 1], 1.0}; mTv3(pose + 12 + 9 * (c - 3), ipv, dv); }
+                    else { const double vel[3] = {s_feat[4 * i + 2], s_feat[4 * i + 3], 0.0}; mTv3(pose + 3, vel, dv); }
+                    double g[3];
+                    mv3(o + 4, dv, g);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) dt[k] = mot[9 + k];
+                    for (int k = 0; k < 3; ++k) g[k] /= o[3];
+                    const double x[3] = {pfw[0] - pose[0], pfw[1] - pose[1], pfw[2] - pose[2]};
+                    const double vx = o[0] * x[0] + o[1] * x[1] + o[2] * x[2], gx = g[0] * x[0] + g[1] * x[1] + g[2] * x[2];
+                    const double u[3] = {g[0] * vx + o[0] * gx, g[1] * vx + o[1] * gx, g[2] * vx + o[2] * gx};
+                    mv3(Sinv, u, col);
+                }
+                if (c < 7) {
 #pragma unroll
-            for (int r = 0; r < 3; ++r) dh[r] = (dC[3 * r] * pfi[0] + dC[3 * r + 1] * pfi[1] + dC[3 * r + 2]) + pfi[2] * dt[r];
-            pair_sums<1>(o, dh, dC, dt, 0.0, 0.0, e3, m9);
-            double *dst = m_p0pair ? s_p0 + (m_comp * MAXP + m_i) * 9 : s_own + m_col * 9;
-            dst[0] = e3[0]; dst[1] = e3[1]; dst[2] = e3[2];
-            dst[3] = m9[0]; dst[4] = m9[1]; dst[5] = m9[2]; dst[6] = m9[4]; dst[7] = m9[5]; dst[8] = m9[8];
-        }
-        __syncthreads();                                      // X, step, error2 are published; everybody is done with the old pfi
-        if (it < 6) VU_STAMP(6 + 4 * it);
-        // 93 sums over the poses, LPS adjacent lanes each (a lane per sum walked nt dependent LDS reads + adds: 1.4 k cycles):
-        //   sigma < 63       pose-0 columns: entry e of column c, motion part            -> totals at s_p0 + 7 MAXP 9
-        //   63 <= sigma < 90 L[u][e]: the linear maps of the plain part                  -> s_lin + 3 MAXP 9
-        //   90 <= sigma < 93 c_t = sum_i E_i' vel_i: the constant of the time-shift column -> s_lin + 3 MAXP 9 + 27
-        constexpr int LPS = VT >= 768 ? 4 : 2;
-        if (tid >= 64 && tid < 64 + 93 * LPS) {
-            const int g = tid - 64, sigma = g / LPS, part = g - sigma * LPS;
-            double acc = 0.0;
-            if (sigma < 63) {
-                const int c = sigma / 9, e = sigma - 9 * c;
-                for (int q = part; q < nt; q += LPS) acc += s_p0[(c * MAXP + q) * 9 + e];
-            } else if (sigma < 90) {
-                const int u = (sigma - 63) / 9, e = sigma - 63 - 9 * u;
-                for (int q = part; q < nt; q += LPS) acc += s_lin[(3 * q + u) * 9 + e];
-            } else {
-                const int r = sigma - 90;
-                for (int q = part; q < nt; q += LPS)
-                    acc += s_it[q * ITER_WORDS + 15 + r] * s_feat[4 * q + 2] + s_it[q * ITER_WORDS + 18 + r] * s_feat[4 * q + 3];
+                    for (int r = 0; r < 3; ++r) s_dpfi[r * ncol + 7 * i + c] = col[r];
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) o[16 + r] = col[r];
+                }
             }
-#pragma unroll
-            for (int o = 1; o < LPS; o <<= 1) acc += __shfl_xor(acc, o);
-            if (part == 0) {
-                if (sigma < 63) s_p0[7 * MAXP * 9 + sigma] = acc;
-                else s_lin[3 * MAXP * 9 + sigma - 63] = acc;
+            __syncthreads();
+            if (tid < 3 && a.est_shift) {                         // d pf / d t: the poses' shares in pose order
+                double t_ = 0.0;
+                for (int i = 0; i < nt; ++i) t_ += s_it[i * ITER_WORDS + 16 + tid];
+                s_dpfi[tid * ncol + dDim] = t_;
             }
+            if (tid == 0) s_flag[0] = 1;
+            __syncthreads();
+        } else {
+            // ---- triangulateWithTwoCameras between pose 0 and pose ind1 (triangulation.cpp:154-173, 612-716): thread j < 15
+            // owns derivative column j (p0 q0 p1 q1 t); every one of them recomputes the small shared part ----
+            const int ind1 = a.stereo ? nt / 2 - 1 : nt - 1;
+            if (tid < 15) two_camera_start(a, tid, ind1, ncol, dDim, s_trail, s_feat, s_dpfi, pfi, pfw, R0T, scal, s_flag);
+            __syncthreads();
+            // ---- Gauss-Newton with derivatives (triangulation.cpp:206-343) ----
+            // Lanes of the derivative-column phase. Every (pose i, column j) pair contributes through d(pfi)/dx_j (the plain
+            // part); a pair also moves C and t of the pose when j belongs to pose i or to pose 0 (the motion part, ~2.5x the
+            // flops). Both parts are linear in their inputs, so they are summed separately:
+            //   plain part  : G = 2 or 4 adjacent lanes per column walk the poses (stride G), no branch in the loop
+            //   motion part : the 7 (2 nt - 1) such pairs are dealt out one (or two) per lane in a single uniform step --
+            //                 lane 0 of a column's group takes the column's own pair, the other lanes take the pairs of the
+            //                 7 pose-0 columns, whose sums go through LDS in a fixed order.
+            // (With a branch inside the loop the wave holding the pose-0 columns took 16.9 k of an iteration's 19 k cycles.)
+            // The last wave (VT - 64 ..) forms ETE / Eerror / the step concurrently.
+            // The motion pairs are dealt out densely, one per lane, to as few waves as hold them -- and to waves chosen by the SIMD they
+            // sit on (wave w runs on SIMD w % 4): the column waves 0 .. 8 already load SIMD 0 with three waves of plain work, so the
+            // pairs go to the two idle waves 9, 10 first, then to waves of SIMDs 1 - 3. (r01 gave every column lane a pair, own or
+            // dummy: the motion code ran on all 9 column waves at 25 - 75 % lane use.) Pair slot ms -> pose, state component:
+            //   ms < 7 nt: pose-0 column  (i = ms / 7, comp = ms % 7, sums through s_p0);  else the own pair of column j = ms - 7 nt + 7.
+            constexpr unsigned long long WAVE_POS = VT == 768 ? 0xF10A43297658ull : 0xF42103ull;   // nibble w = position of wave w in that order
+            const int wpos = (int)((WAVE_POS >> (4 * (tid >> 6))) & 0xF);
+            const int ms = wpos * 64 + (tid & 63), npairs = 14 * nt - 7;
+            const bool m_has = wpos != 0xF && ms < npairs, m_p0pair = ms < 7 * nt;
+            const int m_col = m_p0pair ? ms : ms - 7 * nt + 7;                       // p0 pairs: u = 7 i + comp;  own pairs: the column
+            const int m_i = m_col / 7, m_comp = m_col - 7 * m_i;
+            if (m_has) {
+                double dC[9], dt[3];
+                pose_motion(s_trail, R0T, m_i, m_p0pair ? 0 : m_i, m_comp, dC, dt);
+                double *dst = s_mot + ms * MOT_STRIDE;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) dst[k] = dC[k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dst[9 + k] = dt[k];
+            }
+            VU_STAMP(2);
+            for (int it = 0; it < a.gn_iters; ++it) {
+                if (it < 6) VU_STAMP(3 + 4 * it);
+                if (tid < nt) {                                       // per-pose quantities of this iteration
+                    const double *cur = s_trail + tid * POSE_WORDS;
+                    double *o = s_it + tid * ITER_WORDS;
+                    double C[9], t[3], d[3], h[3];
+                    mm3(cur + 3, R0T, C);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) d[k] = p0[k] - cur[k];
+                    mv3(cur + 3, d, t);
+                    const double pfiab[3] = {pfi[0], pfi[1], 1.0};
+                    mv3(C, pfiab, h);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) h[k] += pfi[2] * t[k];
+                    const double ih2 = 1.0 / h[2], ih2sq = ih2 * ih2;
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) o[k] = C[k];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) { o[9 + k] = t[k]; o[12 + k] = h[k]; o[23 + k] = d[k]; }
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) o[15 + 3 * r + c] = -ih2 * C[3 * r + c] + h[r] * ih2sq * C[6 + c];
+                        o[15 + 3 * r + 2] = -t[r] * ih2 + h[r] * ih2sq * t[2];
+                        o[21 + r] = s_feat[4 * tid + r] - h[r] * ih2;
+                    }
+                }
+                __syncthreads();
+                if (it < 6) VU_STAMP(4 + 4 * it);
+                if (tid >= VT - 64) {                                 // the last wave owns no derivative column: it forms ETE (9),
+                    const int k = tid - (VT - 64);                    // Eerror (3) and error2 concurrently, lane k < 13 summing entry k
+                    // entry k = sum over poses of o[x0]*o[y0] + o[x0+dx]*o[y0+dy] on the pose record (E rows at 15 and 18, err at 21)
+                    const int r = k / 3, c = k - 3 * r;
+                    const int x0 = k < 9 ? 15 + r : k < 12 ? 15 + (k - 9) : 21, y0 = k < 9 ? 15 + c : 21;
+                    const int dx = k < 12 ? 3 : 1, dy = k < 9 ? 3 : 1;
+                    double acc = 0.0;
+                    if (k < 13)
+                        for (int i = 0; i < nt; ++i) {
+                            const double *o = s_it + i * ITER_WORDS;
+                            acc += o[x0] * o[y0] + o[x0 + dx] * o[y0 + dy];
+                        }
+                    double ETE[9], Ee[3];
+#pragma unroll
+                    for (int q = 0; q < 9; ++q) ETE[q] = __shfl(acc, q);
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) Ee[q] = __shfl(acc, 9 + q);
+                    const double e2 = __shfl(acc, 12);
+                    if (k == 0) {
+                        double Xl[9], st[3];
+                        inv3sym(ETE, Xl);
+                        mv3(Xl, Ee, st);
+#pragma unroll
+                        for (int q = 0; q < 9; ++q) X[q] = Xl[q];
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) step[q] = st[q];
+                        scal[0] = e2;
+                        scal[1] = 1.0 / (norm1_3(ETE) * norm1_3(Xl));
+                    }
+                }
+                if (it < 6) VU_STAMP(5 + 4 * it);
+                // derivative columns: dEerror_j and dETE_j accumulated over the poses, with the OLD pfi (:236-312).
+                // PLAIN part (the change of pfi seen by every pose): dh_i = [C_i(:, 0:2) | t_i] d_j with d_j = column j of dpfi, and everything
+                // downstream of dh is linear in it -- so the sum over the poses is taken ONCE, of the linear maps, not per column:
+                //   task (pose i, unit vector u)  ->  the 3 + 6 numbers (dEe, upper dM) pair_sums gives for dh = column u of [C_i | t_i]   (3 nt lanes)
+                //   L[u][9] = sum over the poses                                                                                         (27 lanes)
+                //   column j:  (dEe_j, dM_j) = L' d_j   (+ the velocity term c_t for the time-shift column)                             (27 FMAs)
+                // r01 walked the poses per column: nt x ~90 f64 instructions in each of 9 waves, the critical path of the kernel.
+                if (tid >= 64 && tid < 64 + 3 * nt) {
+                    const int task = tid - 64, i = task / 3, u = task - 3 * i;
+                    const double *o = s_it + i * ITER_WORDS;
+                    const double dh[3] = {u < 2 ? o[u] : o[9], u < 2 ? o[3 + u] : o[10], u < 2 ? o[6 + u] : o[11]};
+                    double e3[3] = {0, 0, 0}, m9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+                    pair_sums<0>(o, dh, nullptr, nullptr, 0.0, 0.0, e3, m9);
+                    double *dst = s_lin + task * 9;
+                    dst[0] = e3[0]; dst[1] = e3[1]; dst[2] = e3[2];
+                    dst[3] = m9[0]; dst[4] = m9[1]; dst[5] = m9[2]; dst[6] = m9[4]; dst[7] = m9[5]; dst[8] = m9[8];
+                }
+                if (m_has) {                                                                    // motion part: one pair per lane, one code path
+                    const double *o = s_it + m_i * ITER_WORDS;
+                    double dC[9], dt[3], dh[3], e3[3] = {0, 0, 0}, m9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+                    const double *mot = s_mot + ms * MOT_STRIDE;
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) dC[k] = mot[k];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) dt[k] = mot[9 + k];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) dh[r] = (dC[3 * r] * pfi[0] + dC[3 * r + 1] * pfi[1] + dC[3 * r + 2]) + pfi[2] * dt[r];
+                    pair_sums<1>(o, dh, dC, dt, 0.0, 0.0, e3, m9);
+                    double *dst = m_p0pair ? s_p0 + (m_comp * MAXP + m_i) * 9 : s_own + m_col * 9;
+                    dst[0] = e3[0]; dst[1] = e3[1]; dst[2] = e3[2];
+                    dst[3] = m9[0]; dst[4] = m9[1]; dst[5] = m9[2]; dst[6] = m9[4]; dst[7] = m9[5]; dst[8] = m9[8];
+                }
+                __syncthreads();                                      // X, step, error2 are published; everybody is done with the old pfi
+                if (it < 6) VU_STAMP(6 + 4 * it);
+                // 93 sums over the poses, LPS adjacent lanes each (a lane per sum walked nt dependent LDS reads + adds: 1.4 k cycles):
+                //   sigma < 63       pose-0 columns: entry e of column c, motion part            -> totals at s_p0 + 7 MAXP 9
+                //   63 <= sigma < 90 L[u][e]: the linear maps of the plain part                  -> s_lin + 3 MAXP 9
+                //   90 <= sigma < 93 c_t = sum_i E_i' vel_i: the constant of the time-shift column -> s_lin + 3 MAXP 9 + 27
+                constexpr int LPS = VT >= 768 ? 4 : 2;
+                if (tid >= 64 && tid < 64 + 93 * LPS) {
+                    const int g = tid - 64, sigma = g / LPS, part = g - sigma * LPS;
+                    double acc = 0.0;
+                    if (sigma < 63) {
+                        const int c = sigma / 9, e = sigma - 9 * c;
+                        for (int q = part; q < nt; q += LPS) acc += s_p0[(c * MAXP + q) * 9 + e];
+                    } else if (sigma < 90) {
+                        const int u = (sigma - 63) / 9, e = sigma - 63 - 9 * u;
+                        for (int q = part; q < nt; q += LPS) acc += s_lin[(3 * q + u) * 9 + e];
+                    } else {
+                        const int r = sigma - 90;
+                        for (int q = part; q < nt; q += LPS)
+                            acc += s_it[q * ITER_WORDS + 15 + r] * s_feat[4 * q + 2] + s_it[q * ITER_WORDS + 18 + r] * s_feat[4 * q + 3];
+                    }
+#pragma unroll
+                    for (int o = 1; o < LPS; o <<= 1) acc += __shfl_xor(acc, o);
+                    if (part == 0) {
+                        if (sigma < 63) s_p0[7 * MAXP * 9 + sigma] = acc;
+                        else s_lin[3 * MAXP * 9 + sigma - 63] = acc;
+                    }
+                }
+                __syncthreads();
+                if (tid < ncol && !(tid == dDim && !a.est_shift)) {   // :324-328: d(A^-1) = -A^-1 dA A^-1, one lane per column
+                    const int j = tid;
+                    const double *Lm = s_lin + 3 * MAXP * 9;
+                    const double d0 = s_dpfi[j], d1 = s_dpfi[ncol + j], d2 = s_dpfi[2 * ncol + j];
+                    double v[9];
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) v[e] = (Lm[e] * d0 + Lm[9 + e] * d1) + Lm[18 + e] * d2;
+                    double dEe[3] = {v[0], v[1], v[2]}, dM[9] = {v[3], v[4], v[5], v[4], v[6], v[7], v[5], v[7], v[8]};
+                    // + the motion sums: the pose-0 totals (columns 0 .. 6), the column's own pair (regular columns), the velocity term (time shift)
+                    const double *add = j < 7 ? s_p0 + 7 * MAXP * 9 + 9 * j : s_own + j * 9;
+                    if (j != dDim) {
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) dEe[k] += add[k];
+                        dM[0] += add[3]; dM[1] += add[4]; dM[2] += add[5]; dM[4] += add[6]; dM[5] += add[7]; dM[8] += add[8];
+                        dM[3] = dM[1]; dM[6] = dM[2]; dM[7] = dM[5];
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) dEe[k] += Lm[27 + k];
+                    }
+                    double t1[3], t2[3], t3[3];
+                    mv3(dM, step, t1);
+                    mv3(X, t1, t2);
+                    mv3(X, dEe, t3);
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) s_dpfi[r * ncol + j] += t2[r] - t3[r];
+                }
+                if (tid == 0) {                                       // :316-342
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) pfi[k] -= step[k];
+                    const double J = 0.5 * scal[0] / (a.conv_r * a.conv_r), Jd = fabs((J - scal[2]) / J);
+                    scal[2] = J;
+                    if (Jd < a.conv_threshold) s_flag[0] = 1;
+                }
+                __syncthreads();
+                if (s_flag[0]) break;
+            }
+        }   // iterative front
+        VU_STAMP(27);
+        // ---- status, back to world coordinates (:345-392) ----
+        double *M = s_small + 40, *pf0 = s_small + 49;           // R0T * dpf0_dpfi, the point in the frame of pose 0
+        if (tid == 0 && !(MAP && map_track)) {
+            int status = HV_TRI_OK;
+            if (a.linear) { /* pfw and the world-frame derivative columns are in place */ }
+            else if (!s_flag[0]) status = HV_TRI_NO_CONVERGENCE;
+            else if (scal[1] < a.rcond_threshold) status = HV_TRI_BAD_COND;
+            if (status == HV_TRI_OK && !a.linear) {
+                double d[9], q[3], w[3], Ml[9];
+                inverse_depth(pfi, q, d);
+                mv3(R0T, q, w);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { pfw[k] = w[k] + p0[k]; pf0[k] = q[k]; }
+                if (pfw[0] == p0[0] && pfw[1] == p0[1] && pfw[2] == p0[2]) status = HV_TRI_UNKNOWN_PROBLEM;
+                mm3(R0T, d, Ml);
+#pragma unroll
+                for (int k = 0; k < 9; ++k) M[k] = Ml[k];
+            }
+            s_flag[1] = status;
+            s_flag[2] = 0;                                        // behind any camera
         }
         __syncthreads();
-        if (tid < ncol && !(tid == dDim && !a.est_shift)) {   // :324-328: d(A^-1) = -A^-1 dA A^-1, one lane per column
-            const int j = tid;
-            const double *Lm = s_lin + 3 * MAXP * 9;
-            const double d0 = s_dpfi[j], d1 = s_dpfi[ncol + j], d2 = s_dpfi[2 * ncol + j];
-            double v[9];
+        status = s_flag[1];
+        if (status == HV_TRI_OK) {
+            if (tid < ncol && !a.linear) {
+                const int j = tid;
+                double u[3] = {0, 0, 0}, v[3];
+                if (j >= 3 && j < 7) mTv3(s_trail + 12 + 9 * (j - 3), pf0, u);                // dR0T * pf0
+                const double cur[3] = {s_dpfi[j], s_dpfi[ncol + j], s_dpfi[2 * ncol + j]};
+                mv3(M, cur, v);
 #pragma unroll
-            for (int e = 0; e < 9; ++e) v[e] = (Lm[e] * d0 + Lm[9 + e] * d1) + Lm[18 + e] * d2;
-            double dEe[3] = {v[0], v[1], v[2]}, dM[9] = {v[3], v[4], v[5], v[4], v[6], v[7], v[5], v[7], v[8]};
-            // + the motion sums: the pose-0 totals (columns 0 .. 6), the column's own pair (regular columns), the velocity term (time shift)
-            const double *add = j < 7 ? s_p0 + 7 * MAXP * 9 + 9 * j : s_own + j * 9;
-            if (j != dDim) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) dEe[k] += add[k];
-                dM[0] += add[3]; dM[1] += add[4]; dM[2] += add[5]; dM[4] += add[6]; dM[5] += add[7]; dM[8] += add[8];
-                dM[3] = dM[1]; dM[6] = dM[2]; dM[7] = dM[5];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) dEe[k] += Lm[27 + k];
+                for (int r = 0; r < 3; ++r) s_dpfi[r * ncol + j] = u[r] + v[r] + (j == r ? 1.0 : 0.0);      // dp0 = e_j for j < 3 (r < 3, so j == r implies it)
             }
-            double t1[3], t2[3], t3[3];
-            mv3(dM, step, t1);
-            mv3(X, t1, t2);
-            mv3(X, dEe, t3);
-#pragma unroll
-            for (int r = 0; r < 3; ++r) s_dpfi[r * ncol + j] += t2[r] - t3[r];
+            if (tid < nt) {                                       // isBehind (:54-60)
+                const double *cur = s_trail + tid * POSE_WORDS;
+                const double d[3] = {pfw[0] - cur[0], pfw[1] - cur[1], pfw[2] - cur[2]};
+                if (cur[9] * d[0] + cur[10] * d[1] + cur[11] * d[2] < 0) atomicOr(&s_flag[2], 1);
+            }
+            __syncthreads();
+            if (s_flag[2]) status = HV_TRI_BEHIND;
         }
-        if (tid == 0) {                                       // :316-342
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pfi[k] -= step[k];
-            const double J = 0.5 * scal[0] / (a.conv_r * a.conv_r), Jd = fabs((J - scal[2]) / J);
-            scal[2] = J;
-            if (Jd < a.conv_threshold) s_flag[0] = 1;
+        if (!(MAP && map_track)) {   // backend.cpp:1098-1102: depth window on whatever point the triangulation left behind
+            const double dx = pfw[0] - p0[0], dy = pfw[1] - p0[1], dz = pfw[2] - p0[2], depth = sqrt(dx * dx + dy * dy + dz * dz);
+            if (depth < a.min_dist || depth > a.max_dist) status = HV_TRI_BAD_DEPTH;
         }
+        with_derivatives = status == HV_TRI_OK;
+        // backend.cpp:1108-1119: per-pose derivative blocks, the two cameras of a pose summed
+        if (with_derivatives)
+            for (int i = tid; i < n * 21; i += VT) {
+                const int k = i / 21, e = i - 21 * k, r = e / 7, c = e - 7 * r;              // [k][r][c]: c < 3 position, else quaternion
+                double v = s_dpfi[r * ncol + 7 * k + c];
+                if (a.stereo) v += s_dpfi[r * ncol + 7 * (k + n) + c];
+                s_dpf[i] = v;
+            }
+        VU_STAMP(28);
+        if (tid < nt) prepare_pose_part(s_trail + tid * POSE_WORDS, pfw, s_it + tid * ITER_WORDS);          // 4
         __syncthreads();
-        if (s_flag[0]) break;
-    }
-    }   // iterative branch
-    VU_STAMP(27);
-    // ---- status, back to world coordinates (:345-392) ----
-    double *M = s_small + 40, *pf0 = s_small + 49;           // R0T * dpf0_dpfi, the point in the frame of pose 0
-    if (tid == 0 && !(MAP && map_track)) {
-        int status = HV_TRI_OK;
-        if (a.linear) { /* pfw and the world-frame derivative columns are in place */ }
-        else if (!s_flag[0]) status = HV_TRI_NO_CONVERGENCE;
-        else if (scal[1] < a.rcond_threshold) status = HV_TRI_BAD_COND;
-        if (status == HV_TRI_OK && !a.linear) {
-            double d[9], q[3], w[3], Ml[9];
-            inverse_depth(pfi, q, d);
-            mv3(R0T, q, w);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { pfw[k] = w[k] + p0[k]; pf0[k] = q[k]; }
-            if (pfw[0] == p0[0] && pfw[1] == p0[1] && pfw[2] == p0[2]) status = HV_TRI_UNKNOWN_PROBLEM;
-            mm3(R0T, d, Ml);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) M[k] = Ml[k];
-        }
-        s_flag[1] = status;
-        s_flag[2] = 0;                                        // behind any camera
-    }
-    __syncthreads();
-    status = s_flag[1];
-    if (status == HV_TRI_OK) {
-        if (tid < ncol && !a.linear) {
-            const int j = tid;
-            double u[3] = {0, 0, 0}, v[3];
-            if (j >= 3 && j < 7) mTv3(s_trail + 12 + 9 * (j - 3), pf0, u);                // dR0T * pf0
-            const double cur[3] = {s_dpfi[j], s_dpfi[ncol + j], s_dpfi[2 * ncol + j]};
-            mv3(M, cur, v);
-#pragma unroll
-            for (int r = 0; r < 3; ++r) s_dpfi[r * ncol + j] = u[r] + v[r] + (j == r ? 1.0 : 0.0);      // dp0 = e_j for j < 3 (r < 3, so j == r implies it)
-        }
-        if (tid < nt) {                                       // isBehind (:54-60)
-            const double *cur = s_trail + tid * POSE_WORDS;
-            const double d[3] = {pfw[0] - cur[0], pfw[1] - cur[1], pfw[2] - cur[2]};
-            if (cur[9] * d[0] + cur[10] * d[1] + cur[11] * d[2] < 0) atomicOr(&s_flag[2], 1);
-        }
-        __syncthreads();
-        if (s_flag[2]) status = HV_TRI_BEHIND;
-    }
-    if (!(MAP && map_track)) {   // backend.cpp:1098-1102: depth window on whatever point the triangulation left behind
-        const double dx = pfw[0] - p0[0], dy = pfw[1] - p0[1], dz = pfw[2] - p0[2], depth = sqrt(dx * dx + dy * dy + dz * dz);
-        if (depth < a.min_dist || depth > a.max_dist) status = HV_TRI_BAD_DEPTH;
-    }
-    with_derivatives = status == HV_TRI_OK;
-    // backend.cpp:1108-1119: per-pose derivative blocks, the two cameras of a pose summed
-    if (with_derivatives)
-        for (int i = tid; i < n * 21; i += VT) {
-            const int k = i / 21, e = i - 21 * k, r = e / 7, c = e - 7 * r;              // [k][r][c]: c < 3 position, else quaternion
-            double v = s_dpfi[r * ncol + 7 * k + c];
-            if (a.stereo) v += s_dpfi[r * ncol + 7 * (k + n) + c];
-            s_dpf[i] = v;
-        }
-    VU_STAMP(28);
-    // ---- prepareVisualUpdate (triangulation.cpp:897-987), full-width H (batch layout of the update kernel) ----
-    // per trail pose: dip*R (2x3), the own-orientation block dip*dRpt (2x4), f, depth class  -> s_it[i][0..16]
-    if (tid < nt) {
-        const double *pose = s_trail + tid * POSE_WORDS;
-        double *o = s_it + tid * ITER_WORDS;
-        const double pt[3] = {pfw[0] - pose[0], pfw[1] - pose[1], pfw[2] - pose[2]};
-        double pfc[3], ipH[3], dip[9];
-        mv3(pose + 3, pt, pfc);
-        inverse_depth(pfc, ipH, dip);
-        o[16] = pfc[2] == 0 ? 1.0 : pfc[2] < 0 ? 2.0 : 0.0;
-        o[14] = ipH[0]; o[15] = ipH[1];
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[3 * r + c] = dip[3 * r] * pose[3 + c] + dip[3 * r + 1] * pose[6 + c] + dip[3 * r + 2] * pose[9 + c];
-#pragma unroll
-        for (int jq = 0; jq < 4; ++jq) {
-            const double *dR = pose + 12 + 9 * jq;
-            double a1[3], b1[3], b2[3];
-            mv3(dR, pt, a1);
-            mTv3(dR, pose + 48, b1);
-            mv3(pose + 3, b1, b2);
-#pragma unroll
-            for (int r = 0; r < 2; ++r) o[6 + 4 * r + jq] = dip[3 * r] * (a1[0] + b2[0]) + dip[3 * r + 1] * (a1[1] + b2[1]) + dip[3 * r + 2] * (a1[2] + b2[2]);
-        }
-    }
-    __syncthreads();
-    VU_STAMP(29);
+        VU_STAMP(29);
     }   // !REC: the front
     // the point's derivative w.r.t. the time shift: the last column of dpfi (record-fed builds keep just that column)
     auto sft_col = [&](int c) -> double { return REC ? s_dpfi[c] : s_dpfi[c * ncol + dDim]; };
@@ -879,6 +895,7 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
         for (int i = 0; i < nt && prep == 0; ++i) prep = (int)s_it[i * ITER_WORDS + 16];   // first failing pose decides (:920-927); uniform
         const double pf_out[3] = {pfw[0], pfw[1], pfw[2]};
         if (!(status == HV_TRI_OK && prep == 0)) {               // nothing to gate (uniform): the track is final
+            // every output but Hc / acol / v / f; the dense exit (vu_prepare_body's end) is this set without chi2
             if (tid == 0) {
                 st_out[0] = status; st_out[1] = prep;
                 if (a.active) a.active[rec] = 0;
@@ -997,6 +1014,7 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
             }
         }
         if constexpr (FUSED == 2) {                               // the gate is the next launch: this track is "prepared, not gated yet"
+            // (chi2, the lists and the adaptive scale are that launch's to write)
             if (tid == 0) {
                 if (a.gate_status) a.gate_status[rec] = 1;        // VuOutlierStatus::NOT_COMPUTED until ekf_sparse_gate_kernel has run
                 if (a.spec_tracks > 0) a.epoch[rec] = a.success_counter[b];
@@ -1009,6 +1027,7 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
         // (structured_S serves the poses in one group where A = na x rows fits g_cap, else in two: the half must fit)
         const int g_half = na * ((2 * ncam * ((n + 1) >> 1)) | 1), g_all = na * (rows | 1);
         if (STRUCT && (Rs * rows > T_CAP || g_cap < 832 + VT / 64 || (g_all > g_cap && g_half > g_cap))) {   // (cannot happen: the launcher admits what the carve holds) not gated, never applied
+            // only gate_status says so: chi2, the scale and epoch keep what they held
             if (tid == 0 && a.gate_status) a.gate_status[rec] = 1;
             return;
         }
@@ -1025,6 +1044,7 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
             double s2 = 0.0;
             for (int c = 0; c < rows; ++c) { const double vc = T[(size_t)c * Rs + rows]; s2 += vc * vc; }    // every thread: same order, same value
             if (sqrt(s2 / rows) > a.rmse_thr * gscale) {
+                // the chi2 decision's set (below) for a rejection that never joins the inlier list; chi2 is 0, not computed
                 if (tid == 0) {
                     if (a.gate_status) a.gate_status[rec] = 2 /*RMSE*/;
                     if (a.chi2) a.chi2[rec] = 0.0;
@@ -1474,14 +1494,14 @@ __device__ __forceinline__ void vu_tri_body(const VuPrepareArgs &a, const int b)
     TRI_STAMP(55);
     int status = s_flag[1];
     double *recp = a.tri_rec + rec * (size_t)a.tri_stride;
-    const int R_DPF = 17 * nt_max, R_SFT = R_DPF + 21 * a.np;
+    const VuTriRec R(a.np, nt_max);
     // ---- prepareVisualUpdate, per-pose part (triangulation.cpp:897-947): dip R (2x3), dip dRpt (2x4), f, depth class; isBehind (:54-60).
     // The last wave takes the poses, the others the columns' way back to world coordinates ----
     {
         const int t0 = NT > 64 ? tid - (NT - 64) : tid;
         if (t0 >= 0 && t0 < nt) {
             const double *pose = s_trail + t0 * POSE_WORDS;
-            double *o = recp + 17 * t0;
+            double *o = recp + VuTriRec::POSE * t0;
             const double pt[3] = {pfw[0] - pose[0], pfw[1] - pose[1], pfw[2] - pose[2]};
             if (status == HV_TRI_OK && pose[9] * pt[0] + pose[10] * pt[1] + pose[11] * pt[2] < 0) atomicOr(&s_flag[2], 1);
             double pfc[3], ipH[3], dip[9];
@@ -1522,9 +1542,9 @@ __device__ __forceinline__ void vu_tri_body(const VuPrepareArgs &a, const int b)
                 const int k = i / 21, e = i - 21 * k, r = e / 7, c = e - 7 * r;
                 double v = world(7 * k + c, r);
                 if (a.stereo) v += world(7 * (k + n) + c, r);
-                recp[R_DPF + i] = v;
+                recp[R.dpf + i] = v;
             }
-        if (tid < 3) recp[R_SFT + tid] = a.est_shift ? world(dDim, tid) : 0.0;
+        if (tid < 3) recp[R.sft + tid] = a.est_shift ? world(dDim, tid) : 0.0;
     }
     sync();
     TRI_STAMP(56);
@@ -1536,7 +1556,7 @@ __device__ __forceinline__ void vu_tri_body(const VuPrepareArgs &a, const int b)
         }
         int prep = 0;
         for (int i = 0; i < nt && prep == 0; ++i) prep = (int)s_it[i * TRI_ITW + 16];   // first failing pose decides (:920-927)
-        recp[R_SFT + 3] = (double)prep;
+        recp[R.prep] = (double)prep;
         a.status[2 * rec] = status;
 #pragma unroll
         for (int k = 0; k < 3; ++k) a.pf[3 * rec + k] = pfw[k];
@@ -1651,6 +1671,30 @@ __global__ __launch_bounds__(VT_THROUGHPUT, 4) void vu_compact_kernel_2percu(VuP
     vu_prepare_body<VT_THROUGHPUT, MAXP_SMALL, 2>(a, blockIdx.x);
 }
 
+// The builds, one entry each: what hv_create raises the dynamic-LDS limit to and what a launch asks for. lds 0: the front kernels, whose
+// carve (TriLds) depends on the launch's longest track and stays below the default limit.
+struct VuBuild { void (*kernel)(VuPrepareArgs); int threads; size_t lds; };
+enum { B_PREPARE, B_PREPARE_2PERCU, B_MAP, B_GATE, B_GATE_2PERCU, B_COMPACT, B_COMPACT_2PERCU, B_GATE_LONG, B_GATE_REC, B_GATE_LONG_REC,
+       B_TRI, B_TRI_X2, B_TRI_X4, B_COUNT };
+const VuBuild vu_builds[B_COUNT] = {
+    {vu_prepare_kernel, VT_LATENCY, VuLds<MAXP_ALL>::BYTES},           {vu_prepare_kernel_2percu, VT_THROUGHPUT, VuLds<MAXP_SMALL>::BYTES},
+    {vu_prepare_map_kernel, VT_LATENCY, VuLds<MAXP_ALL>::BYTES},
+    {vu_gate_kernel, VT_LATENCY, VuLds<MAXP_ALL>::BYTES},              {vu_gate_kernel_2percu, VT_THROUGHPUT, VuLds<MAXP_SMALL>::BYTES},
+    {vu_compact_kernel, VT_LATENCY, VuLds<MAXP_ALL>::BYTES},           {vu_compact_kernel_2percu, VT_THROUGHPUT, VuLds<MAXP_SMALL>::BYTES},
+    {vu_gate_long_kernel, VT_LATENCY, VuLds<MAXP_ALL, true>::BYTES},
+    {vu_gate_rec_kernel, VT_REC, VuRecLds<MAXP_REC>::BYTES},           {vu_gate_long_rec_kernel, VT_LATENCY, VuRecLds<MAXP_ALL, true>::BYTES},
+    {vu_tri_kernel, 64, 0}, {vu_tri_kernel_x2, 128, 0}, {vu_tri_kernel_x4, 256, 0},
+};
+
+void launch_build(int build, dim3 grid, size_t lds, hipStream_t stream, const VuPrepareArgs &a)
+{
+    const VuBuild &B = vu_builds[build];
+    hipLaunchKernelGGL(B.kernel, grid, dim3((unsigned)B.threads), lds, stream, a);
+}
+
+// the longest track a launch processes: its class's upper end (a.np stays the record stride)
+int vu_np_sel(const VuPrepareArgs &a) { return a.np_hi > 0 && a.np_hi < a.np ? a.np_hi : a.np; }
+
 }  // namespace
 
 int launch_visit_order(Ctx *c, int visits, int batch, const int *np_rec_dev, int np_lo, int np_hi, int np_max, int *order_dev,
@@ -1697,7 +1741,7 @@ int vu_split_short_np(const Ctx *c) { return c->knob.ekf_short_np == 11 ? 11 : M
 bool vu_split_supported(const Ctx *c, const VuPrepareArgs &a, int fused)
 {
     if (c->knob.ekf_split_tri == 0 || a.linear || a.map_index || a.spec_tracks > 0 || !a.P || a.n > 160) return false;
-    const int ncam = a.stereo ? 2 : 1, np_sel = a.np_hi > 0 && a.np_hi < a.np ? a.np_hi : a.np;
+    const int ncam = a.stereo ? 2 : 1, np_sel = vu_np_sel(a);
     if (a.np > MAXNP || a.np * ncam > MAXP_ALL) return false;
     if (fused == 1) {
         if (!vu_split_short_ok(c, a.n, a.stereo != 0, a.batch, a.linear != 0) || np_sel * ncam > MAXP_REC) return false;
@@ -1709,18 +1753,11 @@ bool vu_split_supported(const Ctx *c, const VuPrepareArgs &a, int fused)
     return fused == 3 && c->knob.ekf_split_tri != 3;        // (3: experiments -- the short class only, the long class keeps r05's fused launch)
 }
 
-// the kernels' dynamic-LDS limits (each build's whole carve: more than the default 64 KB), set once per context (hv_create)
+// the kernels' dynamic-LDS limits (each build's whole carve, where that is more than the default 64 KB), set once per context (hv_create)
 int vu_prepare_init(Ctx *c)
 {
-    HV_HIP(c, set_lds_limit(vu_prepare_kernel, VuLds<MAXP_ALL>::BYTES));
-    HV_HIP(c, set_lds_limit(vu_prepare_kernel_2percu, VuLds<MAXP_SMALL>::BYTES));
-    HV_HIP(c, set_lds_limit(vu_gate_kernel, VuLds<MAXP_ALL>::BYTES));
-    HV_HIP(c, set_lds_limit(vu_gate_kernel_2percu, VuLds<MAXP_SMALL>::BYTES));
-    HV_HIP(c, set_lds_limit(vu_compact_kernel, VuLds<MAXP_ALL>::BYTES));
-    HV_HIP(c, set_lds_limit(vu_compact_kernel_2percu, VuLds<MAXP_SMALL>::BYTES));
-    HV_HIP(c, set_lds_limit(vu_gate_long_kernel, VuLds<MAXP_ALL, true>::BYTES));
-    HV_HIP(c, set_lds_limit(vu_gate_long_rec_kernel, VuRecLds<MAXP_ALL, true>::BYTES));
-    HV_HIP(c, set_lds_limit(vu_prepare_map_kernel, VuLds<MAXP_ALL>::BYTES));
+    for (const VuBuild &B : vu_builds)
+        if (B.lds > LDS_DEFAULT_LIMIT) HV_HIP(c, set_lds_limit(B.kernel, B.lds));
     return HV_OK;
 }
 
@@ -1731,7 +1768,7 @@ int launch_vu_tri(Ctx *c, const VuPrepareArgs &a, hipStream_t stream)
     if (a.np < 2 || a.batch < 1 || a.np > MAXNP || a.np * ncam > MAXP_ALL) return HV_ERR_INVALID;
     if (!a.tri_rec || a.tri_stride < vu_tri_rec_stride(a.np, ncam) || a.spec_tracks > 0 || a.linear || a.map_index) return HV_ERR_INVALID;
     ScopedKernelTime tm(c, HV_K_VU_TRI, stream);
-    const int np_sel = a.np_hi > 0 && a.np_hi < a.np ? a.np_hi : a.np;
+    const int np_sel = vu_np_sel(a);
     const TriLds L(np_sel * ncam);
     const size_t bytes = sizeof(double) * (size_t)L.total;
     // four wavefronts per track where the launch may hold long tracks (their chain sets the length of the visit), one otherwise
@@ -1740,9 +1777,7 @@ int launch_vu_tri(Ctx *c, const VuPrepareArgs &a, hipStream_t stream)
     // auto: four wavefronts per track where the launch may hold long tracks (their chain sets the length of the visit), two for the short
     // class (profiles/r06/split_tri_ab_v2.txt: 4 lanes 27.90 ms per step with 128 threads, 28.12 with 64, 28.2 with 256)
     const int nthr = forced == 64 || forced == 128 || forced == 256 ? forced : (np_sel * ncam > MAXP_REC ? 256 : 128);
-    if (nthr == 256)      hipLaunchKernelGGL(vu_tri_kernel_x4, dim3((unsigned)a.batch), dim3(256), bytes, stream, a);
-    else if (nthr == 128) hipLaunchKernelGGL(vu_tri_kernel_x2, dim3((unsigned)a.batch), dim3(128), bytes, stream, a);
-    else                  hipLaunchKernelGGL(vu_tri_kernel, dim3((unsigned)a.batch), dim3(64), bytes, stream, a);
+    launch_build(nthr == 256 ? B_TRI_X4 : nthr == 128 ? B_TRI_X2 : B_TRI, dim3((unsigned)a.batch), bytes, stream, a);
     HV_HIP(c, hipGetLastError());
     return HV_OK;
 }
@@ -1755,7 +1790,7 @@ int launch_vu_prepare(Ctx *c, const VuPrepareArgs &a, hipStream_t stream)
     // a longer trail (cameraTrailLength > 20) is a supported filter size but not a supported track length here
     if (a.np > MAXNP || a.np * (a.stereo ? 2 : 1) > MAXP_ALL) return HV_ERR_UNSUPPORTED;
     ScopedKernelTime tm(c, HV_K_VU_PREPARE, stream);
-    const int np_sel = a.np_hi > 0 && a.np_hi < a.np ? a.np_hi : a.np;      // the longest track this launch processes (a.np stays the record stride)
+    const int np_sel = vu_np_sel(a);
     const int nt = np_sel * (a.stereo ? 2 : 1);
     // knob vu_threads (tests / experiments): 384 / 768 forces a build where it applies
     const bool small = vu_small_build(c, nt, a.batch);
@@ -1767,31 +1802,18 @@ int launch_vu_prepare(Ctx *c, const VuPrepareArgs &a, hipStream_t stream)
         if (!a.P || (a.spec_tracks > 0 && a.rec_list) || a.n > 160 || rows > HV_GATE_TIGHT_ROWS || rows >= HV_CHI2INV95_N) return HV_ERR_UNSUPPORTED;
     }
     const dim3 grid((unsigned)a.batch, (unsigned)(a.spec_tracks > 0 ? a.spec_tracks : 1));
+    int build;
     if (a.from_rec) {                                        // the gate half of the split form (the caller has launched vu_tri_kernel)
         if (!a.tri_rec || !vu_split_supported(c, a, a.fused)) return HV_ERR_INVALID;
-        constexpr size_t rec_long_bytes = VuRecLds<MAXP_ALL, true>::BYTES, rec_short_bytes = VuRecLds<MAXP_REC>::BYTES;
-        if (a.fused == 3) hipLaunchKernelGGL(vu_gate_long_rec_kernel, grid, dim3(VT_LATENCY), rec_long_bytes, stream, a);
-        else              hipLaunchKernelGGL(vu_gate_rec_kernel, grid, dim3(VT_REC), rec_short_bytes, stream, a);
-        HV_HIP(c, hipGetLastError());
-        return HV_OK;
-    }
-    if (a.map_index) {                                       // hybrid-map tracks: the dense-H build with the map branch
+        build = a.fused == 3 ? B_GATE_LONG_REC : B_GATE_REC;
+    } else if (a.map_index) {                                // hybrid-map tracks: the dense-H build with the map branch
         if (a.fused || a.map_base < 0) return HV_ERR_INVALID;
-        hipLaunchKernelGGL(vu_prepare_map_kernel, grid, dim3(VT_LATENCY), VuLds<MAXP_ALL>::BYTES, stream, a);
-    } else
-    if (a.fused == 3) {
-        constexpr size_t long_bytes = VuLds<MAXP_ALL, true>::BYTES;
-        hipLaunchKernelGGL(vu_gate_long_kernel, grid, dim3(VT_LATENCY), long_bytes, stream, a);
-    } else if (a.fused == 2) {
-        if (small) hipLaunchKernelGGL(vu_compact_kernel_2percu, grid, dim3(VT_THROUGHPUT), VuLds<MAXP_SMALL>::BYTES, stream, a);
-        else       hipLaunchKernelGGL(vu_compact_kernel, grid, dim3(VT_LATENCY), VuLds<MAXP_ALL>::BYTES, stream, a);
-    } else if (a.fused) {
-        if (small) hipLaunchKernelGGL(vu_gate_kernel_2percu, grid, dim3(VT_THROUGHPUT), VuLds<MAXP_SMALL>::BYTES, stream, a);
-        else       hipLaunchKernelGGL(vu_gate_kernel, grid, dim3(VT_LATENCY), VuLds<MAXP_ALL>::BYTES, stream, a);
-    } else {
-        if (small) hipLaunchKernelGGL(vu_prepare_kernel_2percu, grid, dim3(VT_THROUGHPUT), VuLds<MAXP_SMALL>::BYTES, stream, a);
-        else       hipLaunchKernelGGL(vu_prepare_kernel, grid, dim3(VT_LATENCY), VuLds<MAXP_ALL>::BYTES, stream, a);
-    }
+        build = B_MAP;
+    } else if (a.fused == 3) build = B_GATE_LONG;
+    else if (a.fused == 2)   build = small ? B_COMPACT_2PERCU : B_COMPACT;
+    else if (a.fused)        build = small ? B_GATE_2PERCU : B_GATE;
+    else                     build = small ? B_PREPARE_2PERCU : B_PREPARE;
+    launch_build(build, grid, vu_builds[build].lds, stream, a);
     HV_HIP(c, hipGetLastError());
     return HV_OK;
 }
