@@ -51,6 +51,10 @@ void knobs_from_env(Knobs &k)
     }
 }
 
+// the library's one allocator of device memory (dev_buf.hpp)
+int dev_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? HV_OK : HV_ERR_NOMEM; }
+void dev_free(void *p) { (void)hipFree(p); }
+
 int hip_fail(Ctx *c, hipError_t e, const char *what)
 {
     if (c) {
@@ -170,10 +174,8 @@ int grow_pool(Ctx *c)
     const int n_old = c->p.pool_size, n_new = n_old * 2;
     const long long old_bytes = c->L.slot_bytes * n_old;
     HV_HIP(c, hipStreamSynchronize(c->stream));
-    uint8_t *slab = nullptr; const uint8_t **l0p = nullptr; int *l0s = nullptr;
-    if (hipMalloc(&slab, (size_t)c->L.slot_bytes * n_new + SLAB_SLACK) != hipSuccess) return HV_ERR_NOMEM;
-    if (hipMalloc(&l0p, sizeof(void *) * n_new) != hipSuccess) { (void)hipFree(slab); return HV_ERR_NOMEM; }
-    if (hipMalloc(&l0s, sizeof(int) * n_new) != hipSuccess) { (void)hipFree(slab); (void)hipFree(l0p); return HV_ERR_NOMEM; }
+    DevBuf<uint8_t> slab; DevBuf<const uint8_t *> l0p; DevBuf<int> l0s;       // (an error exit frees them)
+    if (slab.alloc((size_t)c->L.slot_bytes * n_new + SLAB_SLACK) || l0p.alloc(n_new) || l0s.alloc(n_new)) return HV_ERR_NOMEM;
     hipError_t e = hipMemcpyAsync(slab, c->slab, (size_t)old_bytes, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(rebase_l0_kernel, dim3((n_new + 255) / 256), dim3(256), 0, c->stream, l0p, c->d_l0_ptr, l0s, c->d_l0_stride,
@@ -181,9 +183,8 @@ int grow_pool(Ctx *c)
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)hipFree(slab); (void)hipFree(l0p); (void)hipFree(l0s); return hip_fail(c, e, "grow_pool"); }
-    (void)hipFree(c->slab); (void)hipFree(c->d_l0_ptr); (void)hipFree(c->d_l0_stride);
-    c->slab = slab; c->d_l0_ptr = l0p; c->d_l0_stride = l0s;
+    if (e != hipSuccess) return hip_fail(c, e, "grow_pool");
+    c->slab = std::move(slab); c->d_l0_ptr = std::move(l0p); c->d_l0_stride = std::move(l0s);
     c->slot_used.resize(n_new, 0);
     for (int s = n_new - 1; s >= n_old; --s) c->free_slots.push_back(s);
     c->p.pool_size = n_new;
@@ -288,6 +289,33 @@ static int prime_aux_stream(Ctx *c)
     return HV_OK;
 }
 
+// device, streams, buffers and per-kernel limits of a new context; whatever a failed step leaves behind is hv_destroy's
+static int init_ctx(Ctx *c, int high_priority)
+{
+    const hv_params &p = c->p;
+    if (hipSetDevice(p.device) != hipSuccess) return HV_ERR_NO_DEVICE;
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, p.device) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount; }
+    int rc = create_streams(c, high_priority, high_priority ? 1 : 3);       // (lanes: the second streams follow once every lane's context stream is bound)
+    if (rc != HV_OK) return rc;
+    if (c->slab.alloc((size_t)c->L.slot_bytes * p.pool_size + hv::SLAB_SLACK) || c->d_l0_ptr.alloc(p.pool_size) ||
+        c->d_l0_stride.alloc(p.pool_size) || c->d_slots.alloc(4)) return HV_ERR_NOMEM;
+    if (hipMemsetAsync(c->d_l0_ptr, 0, sizeof(void *) * p.pool_size, c->stream) != hipSuccess) return HV_ERR_HIP;
+    // (the second stream runs its first command here, not inside the first frame: a stream's hardware queue is bound when it is used)
+    if (c->aux_stream && prime_aux_stream(c) != HV_OK) return HV_ERR_HIP;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return HV_ERR_HIP;      // the context stream has run its first command
+    c->slot_used.assign(p.pool_size, 0);
+    for (int s = p.pool_size - 1; s >= 0; --s) c->free_slots.push_back(s);
+    rc = hv::KltStage(c, p.max_tracks).s.reserve();
+    if (rc == HV_OK) rc = hv::fill_gradient_borders(c, 0, p.pool_size);
+    if (rc == HV_OK) rc = hv::rot_ransac_alloc_split(c);     // (r05 advisor: once, here -- never inside a launch that may be under capture)
+    if (rc == HV_OK) rc = hv::pyramid_init(c);
+    if (rc == HV_OK) rc = hv::ransac5_init(c);
+    if (rc == HV_OK) rc = hv::detect_tail_init(c);
+    if (rc == HV_OK) rc = hv::ekf_kernels_init(c);
+    if (rc == HV_OK) rc = hv::vu_prepare_init(c);
+    return rc;
+}
+
 static int create_ctx(const hv_params *params, int high_priority, hv_ctx **out)
 {
     if (!params || !out) return HV_ERR_INVALID;
@@ -310,32 +338,7 @@ static int create_ctx(const hv_params *params, int high_priority, hv_ctx **out)
     if (high_priority) c->knob.ekf_side_stream = 5;       // lanes: the visit forks onto the second stream only outside a stream capture (ekf_visit.hip)
     hv::knobs_from_env(c->knob);
     hv::compute_layout(p, c->L);
-    int rc = HV_OK;
-    do {
-        if (hipSetDevice(p.device) != hipSuccess) { rc = HV_ERR_NO_DEVICE; break; }
-        { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, p.device) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount; }
-        rc = create_streams(c, high_priority, high_priority ? 1 : 3);       // (lanes: the second streams follow once every lane's context stream is bound)
-        if (rc != HV_OK) break;
-        const size_t slab_bytes = (size_t)c->L.slot_bytes * p.pool_size + hv::SLAB_SLACK;
-        if (hipMalloc(&c->slab, slab_bytes) != hipSuccess) { rc = HV_ERR_NOMEM; break; }
-        if (hipMalloc(&c->d_l0_ptr, sizeof(void *) * p.pool_size) != hipSuccess) { rc = HV_ERR_NOMEM; break; }
-        if (hipMalloc(&c->d_l0_stride, sizeof(int) * p.pool_size) != hipSuccess) { rc = HV_ERR_NOMEM; break; }
-        if (hipMalloc(&c->d_slots, sizeof(int) * 4) != hipSuccess) { rc = HV_ERR_NOMEM; break; }
-        if (hipMemsetAsync(c->d_l0_ptr, 0, sizeof(void *) * p.pool_size, c->stream) != hipSuccess) { rc = HV_ERR_HIP; break; }
-        // (the second stream runs its first command here, not inside the first frame: a stream's hardware queue is bound when it is used)
-        if (c->aux_stream && prime_aux_stream(c) != HV_OK) { rc = HV_ERR_HIP; break; }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = HV_ERR_HIP; break; }      // the context stream has run its first command
-        c->slot_used.assign(p.pool_size, 0);
-        for (int s = p.pool_size - 1; s >= 0; --s) c->free_slots.push_back(s);
-        rc = hv::KltStage(c, p.max_tracks).s.reserve();
-        if (rc == HV_OK) rc = hv::fill_gradient_borders(c, 0, p.pool_size);
-        if (rc == HV_OK) rc = hv::rot_ransac_alloc_split(c);     // (r05 advisor: once, here -- never inside a launch that may be under capture)
-        if (rc == HV_OK) rc = hv::pyramid_init(c);
-        if (rc == HV_OK) rc = hv::ransac5_init(c);
-        if (rc == HV_OK) rc = hv::detect_tail_init(c);
-        if (rc == HV_OK) rc = hv::ekf_kernels_init(c);
-        if (rc == HV_OK) rc = hv::vu_prepare_init(c);
-    } while (0);
+    const int rc = init_ctx(c, high_priority);
     if (rc != HV_OK) { hv_destroy(h); return rc; }
     *out = h;
     return HV_OK;
@@ -383,22 +386,13 @@ void hv_destroy(hv_ctx *h)
 {
     if (!h) return;
     Ctx *c = &h->c;
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (hipStream_t s : {c->stream, c->aux_stream}) if (s) (void)hipStreamSynchronize(s);   // both streams, before the first free
+    static_cast<hv::CtxBuffers &>(*c) = hv::CtxBuffers{};
     for (auto &t : c->timers) {
         for (auto &e : t.pending) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
         for (auto &e : t.free_list) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     }
-    if (c->slab) (void)hipFree(c->slab);
-    if (c->d_l0_ptr) (void)hipFree(c->d_l0_ptr);
-    if (c->d_l0_stride) (void)hipFree(c->d_l0_stride);
-    if (c->d_slots) (void)hipFree(c->d_slots);
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    if (c->d_ransac_split) (void)hipFree(c->d_ransac_split);
-    for (int k = 0; k < HV_INGEST_CAMERAS; ++k)
-        if (c->d_tile_box[k]) (void)hipFree(c->d_tile_box[k]);
-    for (int k = 0; k < HV_INGEST_CAMERAS; ++k)
-        if (c->d_map_xy[k]) { (void)hipFree(c->d_map_xy[k]); (void)hipFree(c->d_map_xf[k]); (void)hipFree(c->d_map_yf[k]); }
-    if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
+    if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete h;
 }

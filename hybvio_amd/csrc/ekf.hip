@@ -2136,10 +2136,10 @@ int ekf_launch_update(Ekf *e, const UpdateRequest &rq)
     const UpdateShape shape = update_shape(e->n, nr, l, UPD_THREADS / 64);
     a.Rs = shape.Rs;                                     // (lds_stride; unpadded where T lives in the global workspace)
     a.mode = mode; a.generic = generic; a.normalize_all = rq.normalize_all; a.map_dim = e->map_dim;
-    a.m = e->m; a.P = e->P; a.H = rq.H_dev; a.v = rq.v_dev; a.rdiag = rq.rdiag_dev; a.rd0 = rq.rd0; a.rd1 = rq.rd1; a.noise_scale = e->noise_scale;
-    a.ws = e->ws; a.chi2 = rq.chi2_dev; a.status = rq.status_dev; a.active = rq.active_dev; a.require_inlier = rq.require_inlier_dev; a.success_counter = rq.success_counter_dev;
+    a.m = e->fixed.m; a.P = e->fixed.P; a.H = rq.H_dev; a.v = rq.v_dev; a.rdiag = rq.rdiag_dev; a.rd0 = rq.rd0; a.rd1 = rq.rd1; a.noise_scale = e->noise_scale;
+    a.ws = e->fixed.ws; a.chi2 = rq.chi2_dev; a.status = rq.status_dev; a.active = rq.active_dev; a.require_inlier = rq.require_inlier_dev; a.success_counter = rq.success_counter_dev;
     a.spec = spec; a.n_tracks = rq.n_tracks; a.cursor = rq.cursor_dev; a.max_successful = rq.max_successful; a.gate_in = rq.gate_in_dev;
-    a.cursor_out = rq.cursor_out_dev; a.pub = rq.pub_dev; a.pass_id = rq.pass_id; a.nr_rec = rq.nr_rec_dev; a.err = e->err_dev;
+    a.cursor_out = rq.cursor_out_dev; a.pub = rq.pub_dev; a.pass_id = rq.pass_id; a.nr_rec = rq.nr_rec_dev; a.err = e->fixed.err_dev;
     a.h_stride = (size_t)nr_stride * l; a.v_stride = nr_stride;
     if (rq.compact.acol) {
         const CompactH *compact = &rq.compact;
@@ -2227,7 +2227,7 @@ int ekf_launch_gate_stream(Ekf *e, const GateStreamRequest &rq)
     GateArgs a{};
     a.n = e->n; a.nr = nr; a.l = l;
     a.Rs = lds_stride(nr + 1);
-    a.P = e->P; a.H = rq.H_dev; a.v = rq.v_dev; a.rd = rq.rd; a.noise_scale = e->noise_scale; a.chi2 = rq.chi2_dev; a.status = rq.status_dev;
+    a.P = e->fixed.P; a.H = rq.H_dev; a.v = rq.v_dev; a.rd = rq.rd; a.noise_scale = e->noise_scale; a.chi2 = rq.chi2_dev; a.status = rq.status_dev;
     a.active = rq.active_dev; a.success_counter = rq.success_counter_dev; a.max_successful = rq.max_successful;
     const int ti = tiles16(nr);
     const GateStreamLds L = gate_stream_lds(ti, tiles16(l), a.Rs, nr);
@@ -2251,7 +2251,7 @@ int ekf_launch_sparse_gate(Ekf *e, const SparseGateRequest &rq)
     const SparseGateLds L = sparse_gate_lds(np, ncam);      // sized for the launch's longest record
     if (!L.supported) return HV_ERR_UNSUPPORTED;
     SparseGateArgs a{};
-    a.n = e->n; a.nr = nr; a.ncam = ncam; a.na_max = na_max; a.P = e->P; a.Hc = rq.Hc_dev; a.v = rq.v_dev; a.acol = rq.acol_dev; a.nr_rec = rq.nr_rec_dev;
+    a.n = e->n; a.nr = nr; a.ncam = ncam; a.na_max = na_max; a.P = e->fixed.P; a.Hc = rq.Hc_dev; a.v = rq.v_dev; a.acol = rq.acol_dev; a.nr_rec = rq.nr_rec_dev;
     a.active = rq.active_dev; a.rd = rq.rd; a.noise_scale = e->noise_scale; a.chi2 = rq.chi2_dev; a.status = rq.status_dev;
     a.hs_doubles = (int)(L.T - L.Hs); a.lds_doubles = (int)(L.acol - L.Hs);
     ScopedKernelTime tm(c, HV_K_EKF_GATE, stream);
@@ -2305,13 +2305,8 @@ void hv_ekf_destroy(hv_ekf *h)
     if (!h) return;
     Ekf *e = &h->e;
     if (e->c) for (hipStream_t s : {e->c->stream, e->c->aux_stream}) if (s) (void)hipStreamSynchronize(s);   // both streams, before the first free
-    void *ptrs[] = { e->m, e->P, e->P1, e->m1, e->Q, e->dydx, e->ws, e->sH, e->sv, e->sr, e->schi2, e->simu,
-                     e->sstatus, e->sdrop, e->sactive, e->vuH, e->vuv, e->vupf, e->vuactive,
-                     e->spH, e->spv, e->sppf, e->spactive, e->spcursor, e->spepoch, e->spcursor2, e->sppub, e->vurows, e->sprows,
-                     e->vuacol, e->spacol, e->err_dev, e->gate_scale, e->bH, e->bv, e->brows, e->bany, e->sideH, e->sidev, e->side_active, e->side_acol, e->side_dm, e->tri_rec, e->visit_counts, e->visit_lists, e->visit_order, e->visit_long, e->visit_long_count };
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_join) (void)hipEventDestroy(e->ev_join);
+    if (e->longc.ev_fork) (void)hipEventDestroy(e->longc.ev_fork);
+    if (e->longc.ev_join) (void)hipEventDestroy(e->longc.ev_join);
     delete h;
 }
 
@@ -2329,20 +2324,8 @@ int hv_ekf_create(hv_ctx *ctx, const hv_ekf_params *par, int batch, hv_ekf **out
     e->noise_scale = par->noiseScale * par->noiseScale;
     e->max_rows = n;
     const size_t nn = (size_t)n * n;
-    bool ok = true;
-    auto alloc = [&](auto &ptr, size_t bytes) { if (ok && hipMalloc(reinterpret_cast<void **>(&ptr), bytes) != hipSuccess) ok = false; };
-    alloc(e->m, sizeof(double) * n * batch); alloc(e->P, sizeof(double) * nn * batch);
-    alloc(e->P1, sizeof(double) * nn * batch); alloc(e->m1, sizeof(double) * n * batch);
-    alloc(e->Q, sizeof(double) * 144 * batch); alloc(e->dydx, sizeof(double) * 400 * batch);
-    alloc(e->ws, sizeof(double) * (size_t)(2 * n + 1) * n * batch);
-    e->sH_cap = nn * batch;
-    alloc(e->sH, sizeof(double) * e->sH_cap); alloc(e->sv, sizeof(double) * n * batch); alloc(e->sr, sizeof(double) * batch);
-    alloc(e->schi2, sizeof(double) * batch); alloc(e->simu, sizeof(double) * 7 * HV_EKF_MAX_PREDICT_SAMPLES * batch);
-    alloc(e->sstatus, sizeof(int) * batch); alloc(e->sdrop, sizeof(int) * batch); alloc(e->sactive, batch);
-    alloc(e->err_dev, sizeof(int));
-    alloc(e->visit_counts, 4 * sizeof(int) * (Ekf::VISIT_SLOTS + 1)); alloc(e->visit_order, sizeof(int) * (size_t)Ekf::VISIT_SLOTS * batch);
-    alloc(e->visit_long, sizeof(int) * (size_t)Ekf::VISIT_SLOTS * batch); alloc(e->visit_long_count, sizeof(int) * Ekf::VISIT_SLOTS); alloc(e->visit_lists, 3 * sizeof(int) * (size_t)batch);
-    if (ok && hipMemset(e->err_dev, 0, sizeof(int)) != hipSuccess) ok = false;
+    bool ok = e->fixed.ensure(*e) == HV_OK;
+    if (ok && hipMemset(e->fixed.err_dev, 0, sizeof(int)) != hipSuccess) ok = false;
     if (!ok) { hv_ekf_destroy(h); return HV_ERR_NOMEM; }
 
     // initial state and covariance: EKFImplementation ctor, ekf.cpp:153-296
@@ -2416,8 +2399,8 @@ int hv_ekf_insert_map_point(hv_ekf *h, int b, int map_index, const double *pf)
     Ekf *e = &h->e; Ctx *c = e->c;
     if (map_index < 0 || 3 * (map_index + 1) > e->map_dim) return HV_ERR_INVALID;
     const int off = e->n - e->map_dim + 3 * map_index;
-    hipLaunchKernelGGL(hv::ekf_insert_map_point_kernel, dim3(1), dim3(256), 0, c->stream, e->n, off, e->m + (size_t)b * e->n,
-                       e->P + (size_t)b * e->n * e->n, pf[0], pf[1], pf[2]);
+    hipLaunchKernelGGL(hv::ekf_insert_map_point_kernel, dim3(1), dim3(256), 0, c->stream, e->n, off, e->fixed.m + (size_t)b * e->n,
+                       e->fixed.P + (size_t)b * e->n * e->n, pf[0], pf[1], pf[2]);
     HV_HIP(c, hipGetLastError());
     return HV_OK;
 }
@@ -2427,7 +2410,7 @@ int hv_ekf_get_map_point(hv_ekf *h, int b, int map_index, double *pf)
     if (!h || !pf || b < 0 || b >= h->e.batch) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
     if (map_index < 0 || 3 * (map_index + 1) > e->map_dim) return HV_ERR_INVALID;
-    HV_HIP(c, hipMemcpyAsync(pf, e->m + (size_t)b * e->n + e->n - e->map_dim + 3 * map_index, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(pf, e->fixed.m + (size_t)b * e->n + e->n - e->map_dim + 3 * map_index, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -2436,9 +2419,9 @@ int hv_ekf_frame_error(hv_ekf *h, int *flags)
 {
     if (!h || !flags) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    HV_HIP(c, hipMemcpyAsync(flags, e->err_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(flags, e->fixed.err_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
-    if (*flags) HV_HIP(c, hipMemsetAsync(e->err_dev, 0, sizeof(int), c->stream));
+    if (*flags) HV_HIP(c, hipMemsetAsync(e->fixed.err_dev, 0, sizeof(int), c->stream));
     return HV_OK;
 }
 
@@ -2459,8 +2442,8 @@ int hv_ekf_set_state(hv_ekf *h, int b, const double *m, const double *P)
 {
     if (!h || b < 0 || b >= h->e.batch) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c; const size_t n = e->n;
-    if (m) HV_HIP(c, hipMemcpyAsync(e->m + b * n, m, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    if (P) HV_HIP(c, hipMemcpyAsync(e->P + b * n * n, P, sizeof(double) * n * n, hipMemcpyHostToDevice, c->stream));
+    if (m) HV_HIP(c, hipMemcpyAsync(e->fixed.m + b * n, m, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    if (P) HV_HIP(c, hipMemcpyAsync(e->fixed.P + b * n * n, P, sizeof(double) * n * n, hipMemcpyHostToDevice, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -2469,8 +2452,8 @@ int hv_ekf_get_state(hv_ekf *h, int b, double *m, double *P)
 {
     if (!h || b < 0 || b >= h->e.batch) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c; const size_t n = e->n;
-    if (m) HV_HIP(c, hipMemcpyAsync(m, e->m + b * n, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    if (P) HV_HIP(c, hipMemcpyAsync(P, e->P + b * n * n, sizeof(double) * n * n, hipMemcpyDeviceToHost, c->stream));
+    if (m) HV_HIP(c, hipMemcpyAsync(m, e->fixed.m + b * n, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    if (P) HV_HIP(c, hipMemcpyAsync(P, e->fixed.P + b * n * n, sizeof(double) * n * n, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -2479,7 +2462,7 @@ int hv_ekf_get_means(hv_ekf *h, double *m_all)
 {
     if (!h || !m_all) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    HV_HIP(c, hipMemcpyAsync(m_all, e->m, sizeof(double) * e->n * e->batch, hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(m_all, e->fixed.m, sizeof(double) * e->n * e->batch, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -2488,7 +2471,7 @@ int hv_ekf_set_process_noise(hv_ekf *h, int b, const double *Q)
 {
     if (!h || !Q || b < 0 || b >= h->e.batch) return HV_ERR_INVALID;
     Ctx *c = h->e.c;
-    HV_HIP(c, hipMemcpyAsync(h->e.Q + (size_t)b * 144, Q, sizeof(double) * 144, hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(h->e.fixed.Q + (size_t)b * 144, Q, sizeof(double) * 144, hipMemcpyHostToDevice, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -2497,7 +2480,7 @@ int hv_ekf_get_process_noise(hv_ekf *h, int b, double *Q)
 {
     if (!h || !Q || b < 0 || b >= h->e.batch) return HV_ERR_INVALID;
     Ctx *c = h->e.c;
-    HV_HIP(c, hipMemcpyAsync(Q, h->e.Q + (size_t)b * 144, sizeof(double) * 144, hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(Q, h->e.fixed.Q + (size_t)b * 144, sizeof(double) * 144, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -2506,7 +2489,7 @@ int hv_ekf_get_dydx(hv_ekf *h, int b, double *F)
 {
     if (!h || !F || b < 0 || b >= h->e.batch) return HV_ERR_INVALID;
     Ctx *c = h->e.c;
-    HV_HIP(c, hipMemcpyAsync(F, h->e.dydx + (size_t)b * 400, sizeof(double) * 400, hipMemcpyDeviceToHost, c->stream));
+    HV_HIP(c, hipMemcpyAsync(F, h->e.fixed.dydx + (size_t)b * 400, sizeof(double) * 400, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -2514,8 +2497,8 @@ int hv_ekf_get_dydx(hv_ekf *h, int b, double *F)
 int hv_ekf_device_pointers(hv_ekf *h, double **m_dev, double **P_dev)
 {
     if (!h) return HV_ERR_INVALID;
-    if (m_dev) *m_dev = h->e.m;
-    if (P_dev) *P_dev = h->e.P;
+    if (m_dev) *m_dev = h->e.fixed.m;
+    if (P_dev) *P_dev = h->e.fixed.P;
     return HV_OK;
 }
 
@@ -2524,7 +2507,7 @@ static int predict_common(Ekf *e, const double *dt_dev, const double *gyro_dev, 
 {
     Ctx *c = e->c;
     hv::PredictArgs a{};
-    a.n = e->n; a.batch = e->batch; a.m = e->m; a.P = e->P; a.Q = e->Q; a.dydx = e->dydx;
+    a.n = e->n; a.batch = e->batch; a.m = e->fixed.m; a.P = e->fixed.P; a.Q = e->fixed.Q; a.dydx = e->fixed.dydx;
     a.dt = dt_dev; a.gyro = gyro_dev; a.acc = acc_dev; a.dt0 = dt0; a.nsteps = nsteps;
     for (int i = 0; i < 3; i++) { a.g0[i] = g0 ? g0[i] : 0.0; a.a0[i] = a0 ? a0[i] : 0.0; }
     a.noise_scale = e->noise_scale; a.gravity = e->par.gravity;
@@ -2548,10 +2531,10 @@ int hv_ekf_predict(hv_ekf *h, const double *dt, const double *gyro, const double
     Ekf *e = &h->e; Ctx *c = e->c;
     if (e->batch == 1) return predict_common(e, nullptr, nullptr, nullptr, dt[0], gyro, acc);   // immediates, no copy
     const size_t B = e->batch;
-    HV_HIP(c, hipMemcpyAsync(e->simu, dt, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(e->simu + B, gyro, sizeof(double) * 3 * B, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(e->simu + 4 * B, acc, sizeof(double) * 3 * B, hipMemcpyHostToDevice, c->stream));
-    return predict_common(e, e->simu, e->simu + B, e->simu + 4 * B, 0.0, nullptr, nullptr);
+    HV_HIP(c, hipMemcpyAsync(e->fixed.simu, dt, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(e->fixed.simu + B, gyro, sizeof(double) * 3 * B, hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(e->fixed.simu + 4 * B, acc, sizeof(double) * 3 * B, hipMemcpyHostToDevice, c->stream));
+    return predict_common(e, e->fixed.simu, e->fixed.simu + B, e->fixed.simu + 4 * B, 0.0, nullptr, nullptr);
 }
 
 int hv_ekf_predict_dev(hv_ekf *h, const double *dt_dev, const double *gyro_dev, const double *acc_dev)
@@ -2566,7 +2549,7 @@ int hv_ekf_predict_n(hv_ekf *h, int n_samples, const double *dt, const double *g
     Ekf *e = &h->e; Ctx *c = e->c;
     if (n_samples == 1 && e->batch == 1) return predict_common(e, nullptr, nullptr, nullptr, dt[0], gyro, acc);
     const size_t nB = (size_t)n_samples * e->batch;
-    double *d_dt = e->simu, *d_g = e->simu + nB, *d_a = e->simu + 4 * nB;
+    double *d_dt = e->fixed.simu, *d_g = e->fixed.simu + nB, *d_a = e->fixed.simu + 4 * nB;
     HV_HIP(c, hipMemcpyAsync(d_dt, dt, sizeof(double) * nB, hipMemcpyHostToDevice, c->stream));
     HV_HIP(c, hipMemcpyAsync(d_g, gyro, sizeof(double) * 3 * nB, hipMemcpyHostToDevice, c->stream));
     HV_HIP(c, hipMemcpyAsync(d_a, acc, sizeof(double) * 3 * nB, hipMemcpyHostToDevice, c->stream));
@@ -2583,11 +2566,11 @@ static int stage_update_inputs(Ekf *e, int nr, int l, const double *H, const dou
                                const unsigned char *active)
 {
     Ctx *c = e->c; const size_t B = e->batch;
-    if ((size_t)nr * l * B > e->sH_cap) return HV_ERR_INVALID;
-    HV_HIP(c, hipMemcpyAsync(e->sH, H, sizeof(double) * nr * l * B, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(e->sv, v, sizeof(double) * nr * B, hipMemcpyHostToDevice, c->stream));
-    if (rdiag) HV_HIP(c, hipMemcpyAsync(e->sr, rdiag, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
-    if (active) HV_HIP(c, hipMemcpyAsync(e->sactive, active, B, hipMemcpyHostToDevice, c->stream));
+    if ((size_t)nr * l * B > e->fixed.sH_cap) return HV_ERR_INVALID;
+    HV_HIP(c, hipMemcpyAsync(e->fixed.sH, H, sizeof(double) * nr * l * B, hipMemcpyHostToDevice, c->stream));
+    HV_HIP(c, hipMemcpyAsync(e->fixed.sv, v, sizeof(double) * nr * B, hipMemcpyHostToDevice, c->stream));
+    if (rdiag) HV_HIP(c, hipMemcpyAsync(e->fixed.sr, rdiag, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
+    if (active) HV_HIP(c, hipMemcpyAsync(e->fixed.sactive, active, B, hipMemcpyHostToDevice, c->stream));
     return HV_OK;
 }
 
@@ -2600,8 +2583,8 @@ int hv_ekf_update(hv_ekf *h, int nr, int l, const double *H, const double *y, co
     int rc = stage_update_inputs(e, nr, l, H, y, r_diag, active);
     if (rc != HV_OK) return rc;
     hv::UpdateRequest rq;
-    rq.nr = nr; rq.l = l; rq.H_dev = e->sH; rq.v_dev = e->sv; rq.rdiag_dev = e->sr; rq.mode = 1; rq.generic = 1; rq.normalize_all = normalize_all;
-    if (active) rq.active_dev = e->sactive;
+    rq.nr = nr; rq.l = l; rq.H_dev = e->fixed.sH; rq.v_dev = e->fixed.sv; rq.rdiag_dev = e->fixed.sr; rq.mode = 1; rq.generic = 1; rq.normalize_all = normalize_all;
+    if (active) rq.active_dev = e->fixed.sactive;
     return hv::ekf_launch_update(e, rq);
 }
 
@@ -2612,10 +2595,10 @@ int hv_ekf_visual_gate(hv_ekf *h, int nr, int l, const double *H, const double *
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
     int rc = stage_update_inputs(e, nr, l, H, v, nullptr, nullptr);
     if (rc != HV_OK) return rc;
-    rc = hv::ekf_launch_update(e, hv::gate_request(nr, l, e->sH, e->sv, r * r * e->noise_scale, e->schi2, e->sstatus));
+    rc = hv::ekf_launch_update(e, hv::gate_request(nr, l, e->fixed.sH, e->fixed.sv, r * r * e->noise_scale, e->fixed.schi2, e->fixed.sstatus));
     if (rc != HV_OK) return rc;
-    if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, e->schi2, sizeof(double) * e->batch, hipMemcpyDeviceToHost, c->stream));
-    if (status) HV_HIP(c, hipMemcpyAsync(status, e->sstatus, sizeof(int) * e->batch, hipMemcpyDeviceToHost, c->stream));
+    if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, e->fixed.schi2, sizeof(double) * e->batch, hipMemcpyDeviceToHost, c->stream));
+    if (status) HV_HIP(c, hipMemcpyAsync(status, e->fixed.sstatus, sizeof(int) * e->batch, hipMemcpyDeviceToHost, c->stream));
     HV_HIP(c, hipStreamSynchronize(c->stream));
     return HV_OK;
 }
@@ -2627,7 +2610,7 @@ int hv_ekf_visual_update(hv_ekf *h, int nr, int l, const double *H, const double
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
     int rc = stage_update_inputs(e, nr, l, H, v, nullptr, active);
     if (rc != HV_OK) return rc;
-    return hv::ekf_launch_update(e, hv::inlier_update_request(nr, l, e->sH, e->sv, r * r * e->noise_scale, active ? e->sactive : nullptr));
+    return hv::ekf_launch_update(e, hv::inlier_update_request(nr, l, e->fixed.sH, e->fixed.sv, r * r * e->noise_scale, active ? e->fixed.sactive : nullptr));
 }
 
 int hv_ekf_visual_dev(hv_ekf *h, int nr, int l, const double *H_dev, const double *v_dev, double r, int mode,
@@ -2653,7 +2636,7 @@ static size_t augment_fill(const Ekf *e, hv::AugmentArgs &a)
 {
     a = hv::AugmentArgs{};
     a.n = e->n; a.cam_poses = e->cam; a.map_dim = e->map_dim;
-    a.m = e->m; a.P = e->P; a.P1 = e->P1; a.m1 = e->m1;
+    a.m = e->fixed.m; a.P = e->fixed.P; a.P1 = e->fixed.P1; a.m1 = e->fixed.m1;
     a.dropped0 = -1;
     a.q_pos = e->par.noiseInitialPosTrail * e->par.noiseInitialPosTrail * e->noise_scale;
     a.q_ori = e->par.noiseInitialOriTrail * e->par.noiseInitialOriTrail * e->noise_scale;
@@ -2669,14 +2652,14 @@ int hv_ekf_augment(hv_ekf *h, const int *discarded, const unsigned char *active)
     const size_t shmem = augment_fill(e, a);
     if (discarded) {
         if (e->batch == 1) a.dropped0 = discarded[0];
-        else { HV_HIP(c, hipMemcpyAsync(e->sdrop, discarded, sizeof(int) * e->batch, hipMemcpyHostToDevice, c->stream)); a.dropped = e->sdrop; }
+        else { HV_HIP(c, hipMemcpyAsync(e->fixed.sdrop, discarded, sizeof(int) * e->batch, hipMemcpyHostToDevice, c->stream)); a.dropped = e->fixed.sdrop; }
     }
-    if (active) { HV_HIP(c, hipMemcpyAsync(e->sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); a.active = e->sactive; }
+    if (active) { HV_HIP(c, hipMemcpyAsync(e->fixed.sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); a.active = e->fixed.sactive; }
     if (shmem > hv::LDS_AUGMENT_LIMIT) return HV_ERR_UNSUPPORTED;      // (state vectors with map points, n > ~190, need more than the default limit)
     hv::ScopedKernelTime tm(c, HV_K_EKF_AUGMENT);
     hipLaunchKernelGGL(hv::ekf_augment_kernel<false>, dim3(e->batch), dim3(hv::AUG_THREADS), shmem, c->stream, a);
     HV_HIP(c, hipGetLastError());
-    std::swap(e->P, e->P1);                 // the kernel wrote the new covariance to the other buffer
+    std::swap(e->fixed.P, e->fixed.P1);                 // the kernel wrote the new covariance to the other buffer
     return HV_OK;
 }
 
@@ -2692,7 +2675,7 @@ static int augment_dev_impl(hv_ekf *h, const int *discarded_dev, const unsigned 
     if (sym_input) hipLaunchKernelGGL(hv::ekf_augment_kernel<true>, dim3(e->batch), dim3(hv::AUG_THREADS), shmem, c->stream, a);
     else           hipLaunchKernelGGL(hv::ekf_augment_kernel<false>, dim3(e->batch), dim3(hv::AUG_THREADS), shmem, c->stream, a);
     HV_HIP(c, hipGetLastError());
-    std::swap(e->P, e->P1);
+    std::swap(e->fixed.P, e->fixed.P1);
     return HV_OK;
 }
 
@@ -2702,8 +2685,8 @@ int hv_ekf_symmetrize_augment(hv_ekf *h, const int *discarded, const unsigned ch
     if (!h) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
     const int *d_drop = nullptr; const unsigned char *d_act = nullptr;
-    if (discarded) { HV_HIP(c, hipMemcpyAsync(e->sdrop, discarded, sizeof(int) * e->batch, hipMemcpyHostToDevice, c->stream)); d_drop = e->sdrop; }
-    if (active) { HV_HIP(c, hipMemcpyAsync(e->sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); d_act = e->sactive; }
+    if (discarded) { HV_HIP(c, hipMemcpyAsync(e->fixed.sdrop, discarded, sizeof(int) * e->batch, hipMemcpyHostToDevice, c->stream)); d_drop = e->fixed.sdrop; }
+    if (active) { HV_HIP(c, hipMemcpyAsync(e->fixed.sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); d_act = e->fixed.sactive; }
     const int rc = augment_dev_impl(h, d_drop, d_act, true);
     if (rc != HV_ERR_UNSUPPORTED) return rc;
     // (map-point states: the folded kernel's LDS limit; the two calls it stands for)
@@ -2718,12 +2701,12 @@ int hv_ekf_undo_augment(hv_ekf *h, const unsigned char *active)
 {
     if (!h) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    hv::ShiftArgs a{e->n, e->map_dim, e->m, e->P, e->P1, e->m1, nullptr};
-    if (active) { HV_HIP(c, hipMemcpyAsync(e->sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); a.active = e->sactive; }
+    hv::ShiftArgs a{e->n, e->map_dim, e->fixed.m, e->fixed.P, e->fixed.P1, e->fixed.m1, nullptr};
+    if (active) { HV_HIP(c, hipMemcpyAsync(e->fixed.sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); a.active = e->fixed.sactive; }
     hv::ScopedKernelTime tm(c, HV_K_EKF_AUGMENT);
     hipLaunchKernelGGL(hv::ekf_unaugment_kernel, dim3(e->batch), dim3(1024), 0, c->stream, a);
     HV_HIP(c, hipGetLastError());
-    std::swap(e->P, e->P1);
+    std::swap(e->fixed.P, e->fixed.P1);
     return HV_OK;
 }
 
@@ -2731,7 +2714,7 @@ int hv_ekf_symmetrize(hv_ekf *h)
 {
     if (!h) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    hipLaunchKernelGGL(hv::ekf_symmetrize_kernel, dim3(e->batch), dim3(1024), 0, c->stream, e->n, e->P);
+    hipLaunchKernelGGL(hv::ekf_symmetrize_kernel, dim3(e->batch), dim3(1024), 0, c->stream, e->n, e->fixed.P);
     HV_HIP(c, hipGetLastError());
     return HV_OK;
 }
@@ -2740,7 +2723,7 @@ int hv_ekf_normalize_quaternions(hv_ekf *h, int only_current)
 {
     if (!h) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    hipLaunchKernelGGL(hv::ekf_normalize_kernel, dim3(e->batch), dim3(64), 0, c->stream, e->n, e->map_dim, e->m, only_current);
+    hipLaunchKernelGGL(hv::ekf_normalize_kernel, dim3(e->batch), dim3(64), 0, c->stream, e->n, e->map_dim, e->fixed.m, only_current);
     HV_HIP(c, hipGetLastError());
     return HV_OK;
 }
@@ -2751,7 +2734,7 @@ int hv_ekf_transform(hv_ekf *h, int b, const double *pC3x3, const double *qC4x4,
     Ekf *e = &h->e; Ctx *c = e->c;
     hv::TransformArgs a{};
     a.n = e->n; a.cam_poses = e->cam;
-    a.m = e->m + (size_t)b * e->n; a.P = e->P + (size_t)b * e->n * e->n;
+    a.m = e->fixed.m + (size_t)b * e->n; a.P = e->fixed.P + (size_t)b * e->n * e->n;
     for (int i = 0; i < 9; i++) a.pC[i] = pC3x3[i];
     for (int i = 0; i < 16; i++) a.qC[i] = qC4x4[i];
     for (int i = 0; i < 3; i++) a.tr[i] = translation3[i];

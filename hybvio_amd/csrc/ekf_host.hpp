@@ -5,49 +5,146 @@
 
 namespace hv {
 
+// The filter object. Its device buffers are grouped by lifetime: each group keeps its capacity beside its buffers and has ONE
+// ensure(), called where the group is first needed; a group's once-only members are allocated by its first ensure().
 struct Ekf {
     Ctx *c = nullptr;
     hv_ekf_params par{};
     int batch = 0, n = 0, cam = 0, map_dim = 0;
     double noise_scale = 0;
-    double *m = nullptr, *P = nullptr, *P1 = nullptr, *m1 = nullptr, *Q = nullptr, *dydx = nullptr, *ws = nullptr;
-    double *sH = nullptr, *sv = nullptr, *sr = nullptr, *schi2 = nullptr, *simu = nullptr;   // staging for host-pointer calls
-    int *sstatus = nullptr, *sdrop = nullptr;
-    unsigned char *sactive = nullptr;
-    size_t sH_cap = 0;
     int max_rows = 0;
-    // buffers of hv_ekf_visual_track_dev (row f3), sized on first use
-    double *vuH = nullptr, *vuv = nullptr, *vupf = nullptr;
-    unsigned char *vuactive = nullptr;
-    int *vurows = nullptr;                                // ragged batches: per-filter rows of the current visit (written by vu_prepare)
-    int *sprows = nullptr;                                // ... and per (track, filter) record of the speculative loop
-    int vu_rows = 0;
-    // speculative frame loop: per (track, filter) records + per-filter cursor and the update count each record was prepared at
-    double *spH = nullptr, *spv = nullptr, *sppf = nullptr;
-    unsigned char *spactive = nullptr;
-    int *spcursor = nullptr, *spepoch = nullptr;
-    int *spcursor2 = nullptr, *sppub = nullptr;           // fused gate + apply passes: second cursor (ping-pong), published decisions
-    size_t sp_records = 0; int sp_rows = 0;
-    // fused prepare + gate (compact Jacobians live in vuH / spH): the active-column lists of the records
-    int *vuacol = nullptr, *spacol = nullptr;
-    // long-track classes of a ragged visit (ekf_visit.hip, Visit): own stream, events, Jacobian / residual / active buffers
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;    // fork onto / join of the context's second stream (Ctx::aux_stream) inside a visit
-    double *sideH = nullptr, *sidev = nullptr;
-    unsigned char *side_active = nullptr;
-    int side_rows = 0;
-    int *side_acol = nullptr; double *side_dm = nullptr;
-    double *tri_rec = nullptr; int tri_stride = 0;        // factor records of vu_tri_kernel (split form of a visit, r06): [batch][tri_stride]
-    int *err_dev = nullptr;                               // device error word (UpdateArgs::err)
-    double *bH = nullptr, *bv = nullptr; int *brows = nullptr; unsigned char *bany = nullptr; int b_rows = 0;   // batchVisualUpdate: stacked [H; v], rows, flags
-    double *gate_scale = nullptr;                         // [batch] per-filter multiplier of the outlier thresholds inside a frame loop (backend.cpp:1192-1193)
-    bool gate_scale_on = false;                           // set by the frame loop while its visits run with a growth factor != 1
-    int *visit_counts = nullptr, *visit_lists = nullptr;  // compaction lists of a visit: counts {inliers short, long records, inliers long}, lists 3 x [batch]
+
+    // allocated by hv_ekf_create, never regrown
+    struct Fixed {
+        DevBuf<double> m, P, P1, m1, Q, dydx, ws;             // state
+        DevBuf<double> sH, sv, sr, schi2, simu;               // staging for host-pointer calls
+        DevBuf<int> sstatus, sdrop;
+        DevBuf<unsigned char> sactive;
+        size_t sH_cap = 0;
+        DevBuf<int> err_dev;                                  // device error word (UpdateArgs::err)
+        DevBuf<int> visit_counts, visit_lists;                // compaction lists of a visit: counts {inliers short, long records, inliers long}, lists 3 x [batch]
+        DevBuf<int> visit_order;                              // [VISIT_SLOTS][batch] launch_visit_order of the running frame loop, valid while visit_order_ok
+        DevBuf<int> visit_long, visit_long_count;             // ... its long-class lists [VISIT_SLOTS][batch] and their lengths [VISIT_SLOTS]
+        int ensure(const Ekf &e)
+        {
+            const size_t n = e.n, B = e.batch, nn = n * n;
+            sH_cap = nn * B;
+            if (m.alloc(n * B) || P.alloc(nn * B) || P1.alloc(nn * B) || m1.alloc(n * B) || Q.alloc(144 * B) || dydx.alloc(400 * B) ||
+                ws.alloc((2 * n + 1) * n * B) || sH.alloc(sH_cap) || sv.alloc(n * B) || sr.alloc(B) || schi2.alloc(B) ||
+                simu.alloc(7 * HV_EKF_MAX_PREDICT_SAMPLES * B) || sstatus.alloc(B) || sdrop.alloc(B) || sactive.alloc(B) || err_dev.alloc(1) ||
+                visit_counts.alloc(4 * (VISIT_SLOTS + 1)) || visit_order.alloc(VISIT_SLOTS * B) || visit_long.alloc(VISIT_SLOTS * B) ||
+                visit_long_count.alloc(VISIT_SLOTS) || visit_lists.alloc(3 * B)) return HV_ERR_NOMEM;
+            return HV_OK;
+        }
+    } fixed;
+
+    // one track visit (hv_ekf_visual_track_dev, row f3): dense or compact Jacobians and residuals of `cap_rows` rows per filter, regrown
+    // when a longer track arrives; once: point, active flags, the compact Jacobians' column lists, per-filter rows of a ragged visit
+    struct VisitBufs {
+        DevBuf<double> H, v; int cap_rows = 0;
+        DevBuf<double> pf; DevBuf<unsigned char> active; DevBuf<int> acol, rec_rows;
+        int ensure(const Ekf &e, int rows)
+        {
+            if (cap_rows >= rows) return HV_OK;
+            const size_t n = e.n, B = e.batch;
+            cap_rows = 0;
+            if (const int rc = grow_buffers(e.c, {e.c->stream}, {{H, rows * n * B}, {v, rows * B}})) return rc;
+            if (pf.alloc_once(3 * B) || active.alloc_once(B) || acol.alloc_once(n * B) || rec_rows.alloc_once(B)) return HV_ERR_NOMEM;
+            cap_rows = rows;
+            return HV_OK;
+        }
+    } visit;
+
+    // long-track class of a ragged visit (ekf_visit.hip, Visit): compact Jacobians and residuals of `cap_rows` rows; once: active flags,
+    // column lists, block 1's mean step `dm` (zeroed when allocated: r03 advisor, never read uninitialised), and the events of the
+    // fork onto / join of the context's second stream (Ctx::aux_stream) inside a visit
+    struct LongBufs {
+        DevBuf<double> H, v; int cap_rows = 0;
+        DevBuf<unsigned char> active; DevBuf<int> acol; DevBuf<double> dm;
+        hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+        int ensure(const Ekf &e, int rows, hipStream_t main_stream)
+        {
+            Ctx *c = e.c;
+            if (!ev_fork) {
+                HV_HIP(c, hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+                HV_HIP(c, hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+            }
+            if (cap_rows >= rows) return HV_OK;
+            const size_t n = e.n, B = e.batch;
+            cap_rows = 0;
+            if (const int rc = grow_buffers(c, {main_stream, c->aux_stream}, {{H, rows * n * B}, {v, rows * B}})) return rc;
+            if (active.alloc_once(B) || acol.alloc_once(n * B)) return HV_ERR_NOMEM;
+            if (const int rc = ensure_dm(e, main_stream)) return rc;
+            cap_rows = rows;
+            return HV_OK;
+        }
+        // (the speculative loop applies long records through `dm` without the rest of the group)
+        int ensure_dm(const Ekf &e, hipStream_t stream)
+        {
+            if (dm) return HV_OK;
+            const size_t count = (size_t)e.n * e.batch;
+            if (dm.alloc(count)) return HV_ERR_NOMEM;
+            HV_HIP(e.c, hipMemsetAsync(dm, 0, sizeof(double) * count, stream));
+            return HV_OK;
+        }
+    } longc;
+
+    // factor records of vu_tri_kernel (split form of a visit, r06): [batch][stride]
+    struct TriBufs {
+        DevBuf<double> rec; int stride = 0;
+        int ensure(const Ekf &e, int want, hipStream_t main_stream)
+        {
+            if (stride >= want) return HV_OK;
+            Ctx *c = e.c;
+            stride = 0;
+            const GrowSlot g{rec, (size_t)want * e.batch};
+            const int rc = c->aux_stream ? grow_buffers(c, {main_stream, c->aux_stream}, {g}) : grow_buffers(c, {main_stream}, {g});
+            if (rc == HV_OK) stride = want;
+            return rc;
+        }
+    } tri;
+
+    // speculative frame loops and the batch loop: one record per (track, filter) -- compact or dense Jacobian, residual, point, flags,
+    // column list, rows, the update count it was prepared at, published decision -- plus the per-filter cursors (cursor2: ping-pong);
+    // grown on first use of a shape and never shrunk in either dimension (r04 advisor: reallocating to exactly (rec, rows) let
+    // alternating shapes -- a short and a long frame, the speculative and the batch loop -- free and allocate on every call, which a
+    // stream capture cannot hold). The batch loop (batch_rows > 0) adds batchVisualUpdate's stacked [H; v], rows and flags per filter.
+    struct SpecBufs {
+        DevBuf<double> H, v, pf; DevBuf<unsigned char> active; DevBuf<int> cursor, epoch, cursor2, pub, acol, rec_rows;
+        size_t cap_records = 0; int cap_rows = 0;
+        DevBuf<double> bH, bv; DevBuf<int> brows; DevBuf<unsigned char> bany; int b_cap_rows = 0;
+        int ensure(const Ekf &e, size_t records, int rows, int batch_rows = 0)
+        {
+            Ctx *c = e.c;
+            const size_t n = e.n, B = e.batch;
+            if (cap_records < records || cap_rows < rows) {
+                const size_t rec = records > cap_records ? records : cap_records;
+                const size_t r = rows > cap_rows ? rows : cap_rows;
+                cap_records = 0;
+                if (const int rc = grow_buffers(c, {c->stream}, {{H, rec * r * n}, {v, rec * r}, {pf, rec * 3}, {active, rec}, {cursor, B}, {epoch, rec},
+                                                                 {cursor2, B}, {pub, rec}, {acol, rec * n}, {rec_rows, rec}})) return rc;
+                cap_records = rec; cap_rows = (int)r;
+            }
+            if (b_cap_rows < batch_rows) {
+                b_cap_rows = 0;
+                if (const int rc = grow_buffers(c, {c->stream}, {{bH, B * batch_rows * n}, {bv, B * batch_rows}, {brows, B}, {bany, B}})) return rc;
+                b_cap_rows = batch_rows;
+            }
+            return HV_OK;
+        }
+    } spec;
+
+    // [batch] per-filter multiplier of the outlier thresholds inside a frame loop (backend.cpp:1192-1193)
+    struct GateScale {
+        DevBuf<double> scale;
+        bool on = false;                                      // set by the frame loop while its visits run with a growth factor != 1
+        int ensure(const Ekf &e) { return scale.alloc_once(e.batch); }
+    } gate;
+
     // the counts exist once per visit of a frame loop (VISIT_SLOTS x 4 ints, zeroed by ONE memset per frame; visit_slot = the running
     // visit, set by the loop) plus one set for stand-alone visits (zeroed per call): a memset node per visit was 20 more graph nodes
     static constexpr int VISIT_SLOTS = 64;
     int visit_slot = -1;
-    int *visit_order = nullptr;                           // [VISIT_SLOTS][batch] launch_visit_order of the running frame loop, valid while visit_order_ok
-    int *visit_long = nullptr, *visit_long_count = nullptr;   // ... its long-class lists [VISIT_SLOTS][batch] and their lengths [VISIT_SLOTS]
     bool visit_order_ok = false;
 };
 

@@ -122,7 +122,7 @@ static int vu_fill_args(Ekf *e, const hv_vu_params *p, int np, const int *idx, c
     if (!p || !idx || !feat || !vel || np < 2 || np > e->cam + 1) return HV_ERR_INVALID;
     a = hv::VuPrepareArgs{};
     a.batch = e->batch; a.n = e->n; a.np = np; a.stereo = p->useStereo ? 1 : 0;
-    a.m = e->m; a.pose_index = idx; a.features = feat; a.velocities = vel; a.y = y;
+    a.m = e->fixed.m; a.pose_index = idx; a.features = feat; a.velocities = vel; a.y = y;
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) {
         a.imu_to_cam[0][4 * r + c] = p->imuToCamera[4 * r + c];
         a.imu_to_cam[1][4 * r + c] = p->secondImuToCamera[4 * r + c];
@@ -135,7 +135,7 @@ static int vu_fill_args(Ekf *e, const hv_vu_params *p, int np, const int *idx, c
     // adaptive outlier thresholds (ABI 3): the RMSE test applies everywhere the fused gate runs; the per-filter growth only inside a
     // frame loop (visual_frame_dev_impl hands the multiplier array over through Ekf::gate_scale_on)
     a.rmse_thr = p->trackRmseThreshold; a.growth = p->trackOutlierThresholdGrowthFactor;
-    a.gate_scale = e->gate_scale_on ? e->gate_scale : nullptr;
+    a.gate_scale = e->gate.on ? e->gate.scale : nullptr;
     if (!(a.growth > 0.0)) return HV_ERR_INVALID;
     return HV_OK;
 }
@@ -144,7 +144,7 @@ static int vu_fill_args(Ekf *e, const hv_vu_params *p, int np, const int *idx, c
 // the launch reads (R = rd_gate I, already scaled by noiseScale)
 static void vu_fill_fused(const Ekf *e, hv::VuPrepareArgs &a, int fused, double *Hc, int *acol, int np, double rd_gate, double *chi2_dev)
 {
-    a.fused = fused; a.H = nullptr; a.Hc = Hc; a.acol = acol; a.na_max = 7 * np + 1; a.P = e->P;
+    a.fused = fused; a.H = nullptr; a.Hc = Hc; a.acol = acol; a.na_max = 7 * np + 1; a.P = e->fixed.P;
     a.rd_gate = rd_gate; a.noise_scale = e->noise_scale; a.chi2 = chi2_dev;
 }
 
@@ -153,12 +153,12 @@ static void vu_fill_fused(const Ekf *e, hv::VuPrepareArgs &a, int fused, double 
 static const int *vu_fill_spec(Ekf *e, hv::VuPrepareArgs &a, int n_tracks, const int *np_rec_dev, double *pf_dev, int *status_dev,
                                int *gate_status_dev, int *success_counter_dev, int max_successful)
 {
-    a.H = e->spH; a.v = e->spv; a.f = nullptr; a.pf = pf_dev ? pf_dev : e->sppf; a.status = status_dev; a.active = e->spactive;
+    a.H = e->spec.H; a.v = e->spec.v; a.f = nullptr; a.pf = pf_dev ? pf_dev : e->spec.pf; a.status = status_dev; a.active = e->spec.active;
     a.gate_status = gate_status_dev; a.success_counter = success_counter_dev; a.max_successful = max_successful;
-    a.spec_tracks = n_tracks; a.cursor = e->spcursor; a.epoch = e->spepoch;
+    a.spec_tracks = n_tracks; a.cursor = e->spec.cursor; a.epoch = e->spec.epoch;
     if (!np_rec_dev) return nullptr;
-    a.np_rec = np_rec_dev; a.rows_out = e->sprows;
-    return e->sprows;
+    a.np_rec = np_rec_dev; a.rows_out = e->spec.rec_rows;
+    return e->spec.rec_rows;
 }
 
 // the apply launch of a speculative pass (spec 2): per filter the first pending record whose gate said INLIER (gate_in_dev) is applied
@@ -166,9 +166,9 @@ static const int *vu_fill_spec(Ekf *e, hv::VuPrepareArgs &a, int n_tracks, const
 static hv::UpdateRequest spec_apply_request(Ekf *e, int nr, double rd, int n_tracks, const int *gate_in_dev, int *success_counter_dev,
                                             int max_successful, const int *nr_rec)
 {
-    hv::UpdateRequest rq = hv::inlier_update_request(nr, e->n, e->spH, e->spv, rd, e->spactive);
+    hv::UpdateRequest rq = hv::inlier_update_request(nr, e->n, e->spec.H, e->spec.v, rd, e->spec.active);
     rq.gate_in_dev = gate_in_dev; rq.nr_rec_dev = nr_rec;
-    hv::set_spec_pass(rq, 2, n_tracks, e->spcursor, success_counter_dev, max_successful);
+    hv::set_spec_pass(rq, 2, n_tracks, e->spec.cursor, success_counter_dev, max_successful);
     return rq;
 }
 
@@ -198,31 +198,6 @@ static hv::VisitShape visit_shape(const Ekf *e, int np, bool stereo, bool linear
     return v;
 }
 
-// dense or compact Jacobians and residuals of one visit of `rows` rows per filter (regrown when a longer track arrives), and the
-// point / active-flag / column-list buffers that are allocated with them once
-static int ensure_visit_buffers(Ekf *e, int rows)
-{
-    if (e->vu_rows >= rows) return HV_OK;
-    Ctx *c = e->c;
-    e->vu_rows = 0;
-    if (const int rc = hv::grow_buffers(c, {c->stream}, {{e->vuH, sizeof(double) * (size_t)rows * e->n * e->batch}, {e->vuv, sizeof(double) * (size_t)rows * e->batch}})) return rc;
-    if (!e->vupf) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vupf), sizeof(double) * 3 * e->batch));
-    if (!e->vuactive) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuactive), e->batch));
-    if (!e->vuacol) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vuacol), sizeof(int) * (size_t)e->n * e->batch));
-    e->vu_rows = rows;
-    return HV_OK;
-}
-
-// block 1's mean step of the long class's block updates: allocated once, zeroed on `stream` (r03 advisor: never read uninitialised)
-static int ensure_side_dm(Ekf *e, hipStream_t stream)
-{
-    if (e->side_dm) return HV_OK;
-    Ctx *c = e->c;
-    HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->side_dm), sizeof(double) * (size_t)e->n * e->batch));
-    HV_HIP(c, hipMemsetAsync(e->side_dm, 0, sizeof(double) * (size_t)e->n * e->batch, stream));
-    return HV_OK;
-}
-
 // One track visit of a session with a hybrid map (odometry.hybridMapSize > 0; backend.cpp:1016, 1075-1082, 1146, 1160-1168):
 //   map_update_dev [batch]: the map point a mapPointUpdate track belongs to (>= 0) -- the point is read from the state, status
 //                           HV_TRI_HYBRID, H carries dip R in the point's columns -- or -1 for a pose-trail track;
@@ -243,21 +218,21 @@ int hv_ekf_visual_track_hybrid_dev(hv_ekf *h, const hv_vu_params *p, int np, con
     if (a.rmse_thr >= 0.0) return HV_ERR_UNSUPPORTED;                  // (the dense gate has no RMSE test)
     const int rows = 2 * np * (a.stereo ? 2 : 1);
     if (rows > e->max_rows || rows >= HV_CHI2INV95_N) return HV_ERR_INVALID;
-    rc = ensure_visit_buffers(e, rows);
+    rc = e->visit.ensure(*e, rows);
     if (rc != HV_OK) return rc;
     const double ns = e->noise_scale;
-    double *pf = pf_dev ? pf_dev : e->vupf;
-    a.H = e->vuH; a.v = e->vuv; a.f = nullptr; a.pf = pf; a.status = status_dev; a.active = e->vuactive; a.gate_status = gate_status_dev;
+    double *pf = pf_dev ? pf_dev : e->visit.pf;
+    a.H = e->visit.H; a.v = e->visit.v; a.f = nullptr; a.pf = pf; a.status = status_dev; a.active = e->visit.active; a.gate_status = gate_status_dev;
     a.map_index = map_update_dev; a.map_base = e->n - e->map_dim;
     rc = hv::launch_vu_prepare(c, a);
     if (rc != HV_OK) return rc;
     // visualTrackOutlierCheck, then -- per filter -- insertMapPoint or updateVisualTrack where it passed
-    rc = hv::ekf_launch_update(e, hv::gate_request(rows, e->n, e->vuH, e->vuv, r_gate * r_gate * ns, chi2_dev, gate_status_dev, e->vuactive));
+    rc = hv::ekf_launch_update(e, hv::gate_request(rows, e->n, e->visit.H, e->visit.v, r_gate * r_gate * ns, chi2_dev, gate_status_dev, e->visit.active));
     if (rc != HV_OK) return rc;
-    hipLaunchKernelGGL(hv::ekf_hybrid_insert_kernel, dim3(e->batch), dim3(256), 0, c->stream, e->n, e->n - e->map_dim, e->m, e->P, e->vuactive,
-                       gate_status_dev, map_update_dev, map_offer_dev, pf, e->sactive);
+    hipLaunchKernelGGL(hv::ekf_hybrid_insert_kernel, dim3(e->batch), dim3(256), 0, c->stream, e->n, e->n - e->map_dim, e->fixed.m, e->fixed.P, e->visit.active,
+                       gate_status_dev, map_update_dev, map_offer_dev, pf, e->fixed.sactive);
     HV_HIP(c, hipGetLastError());
-    return hv::ekf_launch_update(e, hv::inlier_update_request(rows, e->n, e->vuH, e->vuv, r_update * r_update * ns, e->sactive, gate_status_dev));
+    return hv::ekf_launch_update(e, hv::inlier_update_request(rows, e->n, e->visit.H, e->visit.v, r_update * r_update * ns, e->fixed.sactive, gate_status_dev));
 }
 
 // What the launch sequences of one visit share (visual_track_dev_impl): the shape, the thresholds, the compaction lists, the outputs.
@@ -272,35 +247,6 @@ struct Visit {
     int *gate_status_dev, *success_counter_dev;
     double *chi2_dev;
 
-    // buffers of the long class: compact Jacobians, residuals, column lists, active flags, block 1's mean step; the fork / join events
-    int ensure_long()
-    {
-        if (!e->ev_fork) {
-            HV_HIP(c, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-            HV_HIP(c, hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-        }
-        if (e->side_rows >= rows) return HV_OK;
-        e->side_rows = 0;
-        if (const int rc = hv::grow_buffers(c, {main_stream, c->aux_stream}, {{e->sideH, sizeof(double) * (size_t)rows * e->n * e->batch}, {e->sidev, sizeof(double) * (size_t)rows * e->batch}})) return rc;
-        if (!e->side_active) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->side_active), e->batch));
-        if (!e->side_acol) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->side_acol), sizeof(int) * (size_t)e->n * e->batch));
-        if (const int rc = ensure_side_dm(e, main_stream)) return rc;
-        e->side_rows = rows;
-        return HV_OK;
-    }
-
-    // factor records of the split form (knob ekf_split_tri, r06): vu_tri_kernel -> record -> record-fed gate
-    int ensure_tri()
-    {
-        const int stride = hv::vu_tri_rec_stride(np, ncam);
-        if (e->tri_stride >= stride) return HV_OK;
-        e->tri_stride = 0;
-        const hv::GrowSlot rec{e->tri_rec, sizeof(double) * (size_t)stride * e->batch};
-        const int rc = c->aux_stream ? hv::grow_buffers(c, {main_stream, c->aux_stream}, {rec}) : hv::grow_buffers(c, {main_stream}, {rec});
-        if (rc == HV_OK) e->tri_stride = stride;
-        return rc;
-    }
-
     // the gate launch `g` of one length class in split form: the triangulation front first, on the same stream; false = not a shape
     // the split form serves (the caller issues the fused launch)
     // phase: 0 = both launches, 1 = the triangulation only, 2 = the gate only (one-stream visits interleave the two classes' launches:
@@ -308,8 +254,8 @@ struct Visit {
     bool split_launch(hv::VuPrepareArgs &g, hipStream_t stream, int *rc_out, int phase = 0)
     {
         if (!hv::vu_split_supported(c, g, g.fused)) return false;
-        int rc2 = ensure_tri();
-        g.tri_rec = e->tri_rec; g.tri_stride = e->tri_stride;
+        int rc2 = e->tri.ensure(*e, hv::vu_tri_rec_stride(np, ncam), main_stream);
+        g.tri_rec = e->tri.rec; g.tri_stride = e->tri.stride;
         if (rc2 == HV_OK && phase != 2) rc2 = hv::launch_vu_tri(c, g, stream);
         if (rc2 == HV_OK && phase != 1) { g.from_rec = 1; rc2 = hv::launch_vu_prepare(c, g, stream); }
         *rc_out = rc2;
@@ -382,16 +328,15 @@ static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const
     if (rc != HV_OK) return rc;
     const int rows = 2 * np * (a.stereo ? 2 : 1);
     if (rows > e->max_rows) return HV_ERR_INVALID;
-    rc = ensure_visit_buffers(e, rows);
+    rc = e->visit.ensure(*e, rows);
     if (rc != HV_OK) return rc;
     // ragged batch (filters with tracks of different lengths, or none, in one visit): np is the longest track = the record stride;
     // the prepare launch writes every filter's row count for the gate / update launch
     const int *nr_rec = nullptr;
     if (np_rec_dev) {
-        if (!e->vurows) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->vurows), sizeof(int) * e->batch));
-        a.np_rec = np_rec_dev; a.rows_out = e->vurows; nr_rec = e->vurows;
+        a.np_rec = np_rec_dev; a.rows_out = e->visit.rec_rows; nr_rec = e->visit.rec_rows;
     }
-    a.H = e->vuH; a.v = e->vuv; a.f = nullptr; a.pf = pf_dev ? pf_dev : e->vupf; a.status = status_dev; a.active = e->vuactive;
+    a.H = e->visit.H; a.v = e->visit.v; a.f = nullptr; a.pf = pf_dev ? pf_dev : e->visit.pf; a.status = status_dev; a.active = e->visit.active;
     a.gate_status = gate_status_dev;                       // preset to NOT_COMPUTED; the gate overwrites it where it runs
     a.success_counter = success_counter_dev; a.max_successful = max_successful;
     const double ns = e->noise_scale;
@@ -407,13 +352,13 @@ static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const
     const bool long_ok = shape.long_ok;
     // compaction lists of this visit (VuPrepareArgs): zeroed here, filled by the kernels, consumed by the launches behind them
     const bool own_counts = e->visit_slot < 0 || e->visit_slot >= Ekf::VISIT_SLOTS;
-    int *counts = e->visit_counts + 4 * (own_counts ? Ekf::VISIT_SLOTS : e->visit_slot);
-    int *cnt_inl = counts, *list_inl = e->visit_lists;
-    Visit vis{e, c, np, rows, ncam, r_gate, r_update, ns, main_stream, counts + 1, e->visit_lists + e->batch, counts + 2,
-              e->visit_lists + 2 * (size_t)e->batch, nr_rec, gate_status_dev, success_counter_dev, chi2_dev};
+    int *counts = e->fixed.visit_counts + 4 * (own_counts ? Ekf::VISIT_SLOTS : e->visit_slot);
+    int *cnt_inl = counts, *list_inl = e->fixed.visit_lists;
+    Visit vis{e, c, np, rows, ncam, r_gate, r_update, ns, main_stream, counts + 1, e->fixed.visit_lists + e->batch, counts + 2,
+              e->fixed.visit_lists + 2 * (size_t)e->batch, nr_rec, gate_status_dev, success_counter_dev, chi2_dev};
     // frame loop with sorted visits (launch_visit_order): the long class's records are known -- longest first -- before the fused launch runs
     const bool presorted = !own_counts && e->visit_order_ok;
-    if (presorted) { vis.cnt_long = e->visit_long_count + e->visit_slot; vis.list_long = e->visit_long + (size_t)e->visit_slot * e->batch; }
+    if (presorted) { vis.cnt_long = e->fixed.visit_long_count + e->visit_slot; vis.list_long = e->fixed.visit_long + (size_t)e->visit_slot * e->batch; }
     if (own_counts) HV_HIP(c, hipMemsetAsync(counts, 0, 4 * sizeof(int), main_stream));
     // Ragged batch with long AND short tracks: two length CLASSES per visit. The short tracks -- 4 of 5 at the reference's defaults, see
     // bench.py sample_track_lengths -- run on the fused two-per-CU kernels, the long ones through the launches above; the records of a visit
@@ -426,7 +371,7 @@ static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const
     // (r03 also had the whole long chain on the second stream -- knob values 1 and 4 -- and the long class enqueued BEHIND the fused
     //  launch -- 2: all measured slower, removed in r04 together with the stream swap they needed.)
     if (np_rec_dev && shape.two_class) {
-        rc = vis.ensure_long();
+        rc = e->longc.ensure(*e, rows, main_stream);
         if (rc != HV_OK) return rc;
         bool use_aux = c->knob.ekf_side_stream != 0 && presorted && c->aux_stream;
         if (use_aux && c->knob.ekf_side_stream == 5) {
@@ -440,17 +385,17 @@ static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const
         }
         hv::VuPrepareArgs s_ = a;                              // class "short": 2 .. np_short poses (and the records without a track)
         s_.np_lo = 2; s_.np_hi = np_short; s_.class_inactive = 1;
-        vu_fill_fused(e, s_, 1, e->vuH, e->vuacol, np, r_gate * r_gate * ns, chi2_dev);
+        vu_fill_fused(e, s_, 1, e->visit.H, e->visit.acol, np, r_gate * r_gate * ns, chi2_dev);
         s_.inl_count = cnt_inl; s_.inl_list = list_inl;
         if (!presorted) { s_.long_count = vis.cnt_long; s_.long_list = vis.list_long; }      // (else nothing to collect)
-        if (presorted) s_.order = e->visit_order + (size_t)e->visit_slot * e->batch;     // (frame loop: sorted once per frame)
+        if (presorted) s_.order = e->fixed.visit_order + (size_t)e->visit_slot * e->batch;     // (frame loop: sorted once per frame)
         hv::VuPrepareArgs l_ = a;
         l_.np_lo = np_short + 1; l_.np_hi = np; l_.class_inactive = 1;
         // fork ... join: every exit between the two goes through the join (a HIP-graph capture must not be left with a dangling fork)
         bool forked = false;
         if (use_aux) {
-            hipError_t he = hipEventRecord(e->ev_fork, main_stream);
-            if (he == hipSuccess) he = hipStreamWaitEvent(c->aux_stream, e->ev_fork, 0);
+            hipError_t he = hipEventRecord(e->longc.ev_fork, main_stream);
+            if (he == hipSuccess) he = hipStreamWaitEvent(c->aux_stream, e->longc.ev_fork, 0);
             if (he != hipSuccess) return hv::hip_fail(c, he, "fork onto the second stream");
             forked = true;
         }
@@ -471,7 +416,7 @@ static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const
             return phase == 1 ? HV_OK : hv::launch_vu_prepare(c, s_, short_stream);
         };
         auto long_phase = [&](hipStream_t stream, int phase) -> int {
-            return vis.long_prepare_gate(l_, e->sideH, e->sidev, e->side_acol, e->side_active, true, stream, phase);
+            return vis.long_prepare_gate(l_, e->longc.H, e->longc.v, e->longc.acol, e->longc.active, true, stream, phase);
         };
         // one-stream sorted visits, knob ekf_long_first: 0 = short class (triangulation, gate) then long class; 1 = long class first;
         // 2 .. 4 (split form, r06) = both triangulations in front of both gates: T long, T short, G long, G short / T short, T long,
@@ -492,26 +437,26 @@ static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const
             if (rc == HV_OK && !long_first) rc = long_phase(main_stream, 0);
         }
         if (forked) {
-            hipError_t he = hipEventRecord(e->ev_join, c->aux_stream);
-            if (he == hipSuccess) he = hipStreamWaitEvent(main_stream, e->ev_join, 0);
+            hipError_t he = hipEventRecord(e->longc.ev_join, c->aux_stream);
+            if (he == hipSuccess) he = hipStreamWaitEvent(main_stream, e->longc.ev_join, 0);
             if (he != hipSuccess && rc == HV_OK) rc = hv::hip_fail(c, he, "join of the second stream");
         }
         if (rc != HV_OK) return rc;
         // the short class's update: issued on its own, or -- knob ekf_dual_update (default 1) -- sharing a grid with the first block
         // update of the long class (the two serve different filters)
-        hv::UpdateRequest short_upd = hv::inlier_update_request(2 * np_short * ncam, e->n, e->vuH, e->vuv, r_update * r_update * ns, e->vuactive, gate_status_dev);
+        hv::UpdateRequest short_upd = hv::inlier_update_request(2 * np_short * ncam, e->n, e->visit.H, e->visit.v, r_update * r_update * ns, e->visit.active, gate_status_dev);
         short_upd.success_counter_dev = success_counter_dev; short_upd.nr_rec_dev = nr_rec; short_upd.nr_stride = rows;
-        short_upd.compact = hv::compact_columns(e->vuacol, s_.na_max, ncam, cnt_inl, list_inl);
+        short_upd.compact = hv::compact_columns(e->visit.acol, s_.na_max, ncam, cnt_inl, list_inl);
         const bool pair = c->knob.ekf_dual_update != 0;
         if (!pair) { rc = hv::ekf_launch_update(e, short_upd); if (rc != HV_OK) return rc; }
-        return vis.long_updates(e->sideH, e->sidev, e->side_acol, e->side_active, e->side_dm, pair ? &short_upd : nullptr);
+        return vis.long_updates(e->longc.H, e->longc.v, e->longc.acol, e->longc.active, e->longc.dm, pair ? &short_upd : nullptr);
     }
     if (long_ok && np > np_short) {                            // every record of the launch may be long (uniform 12 .. 21 stereo poses, or ragged)
-        rc = vis.ensure_long();
+        rc = e->longc.ensure(*e, rows, main_stream);
         if (rc != HV_OK) return rc;
-        rc = vis.long_prepare_gate(a, e->vuH, e->vuv, e->vuacol, e->vuactive, false, main_stream);
+        rc = vis.long_prepare_gate(a, e->visit.H, e->visit.v, e->visit.acol, e->visit.active, false, main_stream);
         if (rc != HV_OK) return rc;
-        return vis.long_updates(e->vuH, e->vuv, e->vuacol, e->vuactive, e->side_dm, nullptr);
+        return vis.long_updates(e->visit.H, e->visit.v, e->visit.acol, e->visit.active, e->longc.dm, nullptr);
     }
     if (hv::vu_fused_supported(c, e->n, np, a.stereo, e->batch)) {
         // knob ekf_fused_gate: -1 auto / 1 = the gate inside the prepare launch (vu_gate kernels); 2 = its own launch (vu_compact kernels +
@@ -522,21 +467,21 @@ static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const
         const int fg = c->knob.ekf_fused_gate;
         const bool split_gate = fg == 2;
         if (split_gate && (a.rmse_thr >= 0.0 || a.gate_scale)) return HV_ERR_UNSUPPORTED;   // (adaptive thresholds: fused gates only)
-        vu_fill_fused(e, a, split_gate ? 2 : 1, e->vuH, e->vuacol, np, r_gate * r_gate * ns, chi2_dev);
+        vu_fill_fused(e, a, split_gate ? 2 : 1, e->visit.H, e->visit.acol, np, r_gate * r_gate * ns, chi2_dev);
         if (!split_gate) { a.inl_count = cnt_inl; a.inl_list = list_inl; }
         { int rc_s = HV_OK; rc = (!split_gate && vis.split_launch(a, main_stream, &rc_s)) ? rc_s : hv::launch_vu_prepare(c, a); }
         if (rc != HV_OK) return rc;
         if (split_gate) {
             hv::SparseGateRequest g;
-            g.np = np; g.ncam = a.stereo ? 2 : 1; g.Hc_dev = e->vuH; g.v_dev = e->vuv; g.acol_dev = e->vuacol; g.nr_rec_dev = nr_rec;
-            g.active_dev = e->vuactive; g.rd = a.rd_gate; g.chi2_dev = chi2_dev; g.status_dev = gate_status_dev;
+            g.np = np; g.ncam = a.stereo ? 2 : 1; g.Hc_dev = e->visit.H; g.v_dev = e->visit.v; g.acol_dev = e->visit.acol; g.nr_rec_dev = nr_rec;
+            g.active_dev = e->visit.active; g.rd = a.rd_gate; g.chi2_dev = chi2_dev; g.status_dev = gate_status_dev;
             g.inl_count = cnt_inl; g.inl_list = list_inl;
             rc = hv::ekf_launch_sparse_gate(e, g);
             if (rc != HV_OK) return rc;
         }
-        hv::UpdateRequest u = hv::inlier_update_request(rows, e->n, e->vuH, e->vuv, r_update * r_update * ns, e->vuactive, gate_status_dev);
+        hv::UpdateRequest u = hv::inlier_update_request(rows, e->n, e->visit.H, e->visit.v, r_update * r_update * ns, e->visit.active, gate_status_dev);
         u.success_counter_dev = success_counter_dev; u.nr_rec_dev = nr_rec;
-        u.compact = hv::compact_columns(e->vuacol, a.na_max, a.stereo ? 2 : 1, cnt_inl, list_inl);
+        u.compact = hv::compact_columns(e->visit.acol, a.na_max, a.stereo ? 2 : 1, cnt_inl, list_inl);
         return hv::ekf_launch_update(e, u);
     }
     // (the dense kernels below know neither the RMSE test nor the per-filter threshold growth)
@@ -549,15 +494,15 @@ static int visual_track_dev_impl(hv_ekf *h, const hv_vu_params *p, int np, const
     // knob ekf_stream_gate = 1 (experiment): the streaming gate kernel (two filters per CU) for everybody, then the
     // register-resident update where the gate passed. Measured at 1024 filters (r02): a rejected track costs 0.110 ms instead of the
     // fused launch's 0.130, an accepted one 0.110 + 0.21 instead of 0.23.
-    hv::UpdateRequest gate = hv::gate_request(rows, e->n, e->vuH, e->vuv, r_gate * r_gate * ns, chi2_dev, gate_status_dev, e->vuactive);
+    hv::UpdateRequest gate = hv::gate_request(rows, e->n, e->visit.H, e->visit.v, r_gate * r_gate * ns, chi2_dev, gate_status_dev, e->visit.active);
     gate.nr_rec_dev = nr_rec;
-    hv::UpdateRequest upd = hv::inlier_update_request(rows, e->n, e->vuH, e->vuv, r_update * r_update * ns, e->vuactive, gate_status_dev);
+    hv::UpdateRequest upd = hv::inlier_update_request(rows, e->n, e->visit.H, e->visit.v, r_update * r_update * ns, e->visit.active, gate_status_dev);
     upd.success_counter_dev = success_counter_dev; upd.nr_rec_dev = nr_rec;
     if (c->knob.ekf_stream_gate == 1 && !nr_rec) {
         bool done = false;
         hv::GateStreamRequest g;
-        g.nr = rows; g.l = e->n; g.H_dev = e->vuH; g.v_dev = e->vuv; g.rd = r_gate * r_gate * ns; g.chi2_dev = chi2_dev; g.status_dev = gate_status_dev;
-        g.active_dev = e->vuactive; g.success_counter_dev = success_counter_dev; g.max_successful = max_successful; g.done = &done;
+        g.nr = rows; g.l = e->n; g.H_dev = e->visit.H; g.v_dev = e->visit.v; g.rd = r_gate * r_gate * ns; g.chi2_dev = chi2_dev; g.status_dev = gate_status_dev;
+        g.active_dev = e->visit.active; g.success_counter_dev = success_counter_dev; g.max_successful = max_successful; g.done = &done;
         rc = hv::ekf_launch_gate_stream(e, g);
         if (rc != HV_OK) return rc;
         if (done) return hv::ekf_launch_update(e, upd);
@@ -591,25 +536,6 @@ int hv_ekf_visual_track_limited_dev(hv_ekf *h, const hv_vu_params *p, int np, co
 }
 
 
-// work buffers of the speculative frame loops and the batch loop: one record per (track, filter) -- compact or dense Jacobian, residual,
-// point, flags, column list, rows -- plus the per-filter cursors; grown on first use of a shape and never shrunk in either dimension
-// (r04 advisor: reallocating to exactly (rec, rows) let alternating shapes -- a short and a long frame, the speculative and the batch
-// loop -- free and allocate on every call, which a stream capture cannot hold)
-static int ensure_spec_buffers(Ekf *e, size_t rec, int rows)
-{
-    Ctx *c = e->c;
-    if (e->sp_records >= rec && e->sp_rows >= rows) return HV_OK;
-    rec = std::max(rec, e->sp_records); rows = std::max(rows, e->sp_rows);
-    const size_t B = (size_t)e->batch;
-    e->sp_records = 0;
-    if (const int rc = hv::grow_buffers(c, {c->stream}, {
-        {e->spH, sizeof(double) * rec * rows * e->n}, {e->spv, sizeof(double) * rec * rows}, {e->sppf, sizeof(double) * rec * 3},
-        {e->spactive, rec}, {e->spcursor, sizeof(int) * B}, {e->spepoch, sizeof(int) * rec}, {e->spcursor2, sizeof(int) * B},
-        {e->sppub, sizeof(int) * rec}, {e->spacol, sizeof(int) * rec * e->n}, {e->sprows, sizeof(int) * rec}})) return rc;
-    e->sp_records = rec; e->sp_rows = rows;
-    return HV_OK;
-}
-
 static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks, int np, const int *np_rec_dev, const int *idx,
                                  const double *feat, const double *vel,
                             const double *y, double r_gate, double r_update, int *status_dev, int *gate_status_dev, double *chi2_dev,
@@ -625,12 +551,12 @@ static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks,
     // adaptive outlier thresholds (backend.cpp:994-996,1192-1193): every filter starts the frame at the base thresholds; a rejected
     // track multiplies its filter's thresholds for the tracks behind it. Kept per filter on the device, reset here.
     const bool adaptive = p && p->trackOutlierThresholdGrowthFactor != 1.0;
-    struct ScaleScope { Ekf *e; ~ScaleScope() { e->gate_scale_on = false; } } scale_scope{e};
+    struct ScaleScope { Ekf *e; ~ScaleScope() { e->gate.on = false; } } scale_scope{e};
     if (adaptive) {
-        if (!e->gate_scale) HV_HIP(c, hipMalloc(reinterpret_cast<void **>(&e->gate_scale), sizeof(double) * B));
-        hipLaunchKernelGGL(hv::fill_doubles_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, e->gate_scale, (int)B, 1.0);
+        if (const int rc_gs = e->gate.ensure(*e)) return rc_gs;
+        hipLaunchKernelGGL(hv::fill_doubles_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, e->gate.scale, (int)B, 1.0);
         HV_HIP(c, hipGetLastError());
-        e->gate_scale_on = true;
+        e->gate.on = true;
     }
     // Few sequences (one, for the reference's `main`): the frame is latency bound -- 20 dependent visits of a ~26 us prepare and a
     // ~34 us gate. While the GPU has idle CUs the loop is run SPECULATIVELY instead: a pass prepares and gates
@@ -647,27 +573,27 @@ static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks,
     if (!c->knob.ekf_no_speculation && !adaptive && n_tracks >= 2 && B * (size_t)n_tracks <= (size_t)c->num_cus && rows > 48 && p && idx && feat && vel && y &&
         c->knob.ekf_spec_split == 0 && c->knob.ekf_spec_mode != 3 && c->knob.ekf_long_fused != 0 && visit_shape(e, np, p->useStereo != 0, p->useLinearTriangulation != 0).long_ok) {
         const size_t rec = B * (size_t)n_tracks;
-        if (const int rc_sp = ensure_spec_buffers(e, rec, rows)) return rc_sp;
-        if (const int rc_dm = ensure_side_dm(e, c->stream)) return rc_dm;
-        HV_HIP(c, hipMemsetAsync(e->spcursor, 0, sizeof(int) * B, c->stream));
-        HV_HIP(c, hipMemsetAsync(e->spcursor2, 0xFF, sizeof(int) * B, c->stream));                // sel_io: -1
-        HV_HIP(c, hipMemsetAsync(e->spepoch, 0xFF, sizeof(int) * rec, c->stream));               // -1: nothing prepared yet
+        if (const int rc_sp = e->spec.ensure(*e, rec, rows)) return rc_sp;
+        if (const int rc_dm = e->longc.ensure_dm(*e, c->stream)) return rc_dm;
+        HV_HIP(c, hipMemsetAsync(e->spec.cursor, 0, sizeof(int) * B, c->stream));
+        HV_HIP(c, hipMemsetAsync(e->spec.cursor2, 0xFF, sizeof(int) * B, c->stream));                // sel_io: -1
+        HV_HIP(c, hipMemsetAsync(e->spec.epoch, 0xFF, sizeof(int) * rec, c->stream));               // -1: nothing prepared yet
         hv::VuPrepareArgs a;
         int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
         if (rc != HV_OK) return rc;
         const double ns = e->noise_scale;
         const int ncam = a.stereo ? 2 : 1;
         const int *nr_rec = vu_fill_spec(e, a, n_tracks, np_rec_dev, pf_dev, status_dev, gate_status_dev, success_counter_dev, max_successful);
-        vu_fill_fused(e, a, 3, e->spH, e->spacol, np, r_gate * r_gate * ns, chi2_dev);
+        vu_fill_fused(e, a, 3, e->spec.H, e->spec.acol, np, r_gate * r_gate * ns, chi2_dev);
         // (rows per launch: a whole short record of up to 48 rows, or the longer block -- 2 ceil(rows / 4) rows, the first camera's --
         //  of a long one; 48 for everything visit_shape admits today, rows <= 96)
         hv::UpdateRequest u1 = spec_apply_request(e, std::max(48, 2 * ((rows + 3) / 4)), r_update * r_update * ns, n_tracks, gate_status_dev, success_counter_dev, max_successful, nr_rec);
         u1.nr_stride = rows;
-        u1.compact = hv::compact_columns(e->spacol, a.na_max, ncam);
-        u1.compact.nr_full = rows; u1.compact.dm = e->side_dm; u1.compact.half_auto = 1; u1.compact.sel_io = e->spcursor2;
+        u1.compact = hv::compact_columns(e->spec.acol, a.na_max, ncam);
+        u1.compact.nr_full = rows; u1.compact.dm = e->longc.dm; u1.compact.half_auto = 1; u1.compact.sel_io = e->spec.cursor2;
         hv::UpdateRequest u2 = u1;
         u1.compact.half = 1; u1.compact.gate_rw = gate_status_dev; u1.normalize_all = -1;
-        u2.compact.half = 2; u2.compact.epoch = e->spepoch;
+        u2.compact.half = 2; u2.compact.epoch = e->spec.epoch;
         const int n_pass = (max_successful < n_tracks ? max_successful : n_tracks) + 1;
         for (int pass = 0; pass < n_pass; ++pass) {
             rc = hv::launch_vu_prepare(c, a);
@@ -680,10 +606,10 @@ static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks,
     // (a growth factor != 1 makes the threshold of a track depend on the verdicts of the tracks in front of it: no parallel gating)
     if (!c->knob.ekf_no_speculation && !adaptive && n_tracks >= 2 && B * (size_t)n_tracks <= 256 && e->n <= 160 && rows <= 48 && p && idx && feat && vel && y) {
         const size_t rec = B * (size_t)n_tracks;
-        if (const int rc_sp = ensure_spec_buffers(e, rec, rows)) return rc_sp;
-        HV_HIP(c, hipMemsetAsync(e->spcursor, 0, sizeof(int) * B, c->stream));
-        HV_HIP(c, hipMemsetAsync(e->spcursor2, 0, sizeof(int) * B, c->stream));                   // (ping-pong partner: never read uninitialised)
-        HV_HIP(c, hipMemsetAsync(e->spepoch, 0xFF, sizeof(int) * rec, c->stream));               // -1: nothing prepared yet
+        if (const int rc_sp = e->spec.ensure(*e, rec, rows)) return rc_sp;
+        HV_HIP(c, hipMemsetAsync(e->spec.cursor, 0, sizeof(int) * B, c->stream));
+        HV_HIP(c, hipMemsetAsync(e->spec.cursor2, 0, sizeof(int) * B, c->stream));                   // (ping-pong partner: never read uninitialised)
+        HV_HIP(c, hipMemsetAsync(e->spec.epoch, 0xFF, sizeof(int) * rec, c->stream));               // -1: nothing prepared yet
         hv::VuPrepareArgs a;
         int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
         if (rc != HV_OK) return rc;
@@ -702,8 +628,8 @@ static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks,
         // launch B of form 2, and the second launch of the split form: the first pending inlier of every filter is applied
         hv::UpdateRequest apply = spec_apply_request(e, rows, r_update * r_update * ns, n_tracks, gate_status_dev, success_counter_dev, max_successful, nr_rec);
         if (!split && spec_mode != 3 && hv::vu_fused_supported(c, e->n, np, a.stereo, e->batch)) {
-            vu_fill_fused(e, a, 1, e->spH, e->spacol, np, r_gate * r_gate * ns, chi2_dev);
-            apply.compact = hv::compact_columns(e->spacol, a.na_max, a.stereo ? 2 : 1);
+            vu_fill_fused(e, a, 1, e->spec.H, e->spec.acol, np, r_gate * r_gate * ns, chi2_dev);
+            apply.compact = hv::compact_columns(e->spec.acol, a.na_max, a.stereo ? 2 : 1);
             for (int pass = 0; pass < n_pass; ++pass) {
                 rc = hv::launch_vu_prepare(c, a);
                 if (rc == HV_OK) rc = hv::ekf_launch_update(e, apply);
@@ -712,9 +638,9 @@ static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks,
             return HV_OK;
         }
         if (a.rmse_thr >= 0.0) return HV_ERR_UNSUPPORTED;             // (the dense pass forms have no RMSE test)
-        if (!split) HV_HIP(c, hipMemsetAsync(e->sppub, 0, sizeof(int) * rec, c->stream));
-        int *cur = e->spcursor, *nxt = e->spcursor2;
-        hv::UpdateRequest gate = hv::gate_request(rows, e->n, e->spH, e->spv, r_gate * r_gate * ns, chi2_dev, gate_status_dev, e->spactive);
+        if (!split) HV_HIP(c, hipMemsetAsync(e->spec.pub, 0, sizeof(int) * rec, c->stream));
+        int *cur = e->spec.cursor, *nxt = e->spec.cursor2;
+        hv::UpdateRequest gate = hv::gate_request(rows, e->n, e->spec.H, e->spec.v, r_gate * r_gate * ns, chi2_dev, gate_status_dev, e->spec.active);
         gate.nr_rec_dev = nr_rec;
         for (int pass = 0; pass < n_pass; ++pass) {
             a.cursor = cur;
@@ -725,7 +651,7 @@ static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks,
                 hv::UpdateRequest both = gate;                        // form 3: gate + hand-shake + apply, the cursor ping-pongs
                 both.mode = 3; both.normalize_all = 1; both.rd1 = r_update * r_update * ns; both.two_r_done = &fused;
                 hv::set_spec_pass(both, 3, n_tracks, cur, success_counter_dev, max_successful);
-                both.cursor_out_dev = nxt; both.pub_dev = e->sppub; both.pass_id = pass + 1;
+                both.cursor_out_dev = nxt; both.pub_dev = e->spec.pub; both.pass_id = pass + 1;
                 rc = hv::ekf_launch_update(e, both);
                 if (rc != HV_OK) return rc;
                 if (fused) { int *sw = cur; cur = nxt; nxt = sw; continue; }
@@ -741,7 +667,7 @@ static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks,
         }
         return HV_OK;
     }
-    HV_HIP(c, hipMemsetAsync(e->visit_counts, 0, 4 * sizeof(int) * Ekf::VISIT_SLOTS, c->stream));
+    HV_HIP(c, hipMemsetAsync(e->fixed.visit_counts, 0, 4 * sizeof(int) * Ekf::VISIT_SLOTS, c->stream));
     // ragged visits with two length classes: the short class's fused launches take their records longest track first (one sort per frame)
     e->visit_order_ok = false;
     // (many filters only: below one workgroup per CU nothing queues, and the sort, the fork and the join are pure launch overhead --
@@ -750,7 +676,7 @@ static int visual_frame_dev_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks,
         // (only where the visits really run as two length classes: 12 stereo poses = 48 rows still ride the short class -- r03 advisor)
         const hv::VisitShape shape = visit_shape(e, np, p->useStereo != 0, p->useLinearTriangulation != 0);
         if (shape.two_class) {
-            const int rc = hv::launch_visit_order(c, n_tracks, B, np_rec_dev, 2, shape.np_short, np, e->visit_order, e->visit_long, e->visit_long_count);
+            const int rc = hv::launch_visit_order(c, n_tracks, B, np_rec_dev, 2, shape.np_short, np, e->fixed.visit_order, e->fixed.visit_long, e->fixed.visit_long_count);
             if (rc != HV_OK) return rc;
             e->visit_order_ok = true;
         }
@@ -808,31 +734,25 @@ int hv_ekf_visual_frame_batch_dev(hv_ekf *h, const hv_vu_params *p, int n_tracks
     const hv::VisitShape shape = visit_shape(e, np, p->useStereo != 0, p->useLinearTriangulation != 0);
     const bool long_build = rows > 48;
     if (long_build ? !(shape.long_ok && c->knob.ekf_long_fused != 0) : !hv::vu_fused_supported(c, e->n, np, p->useStereo != 0, (int)rec)) return HV_ERR_UNSUPPORTED;
-    if (const int rc_sp = ensure_spec_buffers(e, rec, rows)) return rc_sp;
-    if (e->b_rows < max_update_rows) {
-        e->b_rows = 0;
-        if (const int rc_b = hv::grow_buffers(c, {c->stream}, {{e->bH, sizeof(double) * B * max_update_rows * e->n}, {e->bv, sizeof(double) * B * max_update_rows},
-                                                               {e->brows, sizeof(int) * B}, {e->bany, B}})) return rc_b;
-        e->b_rows = max_update_rows;
-    }
+    if (const int rc_sp = e->spec.ensure(*e, rec, rows, max_update_rows)) return rc_sp;
     HV_HIP(c, hipMemsetAsync(success_counter_dev, 0, sizeof(int) * B, c->stream));
-    HV_HIP(c, hipMemsetAsync(e->spcursor, 0, sizeof(int) * B, c->stream));
-    HV_HIP(c, hipMemsetAsync(e->spepoch, 0xFF, sizeof(int) * rec, c->stream));
-    HV_HIP(c, hipMemsetAsync(e->spcursor2, 0xFF, sizeof(int) * B, c->stream));               // carry: -1
+    HV_HIP(c, hipMemsetAsync(e->spec.cursor, 0, sizeof(int) * B, c->stream));
+    HV_HIP(c, hipMemsetAsync(e->spec.epoch, 0xFF, sizeof(int) * rec, c->stream));
+    HV_HIP(c, hipMemsetAsync(e->spec.cursor2, 0xFF, sizeof(int) * B, c->stream));               // carry: -1
     hv::VuPrepareArgs a;
     int rc = vu_fill_args(e, p, np, idx, feat, vel, y, a);
     if (rc != HV_OK) return rc;
     const double ns = e->noise_scale;
     const int *nr_rec = vu_fill_spec(e, a, n_tracks, np_rec_dev, pf_dev, status_dev, gate_status_dev, success_counter_dev, max_successful);
-    vu_fill_fused(e, a, long_build ? 3 : 1, e->spH, e->spacol, np, r_gate * r_gate * ns, chi2_dev);
+    vu_fill_fused(e, a, long_build ? 3 : 1, e->spec.H, e->spec.acol, np, r_gate * r_gate * ns, chi2_dev);
     hv::BatchAssembleArgs g{};
     g.n = e->n; g.n_tracks = n_tracks; g.batch = e->batch; g.max_rows = max_update_rows; g.max_successful = max_successful;
-    g.rows_stride = rows; g.na_max = a.na_max; g.ncam = ncam; g.Hc = e->spH; g.v = e->spv; g.acol = e->spacol; g.nr_rec = nr_rec;
-    g.active = e->spactive; g.gate = gate_status_dev; g.cursor = e->spcursor; g.success_counter = success_counter_dev; g.carry = e->spcursor2;
-    g.Hd = e->bH; g.vd = e->bv; g.rows_out = e->brows; g.any_out = e->bany;
+    g.rows_stride = rows; g.na_max = a.na_max; g.ncam = ncam; g.Hc = e->spec.H; g.v = e->spec.v; g.acol = e->spec.acol; g.nr_rec = nr_rec;
+    g.active = e->spec.active; g.gate = gate_status_dev; g.cursor = e->spec.cursor; g.success_counter = success_counter_dev; g.carry = e->spec.cursor2;
+    g.Hd = e->spec.bH; g.vd = e->spec.bv; g.rows_out = e->spec.brows; g.any_out = e->spec.bany;
     // updateVisualTrack on the stacked batch of every filter that has one (ragged dense update)
-    hv::UpdateRequest flush = hv::inlier_update_request(max_update_rows, e->n, e->bH, e->bv, r_update * r_update * ns, e->bany);
-    flush.nr_rec_dev = e->brows;
+    hv::UpdateRequest flush = hv::inlier_update_request(max_update_rows, e->n, e->spec.bH, e->spec.bv, r_update * r_update * ns, e->spec.bany);
+    flush.nr_rec_dev = e->spec.brows;
     const int n_pass = max_successful + 1;
     for (int pass = 0; pass < n_pass; ++pass) {
         rc = hv::launch_vu_prepare(c, a);

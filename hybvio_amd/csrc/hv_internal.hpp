@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/hybvio_hip.h"
+#include "dev_buf.hpp"
 
 namespace hv {
 
@@ -83,7 +84,22 @@ int knob_set(Knobs &k, const char *name, int value);   // HV_ERR_INVALID for an 
 int knob_get(const Knobs &k, const char *name, int *value);
 void knobs_from_env(Knobs &k);
 
-struct Ctx {
+// every device buffer a context owns, apart from Ctx so that hv_destroy can release them all in one statement, before the streams go
+struct CtxBuffers {
+    DevBuf<uint8_t> slab;                 // pool_size * slot_bytes
+    DevBuf<const uint8_t *> d_l0_ptr;     // [pool_size]
+    DevBuf<int> d_l0_stride;              // [pool_size]
+    DevBuf<int> d_slots;                  // [4] slot numbers written by set_ints_kernel: [0] the slot of a one-slot pyramid build, [2] / [3] the pair of hv_klt_track
+    // device staging of every synchronous host-pointer entry point: one block (count() = its bytes), carved per call through Stage (below)
+    DevBuf<unsigned char> d_stage;
+    // ingest (f2): per-camera remap tables
+    DevBuf<uint32_t> d_map_xy[HV_INGEST_CAMERAS];
+    DevBuf<float> d_map_xf[HV_INGEST_CAMERAS], d_map_yf[HV_INGEST_CAMERAS];
+    DevBuf<int> d_tile_box[HV_INGEST_CAMERAS];   // per 64 x 16 output tile: source rectangle (remap_tile_kernel)
+    DevBuf<unsigned char> d_ransac_split;        // records of the split rotation-RANSAC launches (rot_ransac.hip), ransac_split_sets of them
+};
+
+struct Ctx : CtxBuffers {
     hv_params p{};
     Knobs knob{};
     PyrLayout L{};
@@ -95,22 +111,10 @@ struct Ctx {
     hipStream_t aux_stream = nullptr;
     int stream_priority = 0;              // 0: default priority; 1: both streams from the device's HIGH-priority queue pool (hv_lanes_create)
     int num_cus = 256;                    // multiProcessorCount of the device
-    uint8_t *slab = nullptr;              // pool_size * slot_bytes
-    const uint8_t **d_l0_ptr = nullptr;   // [pool_size]
-    int *d_l0_stride = nullptr;           // [pool_size]
     std::vector<int> free_slots;
     std::vector<uint8_t> slot_used;
-    int *d_slots = nullptr;               // [4] slot numbers written by set_ints_kernel: [0] the slot of a one-slot pyramid build, [2] / [3] the pair of hv_klt_track
-    // device staging of every synchronous host-pointer entry point: one block, carved per call through Stage (below)
-    unsigned char *d_stage = nullptr;
-    size_t stage_bytes = 0;
-    // ingest (f2): per-camera remap tables
-    uint32_t *d_map_xy[HV_INGEST_CAMERAS] = {};
-    float *d_map_xf[HV_INGEST_CAMERAS] = {}, *d_map_yf[HV_INGEST_CAMERAS] = {};
     int map_stride = 0;
-    int *d_tile_box[HV_INGEST_CAMERAS] = {};   // per 64 x 16 output tile: source rectangle (remap_tile_kernel)
     bool map_tiled[HV_INGEST_CAMERAS] = {};
-    unsigned char *d_ransac_split = nullptr;   // records of the split rotation-RANSAC launches (rot_ransac.hip), ransac_split_sets of them
     int ransac_split_sets = 0;
     std::string last_error;
     bool profiling = false;
@@ -125,19 +129,10 @@ Ctx *ctx_of(hv_ctx *h);
         if (e__ != hipSuccess) return hv::hip_fail((c), e__, #call);     \
     } while (0)
 
-// Growing device buffers: drains `drain` (in order, before anything is freed), frees and nulls every slot, allocates them again at
-// their new sizes. The caller tests whether growth is needed, zeroes the group's capacity field before the call and sets it after
-// an HV_OK, so that a failure in the middle leaves a group that reads as empty.
-struct GrowSlot {
-    void **slot; size_t bytes;
-    template <class T> GrowSlot(T *&p, size_t b) : slot(reinterpret_cast<void **>(&p)), bytes(b) {}
-};
+// grow_buffers (dev_buf.hpp) with the drain spelled as streams: synchronised in order, before anything is freed
 inline int grow_buffers(Ctx *c, std::initializer_list<hipStream_t> drain, std::initializer_list<GrowSlot> slots)
 {
-    for (hipStream_t s : drain) HV_HIP(c, hipStreamSynchronize(s));
-    for (const GrowSlot &g : slots) if (*g.slot) { (void)hipFree(*g.slot); *g.slot = nullptr; }
-    for (const GrowSlot &g : slots) HV_HIP(c, hipMalloc(g.slot, g.bytes));
-    return HV_OK;
+    return grow_buffers([&]() -> int { for (hipStream_t s : drain) HV_HIP(c, hipStreamSynchronize(s)); return HV_OK; }, slots);
 }
 
 // Staging of one host-pointer call in the context's arena (Ctx::d_stage): take() every section, reserve() once, then at() for the
@@ -158,12 +153,9 @@ struct Stage {
     }
     int reserve()
     {
-        if (total <= c->stage_bytes) return HV_OK;
-        const size_t cap = total > 2 * c->stage_bytes ? total : 2 * c->stage_bytes;
-        c->stage_bytes = 0;
-        if (const int rc = grow_buffers(c, {c->stream}, {{c->d_stage, cap}})) return rc;
-        c->stage_bytes = cap;
-        return HV_OK;
+        const size_t have = c->d_stage.count();
+        if (total <= have) return HV_OK;
+        return grow_buffers(c, {c->stream}, {{c->d_stage, total > 2 * have ? total : 2 * have}});
     }
     template <class T> T *at(StageSection<T> s) const { return reinterpret_cast<T *>(c->d_stage + s.off); }
 };

@@ -323,7 +323,7 @@ int launch_ingest(Ctx *c, int n, const int *slots_dev, int slot0, const uint8_t 
     a.blocks_per_image = (a.groups + 255u) / 256u;
     const bool tiled = camera >= 0 && !gather_remap(c) && c->map_tiled[camera];
     if (tiled) {
-        a.tile_box = reinterpret_cast<const int4 *>(c->d_tile_box[camera]);
+        a.tile_box = reinterpret_cast<const int4 *>(c->d_tile_box[camera].get());
         a.tiles_x = (a.w + RT_W - 1) / RT_W;
         a.blocks_per_image = (unsigned)a.tiles_x * (unsigned)((a.h + RT_H - 1) / RT_H);
     }
@@ -359,16 +359,20 @@ int hv_ingest_set_undistort_map(hv_ctx *h, int camera, const double *pix_orig_xy
     if (!c || camera < 0 || camera >= HV_INGEST_CAMERAS) return HV_ERR_INVALID;
     const int w = c->L.w[0], hgt = c->L.h[0];
     if (w >= 65535 || hgt >= 65535) return HV_ERR_INVALID;
-    if (c->d_map_xy[camera]) {
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_map_xy[camera]); (void)hipFree(c->d_map_xf[camera]); (void)hipFree(c->d_map_yf[camera]);
-        c->d_map_xy[camera] = nullptr; c->d_map_xf[camera] = c->d_map_yf[camera] = nullptr;
-        if (c->d_tile_box[camera]) { (void)hipFree(c->d_tile_box[camera]); c->d_tile_box[camera] = nullptr; }
-        c->map_tiled[camera] = false;
-    }
-    if (!pix_orig_xy) return HV_OK;                       // rectification off for this camera
+    // the new tables are built and uploaded as locals and replace the camera's only when every step has succeeded: a failure leaves
+    // the camera as it was (an error exit frees the locals); no table at all = rectification off for this camera
+    hv::DevBuf<uint32_t> d_xy;
+    hv::DevBuf<float> d_xf, d_yf;
+    hv::DevBuf<int> d_box;
+    auto install = [&](int stride, bool is_tiled) -> int {
+        HV_HIP(c, hipStreamSynchronize(c->stream));                              // (launches in flight read the old tables)
+        c->d_map_xy[camera] = std::move(d_xy); c->d_map_xf[camera] = std::move(d_xf); c->d_map_yf[camera] = std::move(d_yf);
+        c->d_tile_box[camera] = std::move(d_box);
+        c->map_stride = stride; c->map_tiled[camera] = is_tiled;
+        return HV_OK;
+    };
+    if (!pix_orig_xy) return install(c->map_stride, false);
     const int ms = (w + 3) / 4 * 4;
-    c->map_stride = ms;
     std::vector<uint32_t> xy((size_t)ms * hgt, hv::MAP_INVALID);
     std::vector<float> xf((size_t)ms * hgt, 0.0f), yf((size_t)ms * hgt, 0.0f);
     for (int y = 0; y < hgt; ++y)
@@ -403,18 +407,13 @@ int hv_ingest_set_undistort_map(hv_ctx *h, int camera, const double *pix_orig_xy
             b[0] = cx0; b[1] = ymin; b[2] = pitch; b[3] = nrows | (xmax == w - 1 ? 1 << 16 : 0);
             if (nrows > 256 || nrows * (pitch / 4) > 256 * hv::RT_K) tiled = false;
         }
-    c->map_tiled[camera] = tiled;
-    if (c->d_tile_box[camera]) { (void)hipFree(c->d_tile_box[camera]); c->d_tile_box[camera] = nullptr; }
-    HV_HIP(c, hipMalloc((void **)&c->d_tile_box[camera], boxes.size() * sizeof(int)));
-    HV_HIP(c, hipMemcpy(c->d_tile_box[camera], boxes.data(), boxes.size() * sizeof(int), hipMemcpyHostToDevice));
     const size_t n = (size_t)ms * hgt;
-    HV_HIP(c, hipMalloc((void **)&c->d_map_xy[camera], n * 4));
-    HV_HIP(c, hipMalloc((void **)&c->d_map_xf[camera], n * 4));
-    HV_HIP(c, hipMalloc((void **)&c->d_map_yf[camera], n * 4));
-    HV_HIP(c, hipMemcpy(c->d_map_xy[camera], xy.data(), n * 4, hipMemcpyHostToDevice));
-    HV_HIP(c, hipMemcpy(c->d_map_xf[camera], xf.data(), n * 4, hipMemcpyHostToDevice));
-    HV_HIP(c, hipMemcpy(c->d_map_yf[camera], yf.data(), n * 4, hipMemcpyHostToDevice));
-    return HV_OK;
+    if (d_box.alloc(boxes.size()) || d_xy.alloc(n) || d_xf.alloc(n) || d_yf.alloc(n)) return HV_ERR_NOMEM;
+    HV_HIP(c, hipMemcpy(d_box, boxes.data(), boxes.size() * sizeof(int), hipMemcpyHostToDevice));
+    HV_HIP(c, hipMemcpy(d_xy, xy.data(), n * 4, hipMemcpyHostToDevice));
+    HV_HIP(c, hipMemcpy(d_xf, xf.data(), n * 4, hipMemcpyHostToDevice));
+    HV_HIP(c, hipMemcpy(d_yf, yf.data(), n * 4, hipMemcpyHostToDevice));
+    return install(ms, tiled);
 }
 
 static int ingest_check(Ctx *c, int channels, int camera)

@@ -648,10 +648,9 @@ int download_unstored_gradient(Ctx *c, int slot, int lv, int16_t *grad)
         HV_HIP(c, hipMemcpy(&stride, c->d_l0_stride + slot, sizeof(int), hipMemcpyDeviceToHost));
     }
     if (!src) return HV_ERR_INVALID;
-    uint32_t *tmp = nullptr;
-    int *d_slot = nullptr;
-    if (hipMalloc(&tmp, (size_t)L.dstride[lv] * L.h[lv] * 4) != hipSuccess) return HV_ERR_NOMEM;
-    if (hipMalloc(&d_slot, sizeof(int)) != hipSuccess) { (void)hipFree(tmp); return HV_ERR_NOMEM; }
+    DevBuf<uint32_t> tmp;
+    DevBuf<int> d_slot;
+    if (tmp.alloc((size_t)L.dstride[lv] * L.h[lv]) || d_slot.alloc(1)) return HV_ERR_NOMEM;
     int rc = HV_OK;
     PyrLevelArgs a{};
     a.src_base = src; a.src_step = 0; a.src_stride = stride; a.src_by_slot = 0;
@@ -666,7 +665,6 @@ int download_unstored_gradient(Ctx *c, int slot, int lv, int16_t *grad)
     }
     if (rc == HV_OK && hipMemcpy2D(grad, (size_t)L.w[lv] * 4, tmp, (size_t)L.dstride[lv] * 4, (size_t)L.w[lv] * 4, L.h[lv],
                                    hipMemcpyDeviceToHost) != hipSuccess) rc = HV_ERR_HIP;
-    (void)hipFree(tmp); (void)hipFree(d_slot);
     return rc;
 }
 

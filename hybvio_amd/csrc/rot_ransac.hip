@@ -343,7 +343,7 @@ int rot_ransac_alloc_split(Ctx *c)
 {
     if (c->d_ransac_split) return HV_OK;
     const int sets = std::max(16, c->num_cus / RT_SPLIT_GROUPS);       // every set count the auto rule sends to the split form
-    if (hipMalloc(reinterpret_cast<void **>(&c->d_ransac_split), SPLIT_REC_BYTES * (size_t)sets) != hipSuccess) return HV_ERR_NOMEM;
+    if (c->d_ransac_split.alloc(SPLIT_REC_BYTES * (size_t)sets)) return HV_ERR_NOMEM;
     HV_HIP(c, hipMemsetAsync(c->d_ransac_split, 0, SPLIT_REC_BYTES * (size_t)sets, c->stream));
     c->ransac_split_sets = sets;
     return HV_OK;

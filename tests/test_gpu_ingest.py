@@ -102,6 +102,37 @@ def test_undistort_remap_bit_exact(oracle, shape, kind, ch, knobs=None):
             ctx.ingest_build(s, img, camera=0)
 
 
+def test_replacing_and_removing_a_map_equals_fresh_contexts(oracle):
+    """Map A, ingest, map B on the same context, ingest: every level is byte-equal to a fresh context that was given B only (the old
+    tables are released, the new ones installed whole). Then no map: the camera is refused and the unmapped path is what it was."""
+    h, w = 48, 64
+    img = synth.stereo_sequence(17, w, h, 1)[0][0]
+    map_a = oracle.undistort_map(*_cams(oracle, w, h, "radial"), w, h)
+    map_b = oracle.undistort_map(*_cams(oracle, w, h, "rotated"), w, h)
+    assert not np.array_equal(oracle.undistort_apply(img, *map_a), oracle.undistort_apply(img, *map_b))
+
+    def levels(ctx, camera):
+        s = ctx.acquire()
+        ctx.ingest_build(s, img, camera=camera)
+        out = [a.tobytes() for l in range(ctx.levels) for a in ctx.download(s, l)]
+        ctx.release(s)
+        return out
+
+    with capi.Context(width=w, height=h) as fresh:
+        want_plain = levels(fresh, -1)
+        fresh.ingest_set_undistort_map(0, *map_b)
+        want_b = levels(fresh, 0)
+    with capi.Context(width=w, height=h) as ctx:
+        ctx.ingest_set_undistort_map(0, *map_a)
+        got_a = levels(ctx, 0)
+        ctx.ingest_set_undistort_map(0, *map_b)
+        assert levels(ctx, 0) == want_b and got_a != want_b
+        ctx.ingest_set_undistort_map(0, None)
+        with pytest.raises(capi.HvError):
+            ctx.ingest_build(ctx.acquire(), img, camera=0)
+        assert levels(ctx, -1) == want_plain
+
+
 @pytest.mark.parametrize("gather", INGEST_GATHER[1:])
 def test_edge_taps_and_invalid_pixels_gather(oracle, gather):
     test_edge_taps_and_invalid_pixels(oracle, knobs={"ingest_gather": gather})

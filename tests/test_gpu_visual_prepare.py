@@ -985,6 +985,66 @@ def test_one_filter_batch_through_rising_and_falling_shapes_equals_fresh_batches
         run.close()
 
 
+# Who owns a filter batch's work buffers: 2 filters (n = 160), 2 visits, in the split form's sequential visit loop, so that a ragged
+# frame of 13 poses grows the visit, long-class and factor-record groups and one of 21 poses grows them again
+OWN_B, OWN_K, OWN_SEED = 2, 2, 977
+
+
+def test_batches_on_one_context_keep_their_buffers_apart(oracle):
+    """Two batches on one context run the same ragged frame (np_max 13); the first is closed; the survivor runs a frame of np_max 21.
+    A third batch created afterwards runs the same two frames: statuses, success counters, means and covariances are byte-identical
+    to the survivor's -- no buffer of the survivor was freed with the first batch, or moved while a frame used it."""
+    import torch
+    rng = np.random.default_rng(OWN_SEED)
+    T1, T2, means, _, _, _ = _random_tracks(oracle, rng, OWN_B, GROW_TRAIL, 6, True, bad_fraction=0.0)
+    o = oracle.Ekf(oracle.ekf_default_params(cameraTrailLength=GROW_TRAIL))
+    assert o.n == 160
+    P0 = o.P.copy() * 1e-6 + np.eye(o.n) * 1e-4
+    vp = capi.vu_default_params(imu_to_camera=T1, second_imu_to_camera=T2)
+    frames = {np_max: _ragged_frame(oracle, rng, means, GROW_TRAIL, OWN_K, np_max, True)[:5] for np_max in (13, 21)}
+    assert all((f[0] > 12).any() and ((f[0] >= 2) & (f[0] <= 12)).any() for f in frames.values())          # both length classes in either frame
+    with capi.Context(width=64, height=64) as ctx:
+        for k, v in GROW_KNOBS["split_tri"].items():
+            ctx.set_knob(k, v)
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+
+        def batch():
+            g = capi.EkfBatch(ctx, capi.ekf_default_params(cameraTrailLength=GROW_TRAIL), OWN_B)
+            for b in range(OWN_B):
+                g.set_state(b, means[b], P0)
+            return g
+
+        def frame(g, np_max):
+            dev = [torch.from_numpy(np.array(a, dt, order="C")).cuda()
+                   for a, dt in zip(frames[np_max], (np.int32, np.int32, np.float64, np.float64, np.float64))]
+            st = torch.full((OWN_K, OWN_B, 2), -9, dtype=torch.int32, device="cuda"); gs = torch.full((OWN_K, OWN_B), -9, dtype=torch.int32, device="cuda")
+            counter = torch.full((OWN_B,), 77, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            g.visual_frame_ragged_dev(vp, OWN_K, np_max, *[x.data_ptr() for x in dev], 1.5, 0.05, st.data_ptr(), gs.data_ptr(), counter.data_ptr(), OWN_K)
+            torch.cuda.synchronize()
+            assert g.frame_error() == 0
+            out = [x.cpu().numpy().tobytes() for x in (st, gs, counter)] + [a.tobytes() for b in range(OWN_B) for a in g.get_state(b)]
+            return out, gs.cpu().numpy()
+
+        first, survivor = batch(), batch()
+        try:
+            first_13, _ = frame(first, 13)
+            survivor_13, gs_13 = frame(survivor, 13)
+            first.close()
+            survivor_21, gs_21 = frame(survivor, 21)
+            third = batch()
+            try:
+                third_13, _ = frame(third, 13)
+                third_21, _ = frame(third, 21)
+            finally:
+                third.close()
+        finally:
+            survivor.close()
+    assert (gs_13 == 0).any() or (gs_21 == 0).any()                  # a track was applied: the frames moved the state
+    assert first_13 == survivor_13
+    assert third_13 == survivor_13 and third_21 == survivor_21
+
+
 def _batch_loop_case(oracle, seed, B, np_max, K, quota, max_rows, stereo):
     """Inputs of one hv_ekf_visual_frame_batch_dev call over B distinct filters, and `verify(g, st, gs, counts)`: the oracle's
     batchVisualUpdate loop per filter (backend.cpp:1001-1010,1169-1183,1255-1262) against what the device left."""
