@@ -30,7 +30,7 @@ f64p = C.POINTER(C.c_double)
 
 HV_MAX_LEVELS = 6
 (K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI,
- K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL) = range(16)
+ K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL, K_TRACK_TABLE) = range(17)
 RANSAC5_MAX_ITERS = 75
 # RansacResult::Type as reported by hv_hybrid_ransac_lk_batch_dev
 R5_TYPE_SKIPPED, R5_TYPE_R2, R5_TYPE_R5 = 0, 1, 3
@@ -40,6 +40,7 @@ SUBPIX_MAX_WIN = 16
 ST_TRACKED, ST_NEW, ST_FAILED_FLOW, ST_RANSAC_OUTLIER, ST_FLOW_OUT_OF_RANGE = 0, 1, 2, 3, 4
 ST_OUT_OF_RANGE, ST_FAILED_EPIPOLAR_CHECK, ST_CULLED, ST_BLACKLISTED = 5, 6, 7, 8
 DETECTION_FILTER_MAX_POINTS = 1024
+TRACKS_MAX_TRACKS = 1024
 DETECT_TAIL_MAX_KEYPOINTS, DETECT_TAIL_MAX_CORNERS, DETECT_TAIL_MAX_PREV, DETECT_TAIL_MAX_TRACKS = 16384, 32768, 4096, 4096
 
 
@@ -77,6 +78,17 @@ class Ransac5Params(C.Structure):
 class StereoGateParams(C.Structure):
     _fields_ = [("maxStereoEpipolarDistance", C.c_float), ("partOfImageToDetectFeatures", C.c_double), ("fisheyeCamera", C.c_int),
                 ("independentStereoOpticalFlow", C.c_int), ("cam0ToCam1", C.c_double * 16)]
+
+
+class TrackTableParams(C.Structure):
+    _fields_ = [("maxTracks", C.c_int), ("maxTrackLength", C.c_int), ("relativeMaskRadius", C.c_double),
+                ("visualStationarityMovementThreshold", C.c_double), ("visualStationarityScoreThreshold", C.c_double)]
+
+
+class TrackTable(C.Structure):
+    """hv_track_table: device pointers owned by the caller (second_xy None = mono)."""
+    _fields_ = [(k, C.c_void_p) for k in ("n_tracks", "ids", "xy", "second_xy", "status", "blacklist", "kf_xy", "kf_valid",
+                                          "frame_num", "mask_steps", "mask_radius", "frame_flags")]
 
 
 class HvError(RuntimeError):
@@ -194,6 +206,13 @@ PROTOTYPES = {
     "hv_track_gate_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(StereoGateParams), C.c_int, C.c_int] + [C.c_void_p] * 9),
     "hv_detection_filter": (C.c_int, [C.c_void_p, C.POINTER(StereoGateParams), C.c_int] + [C.c_void_p] * 9),
     "hv_detection_filter_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(StereoGateParams), C.c_int, C.c_int] + [C.c_void_p] * 10),
+    "hv_track_table_default_params": (None, [C.POINTER(TrackTableParams)]),
+    "hv_tracks_init_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrackTableParams), C.c_int, C.POINTER(TrackTable)]),
+    "hv_tracks_update_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrackTableParams), C.c_int, C.POINTER(TrackTable)] + [C.c_void_p] * 9),
+    "hv_tracks_append_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrackTableParams), C.c_int, C.POINTER(TrackTable), C.c_int]
+                                   + [C.c_void_p] * 4),
+    "hv_tracks_delete_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrackTableParams), C.c_int, C.POINTER(TrackTable), C.c_int]
+                                   + [C.c_void_p] * 2),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -428,6 +447,38 @@ class Context:
                                                       p(out_second_dev), p(n_out_dev)),
                   "hv_detection_filter_batch_dev")
 
+    # ---- device track table: updateTracks, culling, keyframes, new-track append and deleteTrack ----
+    def tracks_init_batch_dev(self, n_sets, table: "TrackTable", params: "TrackTableParams" = None):
+        tp = params if params is not None else track_table_default_params()
+        self._chk(lib().hv_tracks_init_batch_dev(self._h, C.byref(tp), n_sets, C.byref(table)), "hv_tracks_init_batch_dev")
+
+    def tracks_update_batch_dev(self, n_sets, table: "TrackTable", corners_dev, second_corners_dev, track_status_dev, score_dev,
+                                keyframe_dev, mask_xy_dev, n_mask_dev, src_index_dev=0, max_movement_dev=0,
+                                params: "TrackTableParams" = None):
+        """hv_tracks_update_batch_dev (tracker.cpp:527-530, 578-670, 766-777): mask, keyframe, culling, write-back and compaction."""
+        tp = params if params is not None else track_table_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_tracks_update_batch_dev(self._h, C.byref(tp), n_sets, C.byref(table), p(corners_dev), p(second_corners_dev),
+                                                   p(track_status_dev), p(score_dev), p(keyframe_dev), p(mask_xy_dev), p(n_mask_dev),
+                                                   p(src_index_dev), p(max_movement_dev)),
+                  "hv_tracks_update_batch_dev")
+
+    def tracks_append_batch_dev(self, n_sets, table: "TrackTable", max_new, n_new_dev, new_xy_dev, new_second_dev, n_added_dev=0,
+                                params: "TrackTableParams" = None):
+        """hv_tracks_append_batch_dev (tracker.cpp:199, 540-546, 672-719): new tracks, IDs, mask tuning, frame_num."""
+        tp = params if params is not None else track_table_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_tracks_append_batch_dev(self._h, C.byref(tp), n_sets, C.byref(table), max_new, p(n_new_dev), p(new_xy_dev),
+                                                   p(new_second_dev), p(n_added_dev)),
+                  "hv_tracks_append_batch_dev")
+
+    def tracks_delete_batch_dev(self, n_sets, table: "TrackTable", max_ids, n_ids_dev, ids_dev, params: "TrackTableParams" = None):
+        """hv_tracks_delete_batch_dev (deleteTrack, tracker.cpp:726-738)."""
+        tp = params if params is not None else track_table_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_tracks_delete_batch_dev(self._h, C.byref(tp), n_sets, C.byref(table), max_ids, p(n_ids_dev), p(ids_dev)),
+                  "hv_tracks_delete_batch_dev")
+
     # ---- image ingest (f2): colour -> gray and the undistort / rectify remap in front of the pyramid ----
     def ingest_set_undistort_map(self, camera: int, pix_orig=None, valid=None):
         """pix_orig (h, w, 2) f64 = original-image position of every rectified pixel (None removes the table)."""
@@ -610,6 +661,22 @@ def stereo_gate_default_params(**over) -> StereoGateParams:
         else:
             setattr(p, k, v)
     return p
+
+
+def track_table_default_params(**over) -> TrackTableParams:
+    p = TrackTableParams()
+    lib().hv_track_table_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def track_table(**pointers) -> TrackTable:
+    """hv_track_table from device addresses by member name (second_xy omitted or 0: mono)."""
+    t = TrackTable()
+    for k, v in pointers.items():
+        setattr(t, k, v or None)
+    return t
 
 
 def subpix_default_params(**over) -> SubpixParams:

@@ -670,6 +670,94 @@ int hv_detection_filter_batch_dev(hv_ctx *ctx, const hv_stereo_gate_params *p, i
                                   const hv_camera_model *camera1, int32_t *status_dev, float *out_corners_dev,
                                   float *out_second_dev, int *n_out_dev);
 
+/* ---- device track table: updateTracks, culling, keyframes and new-track append (added within ABI 4) -----------------
+ * Replaces the bookkeeping of TrackerImplementation::add / track from the keyframe decision onwards
+ * (src/tracker/tracker.cpp:199-229, 527-558) for n_sets resident sequences: computeVisualStationarity (:578-602) with
+ * computeMaxPixelCoordinateMovement (:21-41), updateTracks (:604-670), setMask (:766-777), detectNewFeatures' append and
+ * ID rule (:672-703, :199), the maskScale tuning (:540-546, changeMaskSize :561-567) and maskRadius (:569-576), the
+ * construction of prevCorners / prevSecondCorners (:548-558), the reset below five tracks (:209-229) with resetAllTracks
+ * (:705-719), and deleteTrack (:726-738). Equal, array for array, to the literal restatement in
+ * tests/track_table_restatement.py; every rule is integer or IEEE arithmetic, so there is no tolerance.
+ * The table is device memory owned by the caller; set s is at s * maxTracks of every per-track array. Entries of a set at
+ * and beyond n_tracks[s] are unspecified, except that kf_valid and blacklist are 0 there after an update.
+ * lastKeyframeCornerByTrackId (an unordered_map keyed by track ID) is the per-slot pair kf_xy / kf_valid: IDs are unique and
+ * an entry is erased exactly when its track is, so a slot that moves with its track under compaction is the same thing.
+ * maskScale only moves by -1.0 and +0.5 inside [-5, 5] and is held as mask_steps = 2 * maskScale; the 21 possible radii
+ * std::round(std::pow(1.3, steps / 2.0) * min(w, h) * relativeMaskRadius), floor 2 (:569-576; w, h = the context's level-0
+ * size), are computed on the host inside each entry and passed to the kernel.
+ * All _dev entries: asynchronous on the context stream, no allocation or synchronisation inside (capturable in a HIP
+ * graph), one workgroup per set. Checks made before the context is looked at: HV_ERR_INVALID for a NULL required pointer
+ * (a table member included; second_xy may be NULL = mono), a negative size, maxTracks < 1, or a stereo / mono mismatch
+ * between the second_* argument and table->second_xy; then HV_ERR_UNSUPPORTED for n_sets > 65535 or maxTracks >
+ * HV_TRACKS_MAX_TRACKS (a call that is both invalid and too large is HV_ERR_INVALID). Counts read from device memory are
+ * clamped to their capacity. */
+#define HV_TRACKS_MAX_TRACKS 1024          /* = HV_DETECTION_FILTER_MAX_POINTS: one workgroup per set */
+typedef struct hv_track_table_params {
+    int maxTracks;                               /* 200    codegen/parameter_definitions.c:262 */
+    int maxTrackLength;                          /* 21     :265 */
+    double relativeMaskRadius;                   /* 0.0667 :308 */
+    double visualStationarityMovementThreshold;  /* 3.0    :111 */
+    double visualStationarityScoreThreshold;     /* 0.95   :113 */
+} hv_track_table_params;
+typedef struct hv_track_table {            /* set s at s * maxTracks of every per-track array */
+    int32_t *n_tracks;     /* [n_sets]               tracks.size() */
+    int32_t *ids;          /* [n_sets][maxTracks]    Feature::id */
+    float   *xy;           /* [..][2]  points[0] = next frame's prevCorners (prev_xy of hv_klt_track_batch_ragged_dev) */
+    float   *second_xy;    /* [..][2]  points[1]; NULL = mono */
+    int32_t *status;       /* Feature::status: NEW (1) when appended, the frame's status after an update, BLACKLISTED (8) after a delete */
+    uint8_t *blacklist;    /* status == BLACKLISTED, in the form hv_track_gate_batch_dev reads */
+    float   *kf_xy;        /* [..][2] */
+    uint8_t *kf_valid;     /* lastKeyframeCornerByTrackId: the entry of the track in this slot, moved with it */
+    int32_t *frame_num;    /* [n_sets] frameNum on entry to add() */
+    int32_t *mask_steps;   /* [n_sets] 2 * maskScale, in [-10, 10] */
+    int32_t *mask_radius;  /* [n_sets] maskRadius() for the NEXT detect: mask_radius_dev of hv_gftt_detect_batch_dev */
+    uint8_t *frame_flags;  /* [n_sets] written by update, read by append: bit 0 = reset frame */
+} hv_track_table;
+void hv_track_table_default_params(hv_track_table_params *p);
+/* Every set becomes a fresh TrackerImplementation (tracker.cpp:165-174): no tracks, frame_num 0, mask_steps 0, mask_radius =
+ * the radius of step 0; kf_valid, blacklist and frame_flags cleared. */
+int hv_tracks_init_batch_dev(hv_ctx *ctx, const hv_track_table_params *p, int n_sets, const hv_track_table *table);
+/* The table step of one frame after the RANSAC filter. corners_dev / second_corners_dev [n_sets][maxTracks][2] = the current
+ * corners of the table's tracks (second: NULL exactly when table->second_xy is), track_status_dev [n_sets][maxTracks] int32
+ * in / out = the statuses hv_hybrid_ransac_lk_batch_dev left, score_dev [n_sets] = its stationarity score (NULL: 0, never
+ * stationary). Per set, with f = frame_num[s] and n = n_tracks[s], in this order:
+ * - reset frame, f == 0 or n < 5 (:201-205, 209, 222-229): the table and its keyframe entries are cleared, n_mask = 0
+ *   (setMask({}, {})), keyframe = 1, max_movement = -1, frame_flags bit 0 set; track_status_dev is untouched. (The
+ *   reference leaves output.keyframe alone in the n < 5 branch; 1 is this library's choice.)
+ * - otherwise setMask first (:492, 766-777): the TRACKED corners in order go to mask_xy_dev [n_sets][maxTracks][2] with
+ *   their count in n_mask_dev [n_sets]; this is before the culling, so culled corners stay in the mask.
+ * - keyframe_dev [n_sets] int32 = (f + 1 < maxTrackLength) || !stationary (:527-528; frameNum is f + 1 there). maxMovement
+ *   (:21-41) runs over the TRACKED tracks with a keyframe entry: the largest binary64 sqrt(dx*dx + dy*dy), dx and dy
+ *   binary32 differences widened to binary64, uncontracted; -1 without such a track, and then not stationary; else
+ *   stationary = score * (maxMovement < visualStationarityMovementThreshold ? 1 : 0) > visualStationarityScoreThreshold.
+ *   max_movement_dev [n_sets] double (NULL ok) receives maxMovement.
+ * - culling, only when n == maxTracks (:621-639): all pairs i < j in generation order with dist2 in the same arithmetic,
+ *   std::stable_sort by dist2, the walk that puts j into a set and CULLED (7) into track_status[j] whatever it held, stopped
+ *   once the set holds more than maxTracks / 20 members. The kernel selects the same tracks without the sort.
+ * - write-back and erase (:641-669): a TRACKED track takes its new points, and its keyframe entry when keyframe is set;
+ *   every other track is erased with its keyframe entry; the survivors are compacted in order (status TRACKED, blacklist
+ *   0); src_index_dev [n_sets][maxTracks] int32 (NULL ok) receives each survivor's old slot; n_tracks is written.
+ * frame_num is not changed here. Every input is read before any output is written, so corners_dev may be table->xy. */
+int hv_tracks_update_batch_dev(hv_ctx *ctx, const hv_track_table_params *p, int n_sets, const hv_track_table *table,
+                               const float *corners_dev, const float *second_corners_dev, int32_t *track_status_dev,
+                               const double *score_dev, int32_t *keyframe_dev, float *mask_xy_dev, int32_t *n_mask_dev,
+                               int32_t *src_index_dev, double *max_movement_dev);
+/* The end of the frame: the pairs hv_detection_filter_batch_dev compacted, new_xy_dev / new_second_dev
+ * [n_sets][max_new][2] with n_new_dev [n_sets] (clamped to [0, max_new]; max_new == 0: no array is read). On a reset frame,
+ * or when missing = maxTracks - n_tracks >= maxTracks / 10 (:686), the first min(n_new, missing) pairs are appended in
+ * order with IDs f * maxTracks + 1, + 2, ... (:199, 692-698), status NEW (1), no keyframe entry. Unless the frame was a
+ * reset frame the mask is tuned from the new count n (:540-546): steps -= 2 when n < (3 * maxTracks) / 4, else steps += 1
+ * when n == maxTracks, clamped to +-10. On every frame mask_radius = radius(steps), frame_num = f + 1 and frame_flags is
+ * cleared. n_added_dev [n_sets] int32 (NULL ok) receives the number appended. */
+int hv_tracks_append_batch_dev(hv_ctx *ctx, const hv_track_table_params *p, int n_sets, const hv_track_table *table,
+                               int max_new, const int32_t *n_new_dev, const float *new_xy_dev, const float *new_second_dev,
+                               int32_t *n_added_dev);
+/* deleteTrack (:726-738) for the ids_dev [n_sets][max_ids] int32 listed per set (n_ids_dev [n_sets], clamped to
+ * [0, max_ids]): the track that carries a listed ID gets status BLACKLISTED (8) and blacklist 1; unknown IDs and repeats
+ * are ignored. */
+int hv_tracks_delete_batch_dev(hv_ctx *ctx, const hv_track_table_params *p, int n_sets, const hv_track_table *table,
+                               int max_ids, const int32_t *n_ids_dev, const int32_t *ids_dev);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
@@ -678,7 +766,8 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_RANSAC5 = 13 /* added within ABI 4: hv_ransac5*, hv_hybrid_ransac_lk_batch_dev */,
        HV_K_STEREO_GATE = 14 /* added within ABI 4: hv_flow_status_batch_dev, hv_track_gate*, hv_detection_filter* */,
        HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
-       HV_K_COUNT = 16 };
+       HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
+       HV_K_COUNT = 17 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
 /* Synchronizes, then returns accumulated device milliseconds and launch count of a kernel class. */
