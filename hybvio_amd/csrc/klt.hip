@@ -235,6 +235,15 @@ __global__ __launch_bounds__(64, WPS) void klt_kernel(KltArgs a)
     float2 guess = make_float2(0.f, 0.f);
     if (a.use_init) guess = a.next_xy[pt];
 
+    // NaN in the previous point or in the guess. The reference converts with cvFloor, which gives INT_MIN for NaN (oracle/pyrlk_oracle.c
+    // cv_floor_f), so a NaN previous point fails the window test of every level and a NaN guess the first iteration's test at level 0
+    // (the epilogue's when max_count is 0): status 0, err 0, the position the start value carried down the levels. The device's
+    // conversion saturates and turns NaN into 0 -- a window inside the image -- so the range tests of the level loop would let it
+    // through. Decided here, once (every lane holds the same point: a scalar condition): such a point runs no level at all, see
+    // level_top below, which leaves no register live in the level loop. Infinite values and values beyond int's range need nothing: saturated, they fail the range tests as INT_MIN does, and the
+    // arithmetic in front of those tests (a scaling by a power of two, - 15) cannot turn them into NaN.
+    const bool nan_in = __builtin_amdgcn_ballot_w64(__builtin_isunordered(pp.x, pp.y) || __builtin_isunordered(guess.x, guess.y)) != 0;
+
     // fast tile staging: lane (st_lr, st_c) = row-in-pass, 4-pixel group; lanes beyond RPI * G repeat the last item
     // (r06: 8-pixel groups, 16-byte loads -- G = 5 lanes per tile row, 12 rows per pass, 3 passes: half the vector-memory instructions
     //  of r01 .. r05's 4-pixel groups / 8-byte loads / 6 passes. The kernel is co-limited by the rate at which a CU's 20 waves get
@@ -250,8 +259,16 @@ __global__ __launch_bounds__(64, WPS) void klt_kernel(KltArgs a)
     int st = 1;
     float errv = 0.f;
     float nx = 0.f, ny = 0.f;
+    int level_top = L.levels - 1;
+    if (nan_in) {
+        const float top = __uint_as_float((127u - (unsigned)level_top) << 23);
+        nx = (a.use_init ? guess.x : pp.x) * top; ny = (a.use_init ? guess.y : pp.y) * top;
+        for (int l = level_top; l > 0; --l) { nx = nx * 2.f; ny = ny * 2.f; }          // the reference's own sequence: subnormals round
+        st = 0;
+        level_top = -1;                                                                 // no level runs
+    }
 
-    for (int level = L.levels - 1; level >= 0; --level) {
+    for (int level = level_top; level >= 0; --level) {
         const float lscale = __uint_as_float((127u - (unsigned)level) << 23);      // 2^-level exactly (levels < 127): no division sequence
         float px = pp.x * lscale, py = pp.y * lscale;
         if (level == L.levels - 1) {

@@ -129,20 +129,29 @@ int hv_pyramid_download(hv_ctx *ctx, int slot, int level, uint8_t *gray, int16_t
  * next_xy is in/out: initial guess when use_initial_flow != 0 (OPTFLOW_USE_INITIAL_FLOW).
  * status: 1 tracked / 0 lost. max_iter_override <= 0 keeps the context value. err may be NULL (the
  * reference discards it: optical_flow.cpp:26); the level-0 range check that can clear status runs
- * either way. Synchronous. */
+ * either way. Synchronous.
+ * Non-finite and out-of-range coordinates (every LK entry): a previous point or a guess with a NaN, an infinite or a
+ * beyond-int-range coordinate is treated as cvFloor treats it on x86 (INT_MIN: outside every window test). Status 0,
+ * err 0, and next_xy is the start value (the guess under use_initial_flow, else the previous point) scaled down to the
+ * coarsest level and doubled back: the input value itself, a NaN coordinate staying NaN. Other points of the call are not
+ * affected. tests/test_gpu_nonfinite.py holds this to the oracle. */
 int hv_klt_track(hv_ctx *ctx, int prev_slot, int next_slot, int n, const float *prev_xy,
                  float *next_xy, uint8_t *status, float *err, int use_initial_flow,
                  int max_iter_override);
 /* Replaces tracker::OpticalFlow::compute (src/tracker/optical_flow.hpp:31-38,
  * optical_flow.cpp:10-59,78-102): runs LK, maps to Feature::Status (track.hpp:9-21:
  * TRACKED=0, FAILED_FLOW=2) and overrides to FLOW_OUT_OF_RANGE=4 outside the level-0 image.
- * corners is in/out (input when use_initial_corners). n == 0 is a no-op. Synchronous. */
+ * corners is in/out (input when use_initial_corners). n == 0 is a no-op. Synchronous.
+ * A lost point whose returned corner has a NaN coordinate (NaN previous point or guess, see hv_klt_track) is FAILED_FLOW:
+ * no comparison of the range test holds for NaN. Infinite and beyond-int-range ones are FLOW_OUT_OF_RANGE. */
 int hv_optical_flow_compute(hv_ctx *ctx, int prev_slot, int cur_slot, int n,
                             const float *prev_corners, float *corners, int32_t *track_status,
                             int use_initial_corners, int override_max_iterations);
 /* Batched: n_pairs independent (prev,next) pyramid pairs with pts_per_pair points each, one
  * launch; point j of pair p is element p*pts_per_pair + j of every array. All arrays are in
- * device memory (err_dev may be NULL); asynchronous. */
+ * device memory (err_dev may be NULL); asynchronous. Non-finite and out-of-range points and guesses: status 0, as
+ * described at hv_klt_track (predicted corners are NaN whenever the pose they come from is); hv_flow_status_batch_dev
+ * then gives FAILED_FLOW for a NaN corner and FLOW_OUT_OF_RANGE for the others, as hv_optical_flow_compute does. */
 int hv_klt_track_batch_dev(hv_ctx *ctx, int n_pairs, const int *prev_slots_dev,
                            const int *next_slots_dev, int pts_per_pair, const float *prev_xy_dev,
                            float *next_xy_dev, uint8_t *status_dev, float *err_dev,

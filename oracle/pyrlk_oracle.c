@@ -61,6 +61,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <float.h>
+#include <limits.h>
 
 #define ORC_MAX_LEVELS 8
 
@@ -249,8 +250,12 @@ int orc_pyramid_copy_deriv(const orc_pyramid *P, int level, int padded, int16_t 
 #define DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
 #define ORC_USE_INITIAL_FLOW 4      /* cv::OPTFLOW_USE_INITIAL_FLOW */
 
-static inline int cv_round_f(float v) { return (int)lrintf(v); }   /* round-half-even */
-static inline int cv_floor_f(float v) { return (int)floorf(v); }
+/* cvRound / cvFloor as OpenCV's x86 builds compute them (cvtss2si / cvttss2si): NaN and every value outside int's range give
+ * INT_MIN, the "integer indefinite". Stated here: the C cast of such a value is undefined. LK's window tests
+ * (x < -win || x >= cols) then fail such a point at every level: status 0, the position the scaled input. */
+static inline int cv_in_int_range(float v) { return v >= -2147483648.f && v < 2147483648.f; }      /* false for NaN */
+static inline int cv_round_f(float v) { return cv_in_int_range(v) ? (int)lrintf(v) : INT_MIN; }     /* round-half-even */
+static inline int cv_floor_f(float v) { const float f = floorf(v); return cv_in_int_range(f) ? (int)f : INT_MIN; }
 
 static inline void bilinear_weights(float a, float b, int *iw00, int *iw01, int *iw10, int *iw11)
 {

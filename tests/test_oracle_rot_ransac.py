@@ -103,6 +103,29 @@ def test_fit_control_flow_draw_consumption_and_first_maximum(oracle):
     assert best3 == 2 and (st3 == 0).all()
 
 
+def nonfinite_ransac_scene(oracle):
+    """40 clean points of the radial pinhole camera, rng(3); 7 of the 9 non-finite / out-of-int-range pairs of
+    test_oracle_pyrlk.NONFINITE_PAIRS in c2[:7], the other two and NaN again in c1[7:10] (shared with tests/test_gpu_nonfinite.py)."""
+    from test_oracle_pyrlk import NONFINITE_PAIRS
+    cam, c1, c2, _, _ = _scene(oracle, np.random.default_rng(3), 40, 0)
+    c2[:7] = NONFINITE_PAIRS[:7]
+    c1[7:10] = NONFINITE_PAIRS[[7, 8, 0]]
+    return cam, c1, c2
+
+
+def test_fit_is_defined_on_non_finite_points(oracle):
+    """The fit has no conversion to int and no index derived from a coordinate: NaN / inf points are never inliers (every comparison
+    with NaN is false), a hypothesis that draws one has inlier count 0, and the result is that of the clean points."""
+    cam, c1, c2 = nonfinite_ransac_scene(oracle)
+    thr = float(np.float32((4.0 * 480 / 720.0) ** 2))
+    draws = oracle.mt19937_draws(4649, 200)
+    st, Rf, best, used = oracle.rot_ransac_fit(c1, c2, cam, cam, draws, thr)
+    assert st.tolist() == [3] * 10 + [0] * 30
+    assert (best, used) == (30, 200) and np.isfinite(Rf).all()
+    pairs = (draws.astype(np.uint64) % np.uint64(40)).reshape(100, 2)
+    assert int((pairs < 10).any(axis=1).sum()) == 41                          # hypotheses that drew a non-finite point
+
+
 def oracle_refit(oracle, c1, c2, cam, thr, inds):
     """rot_ransac.cpp:107-118 done by hand: rotation of the pair, its inliers, rotation of the inliers."""
     p1 = np.array([cam.pixel_to_ray(*c)[1] for c in c1], np.float32)
