@@ -30,8 +30,11 @@ f64p = C.POINTER(C.c_double)
 
 HV_MAX_LEVELS = 6
 (K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI,
- K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL, K_TRACK_TABLE) = range(17)
+ K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL, K_TRACK_TABLE, K_RANSAC3) = range(18)
 RANSAC5_MAX_ITERS = 75
+RANSAC3_MAX_ITERS = 500
+# RansacResult::Type as reported by hv_ransac3_lk_batch_dev
+R3_TYPE_SKIPPED, R3_TYPE_R3 = 0, 2
 # RansacResult::Type as reported by hv_hybrid_ransac_lk_batch_dev
 R5_TYPE_SKIPPED, R5_TYPE_R2, R5_TYPE_R5 = 0, 1, 3
 SUBPIX_MAX_WIN = 16
@@ -73,6 +76,11 @@ class Ransac5Params(C.Structure):
     _fields_ = [("ransac5Prob", C.c_double), ("ransac5Threshold", C.c_double), ("ransacMaxIters", C.c_int),
                 ("ransac2InliersToSkipRansac5", C.c_double), ("ransacMinInlierFraction", C.c_double),
                 ("ransac2InliersOverRansac5Needed", C.c_double)]
+
+
+class Ransac3Params(C.Structure):
+    _fields_ = [("ransac3ErrorThresh", C.c_double), ("ransac3FailureProbability", C.c_double), ("ransac3MaxIterations", C.c_int),
+                ("ransac3MinIterations", C.c_int), ("ransac3UseMle", C.c_int), ("ransacMinInlierFraction", C.c_double)]
 
 
 class StereoGateParams(C.Structure):
@@ -200,6 +208,10 @@ PROTOTYPES = {
     "hv_ransac5": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int] + [C.c_void_p] * 7),
     "hv_ransac5_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int, C.c_int] + [C.c_void_p] * 8),
     "hv_hybrid_ransac_lk_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Ransac5Params), C.c_int, C.c_int] + [C.c_void_p] * 12),
+    "hv_ransac3_default_params": (None, [C.POINTER(Ransac3Params)]),
+    "hv_ransac3": (C.c_int, [C.c_void_p, C.POINTER(Ransac3Params), C.c_int] + [C.c_void_p] * 10),
+    "hv_ransac3_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Ransac3Params), C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "hv_ransac3_lk_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Ransac3Params), C.c_int, C.c_int] + [C.c_void_p] * 14),
     "hv_stereo_gate_default_params": (None, [C.POINTER(StereoGateParams)]),
     "hv_flow_status_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
     "hv_track_gate": (C.c_int, [C.c_void_p, C.POINTER(StereoGateParams), C.c_int] + [C.c_void_p] * 7),
@@ -391,6 +403,45 @@ class Context:
                                                       p(track_status_dev), p(r2_status_dev), p(r2_summary_dev), C.byref(cam1),
                                                       C.byref(cam2), p(result_dev), p(score_dev), p(E_dev), p(r5_summary_dev)),
                   "hv_hybrid_ransac_lk_batch_dev")
+
+    # ---- stereo RANSAC3 (P3P absolute pose) ----
+    def ransac3(self, status, prev_left, prev_right, cur_left, cam0: "CameraModel", cam1: "CameraModel", second_to_first, draws,
+                params: "Ransac3Params" = None):
+        """hv_ransac3 (doRansac3): returns (new status [n], pose [12] = R row-major + position, summary [inliers, best
+        iteration, iterations run, correspondences]); draws = 3 * ransac3MaxIterations raw std::mt19937 outputs."""
+        rp = params if params is not None else ransac3_default_params()
+        a, b, c = (np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in (prev_left, prev_right, cur_left))
+        st = np.ascontiguousarray(status, np.int32).copy()
+        T = np.ascontiguousarray(second_to_first, np.float64).reshape(16)
+        dr = np.ascontiguousarray(draws, np.uint32).reshape(-1)
+        assert len(a) == len(b) == len(c) == len(st) and len(dr) >= 3 * rp.ransac3MaxIterations
+        pose, sm = np.zeros(12), np.zeros(4, np.int32)
+        vp = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(lib().hv_ransac3(self._h, C.byref(rp), len(a), vp(a), vp(b), vp(c), C.byref(cam0), C.byref(cam1), vp(T), vp(dr),
+                                   vp(st), vp(pose), vp(sm)), "hv_ransac3")
+        return st, pose, sm
+
+    def ransac3_batch_dev(self, n_sets, max_points, n_points_dev, prev_left_dev, prev_right_dev, cur_left_dev, cam0, cam1,
+                          second_to_first, draws_dev, status_dev, pose_dev=0, summary_dev=0, params: "Ransac3Params" = None):
+        rp = params if params is not None else ransac3_default_params()
+        T = np.ascontiguousarray(second_to_first, np.float64).reshape(16)          # (copied by the call: a kernel argument)
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_ransac3_batch_dev(self._h, C.byref(rp), n_sets, max_points, p(n_points_dev), p(prev_left_dev),
+                                             p(prev_right_dev), p(cur_left_dev), C.byref(cam0), C.byref(cam1),
+                                             T.ctypes.data_as(C.c_void_p), p(draws_dev), p(status_dev), p(pose_dev), p(summary_dev)),
+                  "hv_ransac3_batch_dev")
+
+    def ransac3_lk_batch_dev(self, n_sets, max_points, n_points_dev, prev_left_dev, prev_right_dev, cur_left_dev, track_status_dev,
+                             r2_summary_dev, cam0, cam1, second_to_first, draws_dev, result_dev, score_dev, pose_dev=0,
+                             summary_dev=0, params: "Ransac3Params" = None):
+        rp = params if params is not None else ransac3_default_params()
+        T = np.ascontiguousarray(second_to_first, np.float64).reshape(16)
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_ransac3_lk_batch_dev(self._h, C.byref(rp), n_sets, max_points, p(n_points_dev), p(prev_left_dev),
+                                                p(prev_right_dev), p(cur_left_dev), p(track_status_dev), p(r2_summary_dev),
+                                                C.byref(cam0), C.byref(cam1), T.ctypes.data_as(C.c_void_p), p(draws_dev),
+                                                p(result_dev), p(score_dev), p(pose_dev), p(summary_dev)),
+                  "hv_ransac3_lk_batch_dev")
 
     # ---- stereo track gate: flow status, epipolar check, crop, blacklist and the detection filter ----
     def flow_status_batch_dev(self, n_sets, max_points, n_points_dev, xy_dev, lk_status_dev, status_dev):
@@ -646,6 +697,14 @@ def gftt_default_params(**over) -> GfttParams:
 def ransac5_default_params(**over) -> Ransac5Params:
     p = Ransac5Params()
     lib().hv_ransac5_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def ransac3_default_params(**over) -> Ransac3Params:
+    p = Ransac3Params()
+    lib().hv_ransac3_default_params(C.byref(p))
     for k, v in over.items():
         setattr(p, k, v)
     return p

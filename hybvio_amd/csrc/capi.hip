@@ -310,6 +310,7 @@ static int init_ctx(Ctx *c, int high_priority)
     if (rc == HV_OK) rc = hv::rot_ransac_alloc_split(c);     // (r05 advisor: once, here -- never inside a launch that may be under capture)
     if (rc == HV_OK) rc = hv::pyramid_init(c);
     if (rc == HV_OK) rc = hv::ransac5_init(c);
+    if (rc == HV_OK) rc = hv::ransac3_init(c);
     if (rc == HV_OK) rc = hv::detect_tail_init(c);
     if (rc == HV_OK) rc = hv::ekf_kernels_init(c);
     if (rc == HV_OK) rc = hv::vu_prepare_init(c);

@@ -257,15 +257,18 @@ std::unique_ptr<rot_ransac::RotRansac> rot_ransac::RotRansac::buildHip(Session &
 }
 
 namespace {
-// Counterpart of RansacPipelineImplementation (src/tracker/ransac_pipeline.cpp:43-151) on its RANSAC2 and hybrid paths.
+// Counterpart of RansacPipelineImplementation (src/tracker/ransac_pipeline.cpp:43-151) on its RANSAC2, hybrid and RANSAC3 paths.
 class HipRansacPipeline : public RansacPipeline {
     Session &session;
     const RansacPipelineParameters parameters;
-    std::mt19937 rng;
+    std::mt19937 rng, rng3;                                                  // :66, :78
+    const bool stereo;                                                       // built with secondToFirstCamera
+    std::array<double, 16> secondToFirstCamera{};
     std::unique_ptr<rot_ransac::RotRansac> rotRansac;
     RansacResult ransacResult, ransac2Result, ransac5Result;
     std::vector<Feature::Point> c1, c2;
-    std::vector<int> status5;
+    std::vector<int> status5, status3;
+    std::vector<std::uint32_t> draws3;
 
     static void initialize(RansacResult &r, std::size_t n) {                 // RansacResult::initialize (:20-27)
         r.type = RansacResult::Type::SKIPPED;
@@ -315,6 +318,33 @@ class HipRansacPipeline : public RansacPipeline {
         return true;
     }
 
+    bool doRansac3(const std::vector<std::array<const hv_camera_model *, 2>> &cameras,
+                   const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners,
+                   std::vector<Feature::Status> &trackStatus) {            // :218-272
+        const std::size_t n = corners[0][0]->size();
+        assert(corners[1][0]->size() == n && corners[0][1]->size() == n && trackStatus.size() == n);
+        initialize(ransacResult, n);
+        status3.resize(n);
+        for (std::size_t i = 0; i < n; ++i) status3[i] = static_cast<int>(trackStatus[i]);
+        // the next 3 * maxIterations raw outputs of a COPY of the generator; the real one advances by what the loop consumed
+        std::mt19937 ahead = rng3;
+        draws3.resize(3 * static_cast<std::size_t>(parameters.ransac3.ransac3MaxIterations));
+        for (auto &d : draws3) d = static_cast<std::uint32_t>(ahead());
+        int summary[4];
+        static_assert(sizeof(Feature::Point) == 2 * sizeof(float), "Point must be two packed floats");
+        auto xy = [](const std::vector<Feature::Point> *v) { return reinterpret_cast<const float *>(v->data()); };
+        session.check(hv_ransac3(session.ctx(), &parameters.ransac3, static_cast<int>(n), xy(corners[0][0]), xy(corners[1][0]),
+                                 xy(corners[0][1]), cameras[0][0], cameras[1][0], secondToFirstCamera.data(), draws3.data(),
+                                 status3.data(), nullptr, summary),
+                      "hv_ransac3");
+        rng3.discard(3ull * static_cast<unsigned long long>(summary[2]));
+        for (std::size_t i = 0; i < n; ++i) trackStatus[i] = static_cast<Feature::Status>(status3[i]);
+        if (summary[3] < 3 || summary[1] < 0) return false;                  // :253-255, 261-263
+        ransacResult.inlierCount = static_cast<std::size_t>(summary[0]);
+        ransacResult.type = RansacResult::Type::R3;
+        return true;
+    }
+
     void computeHybridRansac(const hv_camera_model &camera1, const hv_camera_model &camera2, bool ransac2Done) {   // :158-195
         const auto &p = parameters.ransac5;
         const std::size_t n = c1.size();
@@ -333,8 +363,10 @@ class HipRansacPipeline : public RansacPipeline {
     }
 
 public:
-    HipRansacPipeline(Session &s, int width, int height, const RansacPipelineParameters &p)
-        : session(s), parameters(p), rng(p.ransacRngSeed), rotRansac(rot_ransac::RotRansac::buildHip(s)) {
+    HipRansacPipeline(Session &s, int width, int height, const RansacPipelineParameters &p, const std::array<double, 16> *secondToFirst)
+        : session(s), parameters(p), rng(p.ransacRngSeed), rng3(p.ransacRngSeed), stereo(secondToFirst != nullptr),
+          rotRansac(rot_ransac::RotRansac::buildHip(s)) {
+        if (secondToFirst) secondToFirstCamera = *secondToFirst;
         const double su = std::min(height, width) / 720.0;                   // :91-93
         rotRansac->threshold_pow2 = static_cast<float>(std::pow(p.ransac2Threshold * su, 2));
     }
@@ -352,10 +384,15 @@ public:
         }
         const std::size_t n = c1.size();
         const bool ransac2Done = doRansac2(*cameras[0][0], *cameras[0][1]);
-        if (!parameters.useHybridRansac) return ransac2Result.inlierCount / static_cast<double>(n);   // :133-135
-        computeHybridRansac(*cameras[0][0], *cameras[0][1], ransac2Done);
-        if (ransacResult.type != RansacResult::Type::SKIPPED) updateTrackStatus(ransacResult, trackStatus);
-        else
+        if (stereo && parameters.useRansac3 && cameras.size() >= 2 && corners.size() >= 2) {   // :121-123
+            doRansac3(cameras, corners, trackStatus);
+        } else if (parameters.useHybridRansac) {
+            computeHybridRansac(*cameras[0][0], *cameras[0][1], ransac2Done);
+            if (ransacResult.type != RansacResult::Type::SKIPPED) updateTrackStatus(ransacResult, trackStatus);
+        } else {
+            return ransac2Result.inlierCount / static_cast<double>(n);       // :133-135
+        }
+        if (ransacResult.type == RansacResult::Type::SKIPPED)
             for (auto &st : trackStatus) st = Feature::Status::RANSAC_OUTLIER;   // :139-144
         if (n == 0) return 0.0;
         return ransac2Result.inlierCount / static_cast<double>(n);
@@ -368,11 +405,19 @@ public:
 std::unique_ptr<RansacPipeline> RansacPipeline::buildHip(Session &s, int width, int height, const RansacPipelineParameters &p)
 {
     if (p.useRansac3)
-        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useRansac3 (Theia P3P RANSAC) is not implemented on the device; "
-                                    "set useRansac3 false to use the hybrid RANSAC2 / RANSAC5 path");
+        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useRansac3 needs the stereo transform: call the overload that "
+                                    "takes secondToFirstCamera, or set useRansac3 false to use the hybrid RANSAC2 / RANSAC5 path");
     if (p.useStereoUpright2p)
         throw std::invalid_argument("RansacPipeline::buildHip: tracker.useStereoUpright2p is not implemented on the device");
-    return std::unique_ptr<RansacPipeline>(new HipRansacPipeline(s, width, height, p));
+    return std::unique_ptr<RansacPipeline>(new HipRansacPipeline(s, width, height, p, nullptr));
+}
+
+std::unique_ptr<RansacPipeline> RansacPipeline::buildHip(Session &s, int width, int height, const RansacPipelineParameters &p,
+                                                         const std::array<double, 16> &secondToFirstCamera)
+{
+    if (p.useStereoUpright2p)
+        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useStereoUpright2p is not implemented on the device");
+    return std::unique_ptr<RansacPipeline>(new HipRansacPipeline(s, width, height, p, &secondToFirstCamera));
 }
 
 namespace {

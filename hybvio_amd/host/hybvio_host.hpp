@@ -243,23 +243,35 @@ struct RansacResult {
 // The tracker.* parameters RansacPipeline reads (codegen/parameter_definitions.c:268-305).
 struct RansacPipelineParameters {
     bool useHybridRansac = true;
-    bool useRansac3 = true;                  // the reference's default; buildHip refuses it (Theia P3P is not implemented)
-    bool useStereoUpright2p = false;         // refused as well
+    bool useRansac3 = true;                  // the reference's default; needs the buildHip overload with the stereo transform
+    bool useStereoUpright2p = false;         // refused by both overloads
     double ransac2Threshold = 4.0;
     unsigned ransacRngSeed = 4649;
     hv_ransac5_params ransac5{0.999, 2.0, 75, 0.9, 0.3, 0.9};
+    hv_ransac3_params ransac3{1e-4, 1e-4, 500, 50, 1, 0.3};
 };
 
 // tracker::RansacPipeline (src/tracker/ransac_pipeline.hpp:15-45) on the hybrid path (ransac_pipeline.cpp:95-195): RANSAC2
 // through RotRansac::buildHip with the pipeline's own std::mt19937(ransacRngSeed), then hv_ransac5 unless RANSAC2 already
 // explains more than ransac2InliersToSkipRansac5 of the tracks, the hybrid choice and the status rewrite. With
-// useHybridRansac false compute() only runs RANSAC2 and returns its score, as the reference does. buildHip throws
-// std::invalid_argument when the parameters ask for RANSAC3 or the upright 2-point solver. The cameras are
-// hv_camera_model descriptions of cameras[i][0 / 1]; poses are not used on these paths and may be null.
+// useHybridRansac false compute() only runs RANSAC2 and returns its score, as the reference does. The four-argument
+// buildHip has no stereo transform: it throws std::invalid_argument when the parameters ask for RANSAC3 (use the overload
+// below) or the upright 2-point solver. The cameras are hv_camera_model descriptions of cameras[i][0 / 1]; poses are not
+// used on these paths and may be null.
+// The overload with secondToFirstCamera = imuToCamera * secondImuToCamera.inverse() (ransac_pipeline.cpp:225; 16 row-major
+// doubles formed by the caller) accepts useRansac3: compute() then takes the RANSAC3 branch (:121-123, doRansac3 :218-272
+// through hv_ransac3) whenever cameras.size() >= 2 && corners.size() >= 2, with cameras[0][0] / cameras[1][0] as the first /
+// second camera, and the hybrid / RANSAC2-only branches otherwise. hv_ransac3 has one model for the first camera, so the
+// current-left corner is normalised with cameras[0][0] where the reference uses cameras[0][1] (:248): the same model in both
+// frames, as the tracker always passes it. RANSAC3 draws from its own std::mt19937(ransacRngSeed)
+// (:78), advanced by three draws per iteration run. It still refuses useStereoUpright2p.
 class RansacPipeline {
 public:
     static std::unique_ptr<RansacPipeline> buildHip(Session &session, int imageWidth, int imageHeight,
                                                     const RansacPipelineParameters &parameters);
+    static std::unique_ptr<RansacPipeline> buildHip(Session &session, int imageWidth, int imageHeight,
+                                                    const RansacPipelineParameters &parameters,
+                                                    const std::array<double, 16> &secondToFirstCamera);
     virtual ~RansacPipeline();
     virtual double compute(
         const std::vector<std::array<const hv_camera_model *, 2>> &cameras,

@@ -615,6 +615,57 @@ int hv_hybrid_ransac_lk_batch_dev(hv_ctx *ctx, const hv_ransac5_params *p, int n
                                   const hv_camera_model *camera2, int *result_dev, double *score_dev, double *E_dev,
                                   int *r5_summary_dev);
 
+/* ---- stereo RANSAC3: P3P absolute-pose track filter (added within ABI 4) ----------------------------------------------
+ * Replaces doRansac3 (src/tracker/ransac_pipeline.cpp:218-272) and the RANSAC3 branch of RansacPipeline::compute
+ * (:121-123, 137-149) without Theia. Per feature with status TRACKED (0), in feature order: the status becomes
+ * RANSAC_OUTLIER (3); Camera::normalizePixel of the previous-left (camera0), previous-right (camera1) and current-left
+ * (camera0) corner; triangulateStereoFeatureIdp (src/odometry/triangulation.cpp:711-764) of the previous pair with
+ * second_to_first = imuToCamera * secondImuToCamera^-1 (16 row-major doubles formed by the caller: the library does not
+ * restate Eigen's inverse); world point = (idp.x, idp.y, 1) / idp.z. A feature failing any step takes no part. With at
+ * least 3 correspondences a P3P RANSAC estimates the current-left camera pose and its inliers go back to TRACKED.
+ * The sample-consensus loop, the sampler and the minimal solver are the ones stated in tests/ransac3_restatement.py
+ * (Theia is not in the reference tree; DESIGN.md 3.14 lists what follows a recollection of it and what departs from it).
+ * draws = the next 3 * ransac3MaxIterations raw outputs of the caller's std::mt19937 (the kernel forms
+ * i + raw % (m - i) itself because m is only known on the device); afterwards the caller keeps 3 * iterations-run of them
+ * consumed. Field names are the reference's parameters (codegen/parameter_definitions.c:282, 292-296).
+ * HV_ERR_UNSUPPORTED: ransac3MaxIterations > HV_RANSAC3_MAX_ITERS or more than 1024 points; HV_ERR_INVALID:
+ * ransac3FailureProbability outside (0, 1), ransac3ErrorThresh <= 0, ransac3MaxIterations < 1, ransac3MinIterations >
+ * ransac3MaxIterations, ransacMinInlierFraction outside [0, 1] or a NULL required pointer. The parameter and size checks
+ * come before the context is looked at. */
+#define HV_RANSAC3_MAX_ITERS 500
+typedef struct hv_ransac3_params {
+    double ransac3ErrorThresh; double ransac3FailureProbability; int ransac3MaxIterations; int ransac3MinIterations;
+    int ransac3UseMle; double ransacMinInlierFraction;
+} hv_ransac3_params;
+void hv_ransac3_default_params(hv_ransac3_params *p);   /* 1e-4, 1e-4, 500, 50, 1, 0.3 */
+/* doRansac3 on one set of n features: status[n] int32 Feature::Status in/out (entries other than TRACKED stay), pose[12]
+ * (NULL ok) = R row-major then the camera position c, x_cam = R (X - c), zeros without a model; summary[4] (NULL ok) =
+ * {inlier count, iteration of the best model (-1: none), iterations run, correspondences m}. Fewer than 3
+ * correspondences: not run, {0, -1, 0, m}. Synchronous. */
+int hv_ransac3(hv_ctx *ctx, const hv_ransac3_params *p, int n, const float *prev_left_xy, const float *prev_right_xy,
+               const float *cur_left_xy, const hv_camera_model *camera0, const hv_camera_model *camera1,
+               const double *second_to_first, const uint32_t *draws, int *status, double *pose, int *summary);
+/* n_sets sets in device memory: set s = n_points_dev[s] <= max_points (<= 1024) features at *_dev + s * max_points * 2,
+ * draws_dev [n_sets][3 * ransac3MaxIterations], status_dev [n_sets][max_points] in/out (entries >= n_points_dev[s] are
+ * never written), pose_dev [n_sets][12] and summary_dev [n_sets][4] as above (NULL ok). Asynchronous on the context
+ * stream, no allocation or synchronisation inside (capturable in a HIP graph). n_sets <= 65535. */
+int hv_ransac3_batch_dev(hv_ctx *ctx, const hv_ransac3_params *p, int n_sets, int max_points, const int *n_points_dev,
+                         const float *prev_left_dev, const float *prev_right_dev, const float *cur_left_dev,
+                         const hv_camera_model *camera0, const hv_camera_model *camera1, const double *second_to_first,
+                         const uint32_t *draws_dev, int *status_dev, double *pose_dev, int *summary_dev);
+/* The stereo device chain step after hv_rot_ransac_lk_batch_dev: RansacPipeline::compute on the RANSAC3 branch.
+ * track_status_dev [n_sets][max_points] in/out as above, and when RANSAC3 did not run or produced no model (SKIPPED)
+ * every entry < n_points_dev[s] becomes 3 (:139-144). r2_summary_dev = the summary_dev of hv_rot_ransac_lk_batch_dev on
+ * the same set. result_dev [n_sets][2] = {type 0 SKIPPED / 2 R3, inlierCount}, score_dev [n_sets] = RANSAC2 inliers /
+ * TRACKED count on entry (0 when that is 0), the return value of compute. The corner arguments are table.xy,
+ * table.second_xy and the current corners of the track-table chain: call it before hv_tracks_update_batch_dev overwrites
+ * them. Asynchronous, capturable. */
+int hv_ransac3_lk_batch_dev(hv_ctx *ctx, const hv_ransac3_params *p, int n_sets, int max_points, const int *n_points_dev,
+                            const float *prev_left_dev, const float *prev_right_dev, const float *cur_left_dev,
+                            int *track_status_dev, const int *r2_summary_dev, const hv_camera_model *camera0,
+                            const hv_camera_model *camera1, const double *second_to_first, const uint32_t *draws_dev,
+                            int *result_dev, double *score_dev, double *pose_dev, int *summary_dev);
+
 /* ---- stereo track gate: flow status, epipolar check, crop, blacklist and the detection filter (added within ABI 4) -----
  * Replaces the per-track status rules between the LK calls and RansacPipeline::compute in TrackerImplementation::track
  * (src/tracker/tracker.cpp:441-478) and the filter of new corners in detectFeatures (:266-311), with the helpers
@@ -776,7 +827,8 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_STEREO_GATE = 14 /* added within ABI 4: hv_flow_status_batch_dev, hv_track_gate*, hv_detection_filter* */,
        HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
-       HV_K_COUNT = 17 };
+       HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3* */,
+       HV_K_COUNT = 18 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
 /* Synchronizes, then returns accumulated device milliseconds and launch count of a kernel class. */
