@@ -30,7 +30,7 @@ f64p = C.POINTER(C.c_double)
 
 HV_MAX_LEVELS = 6
 (K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI,
- K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL, K_TRACK_TABLE, K_RANSAC3) = range(18)
+ K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL, K_TRACK_TABLE, K_RANSAC3, K_EKF_CONTROL) = range(19)
 RANSAC5_MAX_ITERS = 75
 RANSAC3_MAX_ITERS = 500
 # RansacResult::Type as reported by hv_ransac3_lk_batch_dev
@@ -97,6 +97,17 @@ class TrackTable(C.Structure):
     """hv_track_table: device pointers owned by the caller (second_xy None = mono)."""
     _fields_ = [(k, C.c_void_p) for k in ("n_tracks", "ids", "xy", "second_xy", "status", "blacklist", "kf_xy", "kf_valid",
                                           "frame_num", "mask_steps", "mask_radius", "frame_flags")]
+
+
+class EkfControlParams(C.Structure):
+    _fields_ = [("useDecayingZeroVelocityUpdate", C.c_int), ("usePseudoVelocity", C.c_int), ("pseudoVelocityLimit", C.c_double),
+                ("pseudoVelocityTarget", C.c_double), ("pseudoVelocityR", C.c_double), ("useVisualStationarity", C.c_int),
+                ("visualStationarityFrameCountThreshold", C.c_int), ("visualZuptR", C.c_double)]
+
+
+class EkfControlTable(C.Structure):
+    """hv_ekf_control: device pointers owned by the caller."""
+    _fields_ = [(k, C.c_void_p) for k in ("zupt_time", "init_zupt_time", "was_stationary", "frames_since_keyframe")]
 
 
 class HvError(RuntimeError):
@@ -225,6 +236,13 @@ PROTOTYPES = {
                                    + [C.c_void_p] * 4),
     "hv_tracks_delete_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrackTableParams), C.c_int, C.POINTER(TrackTable), C.c_int]
                                    + [C.c_void_p] * 2),
+    "hv_ekf_block_update_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p]),
+    "hv_ekf_pseudo_velocity_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "hv_ekf_undo_augment_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hv_ekf_control_default_params": (None, [C.POINTER(EkfControlParams)]),
+    "hv_ekf_control_init_dev": (C.c_int, [C.c_void_p, C.POINTER(EkfControlTable)]),
+    "hv_ekf_imu_control_dev": (C.c_int, [C.c_void_p, C.POINTER(EkfControlParams), C.POINTER(EkfControlTable), C.c_void_p, C.c_void_p]),
+    "hv_ekf_frame_control_dev": (C.c_int, [C.c_void_p, C.POINTER(EkfControlParams), C.POINTER(EkfControlTable)] + [C.c_void_p] * 7),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -763,6 +781,26 @@ def ekf_default_params(**over) -> EkfParams:
     return p
 
 
+def ekf_control_default_params(**over) -> EkfControlParams:
+    p = EkfControlParams()
+    lib().hv_ekf_control_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+class EkfControl:
+    """hv_ekf_control for `batch` filters: four torch tensors on the current device (zupt_time, init_zupt_time float64;
+    was_stationary, frames_since_keyframe int32) and the pointer table over them. Uninitialised until control_init_dev."""
+
+    def __init__(self, batch: int):
+        self.zupt_time = torch.empty(batch, dtype=torch.float64, device="cuda")
+        self.init_zupt_time = torch.empty(batch, dtype=torch.float64, device="cuda")
+        self.was_stationary = torch.empty(batch, dtype=torch.int32, device="cuda")
+        self.frames_since_keyframe = torch.empty(batch, dtype=torch.int32, device="cuda")
+        self.table = EkfControlTable(*(getattr(self, k).data_ptr() for k, _ in EkfControlTable._fields_))
+
+
 def _f(a):
     return np.ascontiguousarray(a, np.float64)
 
@@ -1071,6 +1109,33 @@ class EkfBatch:
         act = np.ascontiguousarray(active, np.uint8) if active is not None else None
         self._chk(lib().hv_ekf_undo_augment(self._h, _p(act, u8p)), "hv_ekf_undo_augment")
         self.ctx.synchronize()
+
+    def undo_augment_dev(self, active_dev=0):
+        """hv_ekf_undo_augment_dev: the mask as a device array (or 0), asynchronous."""
+        self._chk(lib().hv_ekf_undo_augment_dev(self._h, C.c_void_p(active_dev)), "hv_ekf_undo_augment_dev")
+
+    def block_update_dev(self, col0, rows, y_dev=0, r_dev=0, r0=0.0, active_dev=0, normalize_all=False, applied_dev=0):
+        """hv_ekf_block_update_dev: the update with `rows` unit rows at state entry col0; R = r I already scaled by noiseScale^2."""
+        self._chk(lib().hv_ekf_block_update_dev(self._h, int(col0), int(rows), C.c_void_p(y_dev), C.c_void_p(r_dev), float(r0),
+                                                C.c_void_p(active_dev), int(normalize_all), C.c_void_p(applied_dev)), "hv_ekf_block_update_dev")
+
+    def pseudo_velocity_dev(self, limit, target, r, active_dev=0, applied_dev=0):
+        self._chk(lib().hv_ekf_pseudo_velocity_dev(self._h, float(limit), float(target), float(r), C.c_void_p(active_dev),
+                                                   C.c_void_p(applied_dev)), "hv_ekf_pseudo_velocity_dev")
+
+    def control_init_dev(self, ctl: "EkfControl"):
+        self._chk(lib().hv_ekf_control_init_dev(self._h, C.byref(ctl.table)), "hv_ekf_control_init_dev")
+
+    def imu_control_dev(self, params: "EkfControlParams", ctl: "EkfControl", time_dev, active_dev=0):
+        """hv_ekf_imu_control_dev: init-ZUPT then pseudo-velocity behind a predict; time_dev [batch] float64."""
+        self._chk(lib().hv_ekf_imu_control_dev(self._h, C.byref(params), C.byref(ctl.table), C.c_void_p(time_dev), C.c_void_p(active_dev)),
+                  "hv_ekf_imu_control_dev")
+
+    def frame_control_dev(self, params: "EkfControlParams", ctl: "EkfControl", time_dev, keyframe_dev, full_update_dev=0, keyframe_out_dev=0,
+                          undo_active_dev=0, stationary_dev=0, applied_dev=0):
+        """hv_ekf_frame_control_dev: the frame's keyframe counter, visual-stationarity ZUPT and undo mask."""
+        a = [C.c_void_p(x) for x in (time_dev, keyframe_dev, full_update_dev, keyframe_out_dev, undo_active_dev, stationary_dev, applied_dev)]
+        self._chk(lib().hv_ekf_frame_control_dev(self._h, C.byref(params), C.byref(ctl.table), *a), "hv_ekf_frame_control_dev")
 
     def symmetrize(self):
         self._chk(lib().hv_ekf_symmetrize(self._h), "hv_ekf_symmetrize")

@@ -2710,6 +2710,19 @@ int hv_ekf_undo_augment(hv_ekf *h, const unsigned char *active)
     return HV_OK;
 }
 
+// hv_ekf_undo_augment with the mask already on the device (added within ABI 4): no host copy, capturable
+int hv_ekf_undo_augment_dev(hv_ekf *h, const unsigned char *active_dev)
+{
+    if (!h) return HV_ERR_INVALID;
+    Ekf *e = &h->e; Ctx *c = e->c;
+    hv::ShiftArgs a{e->n, e->map_dim, e->fixed.m, e->fixed.P, e->fixed.P1, e->fixed.m1, active_dev};
+    hv::ScopedKernelTime tm(c, HV_K_EKF_AUGMENT);
+    hipLaunchKernelGGL(hv::ekf_unaugment_kernel, dim3(e->batch), dim3(1024), 0, c->stream, a);
+    HV_HIP(c, hipGetLastError());
+    std::swap(e->fixed.P, e->fixed.P1);
+    return HV_OK;
+}
+
 int hv_ekf_symmetrize(hv_ekf *h)
 {
     if (!h) return HV_ERR_INVALID;

@@ -169,7 +169,8 @@ int hv_klt_track_batch_ragged_dev(hv_ctx *ctx, int n_pairs, const int *prev_slot
  * independent filters that share one parameter set (batch = 1 is the reference's single session).
  * State m (n = 20 + 7*cameraTrailLength + 3*hybridMapSize) and covariance P (n x n, f64,
  * column-major like Eigen) stay on the device; the scalar bookkeeping of the reference class
- * (sample clock, ZUPT rate limits, augmentTimes) lives in the host adapter (hybvio_amd/host).
+ * (sample clock, ZUPT rate limits, augmentTimes) lives in the host adapter (hybvio_amd/host); a batch of
+ * resident sequences keeps the rate limits and flags on the device instead (hv_ekf_control, below).
  * Per-filter inputs are arrays indexed [filter][...]. Calls are asynchronous on the context
  * stream unless they return data to the host. */
 typedef struct hv_ekf hv_ekf;
@@ -818,6 +819,82 @@ int hv_tracks_append_batch_dev(hv_ctx *ctx, const hv_track_table_params *p, int 
 int hv_tracks_delete_batch_dev(hv_ctx *ctx, const hv_track_table_params *p, int n_sets, const hv_track_table *table,
                                int max_ids, const int32_t *n_ids_dev, const int32_t *ids_dev);
 
+/* ---- EKF control updates: ZUPT, pseudo-velocity, unit-block updates and the per-frame rules (added within ABI 4) -------
+ * Replaces, for a batch of resident filters, the control part of Session::process (src/odometry/backend.cpp:738-749,
+ * 774-796) and the updates it calls (ekf.cpp:573-677): every one of them has a measurement matrix made of unit rows
+ * (pseudo-velocity: one 1 x 2 unit vector), so HP is rows of P, S a sub-block of P plus r I, and the update one rank-k
+ * downdate that reads and writes P once (csrc/ekf_control.hip). The reference's operands are kept -- HP
+ * from the ROWS of P, S factored from its lower triangle -- because P is only symmetrised at maintainPositiveSemiDefinite.
+ * A filter whose S has a pivot that is not positive is left untouched (applied = 0), the library's rule for S.
+ * All entries: one launch, one workgroup per filter, asynchronous on the context stream, no allocation or synchronisation
+ * inside (capturable in a HIP graph). HV_ERR_INVALID for a NULL handle, a NULL required pointer (a member of hv_ekf_control
+ * included) or the argument ranges stated below, decided before any device work; HV_ERR_UNSUPPORTED for a state of more
+ * than 1024 entries. Masked-out filters are not touched at all. */
+/* update(m, P, y, H, R) + updateCommon for H = the `rows` (1 .. 4) unit rows of the state entries col0 .. col0 + rows - 1
+ * (col0 >= 0, col0 + rows <= stateDim): updateZupt / updateZuptInitialization (VEL = 3, 3), updateZrupt (BGA = 10, 3),
+ * updatePosition (POS = 0, 3), updateZeroHeight (2, 1), updateOrientation (ORI = 6, 4, normalize_all = 1); the caller follows
+ * it with hv_ekf_symmetrize where the reference calls maintainPositiveSemiDefinite and applies the reference's rate limits
+ * itself (or uses the control steps below). y_dev [batch][rows] (NULL: zeros); R = r I with r = r_dev[f] (r_dev [batch]) or,
+ * r_dev NULL, r0 for every filter: already scaled by noiseScale^2, like the r_diag of hv_ekf_update. active_dev [batch]
+ * uint8 (NULL: all). normalize_all != 0: normalizeQuaternions() on the trail as well (the current orientation always is).
+ * applied_dev [batch] uint8 (NULL ok) = 1 where the update was applied, 0 where masked out or refused. */
+int hv_ekf_block_update_dev(hv_ekf *ekf, int col0, int rows, const double *y_dev, const double *r_dev, double r0,
+                            const unsigned char *active_dev, int normalize_all, unsigned char *applied_dev);
+/* updatePseudoVelocity(target, r) (ekf.cpp:628-649) behind the caller's speed test (backend.cpp:744-745), the mean read on
+ * the device: h = |m[VEL : VEL + 2]| (two rounded products, one rounded sum, sqrt); skipped when h <= 1e-7 or h <= limit
+ * (limit < 0: no limit test); otherwise the scalar update with H = m[VEL : VEL + 2]' / h, residual target - h and
+ * R = r * noiseScale^2. applied_dev as above (0 for a skipped filter). */
+int hv_ekf_pseudo_velocity_dev(hv_ekf *ekf, double limit, double target, double r, const unsigned char *active_dev,
+                               unsigned char *applied_dev);
+/* hv_ekf_undo_augment with the mask in device memory (NULL: all): the same kernel and ping-pong (fetch P_dev again
+ * afterwards), masked-out filters carried over unchanged. active_dev is what hv_ekf_frame_control_dev writes as undo_active_dev. */
+int hv_ekf_undo_augment_dev(hv_ekf *ekf, const unsigned char *active_dev);
+/* The odometry parameters the control steps read (codegen/parameter_definitions.c:87-119); initZuptR is hv_ekf_params'. */
+typedef struct hv_ekf_control_params {
+    int useDecayingZeroVelocityUpdate;            /* 0 */
+    int usePseudoVelocity;                        /* 0 */
+    double pseudoVelocityLimit;                   /* 1.4 */
+    double pseudoVelocityTarget;                  /* 0 */
+    double pseudoVelocityR;                       /* 1e-4 */
+    int useVisualStationarity;                    /* 1 */
+    int visualStationarityFrameCountThreshold;    /* 3 */
+    double visualZuptR;                           /* 1e-7 */
+} hv_ekf_control_params;
+void hv_ekf_control_default_params(hv_ekf_control_params *p);
+/* The scalar members of odometry::EKF and Session the control steps keep, as device arrays of [batch] owned by the caller
+ * (like hv_track_table). */
+typedef struct hv_ekf_control {
+    double  *zupt_time;              /* EKF::ZUPTtime */
+    double  *init_zupt_time;         /* EKF::initZUPTtime */
+    int32_t *was_stationary;         /* EKF::wasStationary */
+    int32_t *frames_since_keyframe;  /* Session::framesSinceKeyframe */
+} hv_ekf_control;
+/* A fresh session: both clocks -1.0, the flag and the counter 0. */
+int hv_ekf_control_init_dev(hv_ekf *ekf, const hv_ekf_control *ctl);
+/* The control updates behind an IMU sample's predict (backend.cpp:738-749). time_dev [batch] double = the filter clock
+ * t - firstSampleT (ekf.cpp:360), supplied by the caller. Per active filter, in this order:
+ * - useDecayingZeroVelocityUpdate: updateZuptInitialization (ekf.cpp:594-611), skipped when was_stationary, time > 60 or
+ *   time - init_zupt_time < 0.1; otherwise init_zupt_time = time and the zero-velocity update with
+ *   R = initZuptR * noiseScale^2 * exp(0.5 * time);
+ * - usePseudoVelocity: hv_ekf_pseudo_velocity_dev(pseudoVelocityLimit, pseudoVelocityTarget, pseudoVelocityR) on the mean
+ *   the first update left.
+ * With both switches off nothing is launched. */
+int hv_ekf_imu_control_dev(hv_ekf *ekf, const hv_ekf_control_params *p, const hv_ekf_control *ctl, const double *time_dev,
+                           const unsigned char *active_dev);
+/* The control part of a frame (backend.cpp:774-796), every filter. keyframe_dev [batch] int32 = what
+ * hv_tracks_update_batch_dev writes; full_update_dev [batch] uint8 (NULL: every frame is a full visual update, the default
+ * visualUpdateForEveryNFrame = 1). Per filter:
+ * - frames_since_keyframe = keyframe ? 0 : frames_since_keyframe + 1; stationary = frames_since_keyframe >=
+ *   visualStationarityFrameCountThreshold;
+ * - useVisualStationarity && stationary: updateZupt(visualZuptR) (ekf.cpp:573-590), skipped when time - zupt_time < 0.25;
+ *   otherwise zupt_time = time, was_stationary = 1 and the zero-velocity update with R = visualZuptR * noiseScale^2;
+ * - keyframe_out = keyframe && full; undo_active = !keyframe_out (the filters hv_ekf_undo_augment_dev shifts).
+ * Outputs, each [batch] and each NULL ok: keyframe_out_dev int32, undo_active_dev / stationary_dev / applied_dev uint8
+ * (applied: the ZUPT was due and applied). */
+int hv_ekf_frame_control_dev(hv_ekf *ekf, const hv_ekf_control_params *p, const hv_ekf_control *ctl, const double *time_dev,
+                             const int32_t *keyframe_dev, const unsigned char *full_update_dev, int32_t *keyframe_out_dev,
+                             unsigned char *undo_active_dev, unsigned char *stationary_dev, unsigned char *applied_dev);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
@@ -828,7 +905,8 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3* */,
-       HV_K_COUNT = 18 };
+       HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev */,
+       HV_K_COUNT = 19 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
 /* Synchronizes, then returns accumulated device milliseconds and launch count of a kernel class. */
