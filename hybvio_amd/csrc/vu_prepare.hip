@@ -668,6 +668,7 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
                 for (int k = 0; k < 3; ++k) dst[9 + k] = dt[k];
             }
             VU_STAMP(2);
+            double d_before[3] = {0.0, 0.0, 0.0};                     // this lane's column of dpfi as the last iteration found it (see the final pass)
             for (int it = 0; it < a.gn_iters; ++it) {
                 if (it < 6) VU_STAMP(3 + 4 * it);
                 if (tid < nt) {                                       // per-pose quantities of this iteration
@@ -813,7 +814,7 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
                     mv3(X, t1, t2);
                     mv3(X, dEe, t3);
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) s_dpfi[r * ncol + j] += t2[r] - t3[r];
+                    for (int r = 0; r < 3; ++r) { d_before[r] = s_dpfi[r * ncol + j]; s_dpfi[r * ncol + j] = d_before[r] + (t2[r] - t3[r]); }
                 }
                 if (tid == 0) {                                       // :316-342
 #pragma unroll
@@ -825,6 +826,44 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
                 __syncthreads();
                 if (s_flag[0]) break;
             }
+            // ---- the converging iteration's derivative update once more, in the reference's order (profiles/vu_accuracy/README.md) ----
+            // The sums above are equal to the reference's in exact arithmetic, not in binary64: the plain part goes through the summed maps,
+            // (sum_i L_i) d_j, and the pose-0 columns' plain and motion parts cancel only after both were summed over the poses. On a track
+            // with rcond(E'E) below ~1e-4 that costs 50 .. 2000 x the reference's own rounding error in H, since X = (E'E)^-1 multiplies it.
+            // The recursion d <- d - X (residual of d) corrects itself, so only its last application has to be accurate: every column lane
+            // walks the poses once, pose by pose as triangulation.cpp:264-311 does, from the column it had before this iteration, with the
+            // pose records, X and the step of this iteration (all still in place; pfi was already stepped, so the old iterate is pfi + step).
+            if (s_flag[0] && tid < ncol && !(tid == dDim && !a.est_shift)) {
+                const int j = tid, pj = j / 7, comp = j - 7 * pj;
+                const bool is_t = j == dDim, p0col = !is_t && pj == 0;
+                const double q0 = pfi[0] + step[0], q1 = pfi[1] + step[1], q2 = pfi[2] + step[2];
+                double dEe[3] = {0, 0, 0}, dM[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+                for (int i = 0; i < nt; ++i) {
+                    const double *o = s_it + i * ITER_WORDS;
+                    // the motion pair of (pose i, this column), if there is one: pose-0 columns move every pose, an own column its pose
+                    const bool moves = !is_t && (p0col || i == pj);
+                    const double w = moves ? 1.0 : 0.0;
+                    const double *mot = s_mot + (moves ? (p0col ? 7 * i + comp : 7 * nt + j - 7) : 0) * MOT_STRIDE;
+                    double dC[9], dt[3], dh[3];
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) dC[k] = w * mot[k];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) dt[k] = w * mot[9 + k];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+                        dh[r] = ((dC[3 * r] * q0 + dC[3 * r + 1] * q1 + dC[3 * r + 2]) + q2 * dt[r])
+                                + ((o[3 * r] * d_before[0] + o[3 * r + 1] * d_before[1]) + o[9 + r] * d_before[2]);
+                    pair_sums<1>(o, dh, dC, dt, is_t ? s_feat[4 * i + 2] : 0.0, is_t ? s_feat[4 * i + 3] : 0.0, dEe, dM);
+                }
+                dM[3] = dM[1]; dM[6] = dM[2]; dM[7] = dM[5];
+                double t1[3], t2[3], t3[3];
+                mv3(dM, step, t1);
+                mv3(X, t1, t2);
+                mv3(X, dEe, t3);
+#pragma unroll
+                for (int r = 0; r < 3; ++r) s_dpfi[r * ncol + j] = d_before[r] + (t2[r] - t3[r]);
+            }
+            __syncthreads();
         }   // iterative front
         VU_STAMP(27);
         // ---- status, back to world coordinates (:345-392) ----

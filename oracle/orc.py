@@ -620,6 +620,71 @@ def tri_last_diag():
     return out
 
 
+# ---- the same source at two more builds (oracle/Makefile: liboracle_ld.so, standin) ----
+ldp = C.POINTER(C.c_longdouble)
+_VARIANTS = {}
+
+
+class TriParamsLD(C.Structure):      # orc_tri_params with real = long double
+    _fields_ = [(k, C.c_longdouble if t is C.c_double else t) for k, t in TriParams._fields_]
+
+
+def _variant(kind):
+    """'ld': triangulation_oracle.c with real = long double (names suffixed _ld), built beside liboracle.so when stale.
+    'standin': its -O3 -march=native -ffp-contract=fast -ffast-math double build, compiled on the machine that runs it, outside the tree."""
+    if kind not in _VARIANTS:
+        src = [os.path.join(_DIR, f) for f in ("triangulation_oracle.c", "Makefile")]
+        if kind == "ld":
+            if np.finfo(np.longdouble).eps >= 2e-19 or C.sizeof(C.c_longdouble) != np.dtype(np.longdouble).itemsize:
+                raise RuntimeError("liboracle_ld.so needs an extended-precision long double that numpy and ctypes agree on "
+                                   f"(np.longdouble eps = {np.finfo(np.longdouble).eps})")
+            so = os.path.join(_DIR, "liboracle_ld.so")
+            if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
+                subprocess.check_call(["make", "-C", _DIR, "-B", "liboracle_ld.so"], stdout=subprocess.DEVNULL)
+            sfx, real, ptr = "_ld", C.c_longdouble, ldp
+        elif kind == "standin":
+            import tempfile
+            so = os.path.join(tempfile.gettempdir(), f"liboracle_standin_{os.getuid()}.so")
+            subprocess.check_call(["make", "-C", _DIR, "-B", "standin", f"STANDIN_OUT={so}"], stdout=subprocess.DEVNULL)
+            sfx, real, ptr = "", C.c_double, f64p
+        else:
+            raise ValueError(kind)
+        L = C.CDLL(so)
+        vtp, diag = getattr(L, "orc_visual_track_prepare" + sfx), getattr(L, "orc_tri_last_diag" + sfx)
+        vtp.restype = C.c_int
+        vtp.argtypes = [C.c_void_p, ptr, C.c_int, i32p, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32p]
+        diag.restype, diag.argtypes = None, [ptr]
+        _VARIANTS[kind] = (vtp, diag, np.longdouble if kind == "ld" else np.float64, ptr, TriParamsLD if kind == "ld" else TriParams)
+    return _VARIANTS[kind]
+
+
+def visual_track_prepare_as(kind, par, m, pose_trail_index, imu_to_cam, imu_to_cam2, image_features, feature_velocities):
+    """visual_track_prepare through another build of the same source (kind 'ld' or 'standin', see _variant). The inputs are taken as
+    they are given (binary64 values convert to long double exactly); pf, H and f come back in the build's own real type."""
+    vtp, _, dt, ptr, Par = _variant(kind)
+    q = Par()
+    for k, _t in TriParams._fields_:
+        setattr(q, k, getattr(par, k))
+    arr = lambda a: np.ascontiguousarray(a, dt)
+    m = arr(m)
+    idx = np.ascontiguousarray(pose_trail_index, np.int32)
+    nt = len(idx) * (2 if imu_to_cam2 is not None else 1)
+    H = np.zeros((len(m), 2 * nt), dt)
+    f, pf, ps = np.zeros(2 * nt, dt), np.zeros(3, dt), np.zeros(1, np.int32)
+    a, b = arr(imu_to_cam), (None if imu_to_cam2 is None else arr(imu_to_cam2))
+    ft, vl = arr(image_features), arr(feature_velocities)
+    st = vtp(C.byref(q), _p(m, ptr), len(m), _p(idx, i32p), len(idx), _p(a, ptr), None if b is None else _p(b, ptr),
+             _p(ft, ptr), _p(vl, ptr), _p(pf, ptr), _p(H, ptr), _p(f, ptr), _p(ps, i32p))
+    return st, int(ps[0]), pf, H.T.copy(), f
+
+
+def tri_last_diag_as(kind):
+    _, diag, dt, ptr, _Par = _variant(kind)
+    out = np.zeros(4, dt)
+    diag(_p(out, ptr))
+    return out
+
+
 # ---- 2-point rotation RANSAC (oracle/rot_ransac_oracle.c) ----
 def mt19937_draws(seed: int, n: int, skip: int = 0) -> np.ndarray:
     """Raw outputs of std::mt19937(seed) after `skip` draws."""

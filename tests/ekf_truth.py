@@ -132,6 +132,18 @@ def visual_update(m, P, H, v, rd, trail, ns=1.0):
     return m, P, float(chi2)
 
 
+def gate_chi2(P, H, v, rd, ns=1.0):
+    """The gate's statistic alone, chi2 = ns v' S^-1 v with S = H P H' + rd I, as visual_update forms it but without the covariance
+    update (for callers that need it many times per track). H is nr x l; columns of H that are entirely zero add exact zeros to
+    every sum and are left out."""
+    H, v = np.asarray(H, LD), np.asarray(v, LD)
+    c = np.flatnonzero(np.abs(H).sum(0))
+    Hc = H[:, c]
+    S = (Hc @ np.asarray(P, LD)[np.ix_(c, c)]) @ Hc.T
+    S[np.diag_indices(len(v))] += LD(rd)
+    return LD(ns) * (v @ spd_solve(chol(S), v))
+
+
 def aug_src(n, dropped):
     """visAugA[dropped] as an index map: row i of A m takes m[src[i]], -1 a zero row."""
     src = np.full(n, -1)
