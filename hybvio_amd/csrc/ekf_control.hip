@@ -16,7 +16,7 @@
 #include "ekf_device.hpp"
 #include "ekf_host.hpp"
 
-// (as ekf.hip: the EKF is judged against a relative tolerance; the library's default is -ffp-contract=off)
+// (as ekf_update.hip: the EKF is judged against a relative tolerance; the library's default is -ffp-contract=off)
 #pragma clang fp contract(fast)
 
 namespace hv {

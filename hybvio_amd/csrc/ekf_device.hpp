@@ -1,13 +1,13 @@
-// Device building blocks shared by the EKF kernels (ekf.hip) and the fused prepare + chi2-gate kernel (vu_prepare.hip):
-// state layout constants, the f64 MFMA tile product, the in-register 16 x 16 Cholesky block factor and the chi2 table.
-// Everything lives in an anonymous namespace (force-inlined per translation unit).
+// Device building blocks shared by the EKF kernel families (ekf_predict.hip, ekf_update.hip, ekf_gate.hip, ekf_augment.hip) and the fused
+// prepare + chi2-gate kernel (vu_prepare.hip): state layout constants, the f64 MFMA tile product, the in-register 16 x 16 Cholesky block
+// factor, the chi2 table and the phase stamps. Everything lives in an anonymous namespace (force-inlined per translation unit).
 #pragma once
 #include <type_traits>
 #include "chi2inv95.h"
 #include "hv_internal.hpp"
 #include "lds_layout.hpp"
 
-// (both including translation units select fused multiply-adds for their f64 algebra; see ekf.hip)
+// (every including translation unit selects fused multiply-adds for its f64 algebra; see ekf_update.hip)
 #pragma clang fp contract(fast)
 
 namespace hv {
@@ -19,6 +19,26 @@ enum { Q_ACC = 0, Q_GYRO = 3, Q_BGA_DRIFT = 6, Q_BAA_DRIFT = 9 };
 typedef double double4v __attribute__((ext_vector_type(4)));
 
 __device__ const double d_chi2inv95[HV_CHI2INV95_N] = { HV_CHI2INV95_VALUES };
+
+// developer aid: s_memtime stamps of the kernels' phases (block 0, thread 0), read back through
+// hv_debug_ekf_phase_stamps. Compiled in only with -DHV_EKF_PHASE_STAMPS (HV_EKF_PHASE_STAMPS=1 in the
+// environment of hybvio_amd/build.py): every stamp is a scalar memory wait in the middle of a pipeline.
+// The library is not built with relocatable device code, so every file that stamps has an array of its own
+// and a reader beside its kernels (ekf_host.hpp); the entry merges them.
+#ifdef HV_EKF_PHASE_STAMPS
+__device__ long long g_phase_stamp[16];
+#define PHASE_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_phase_stamp[i] = (long long)__builtin_readcyclecounter(); } while (0)
+#define PHASE_STAMP_ARRAY g_phase_stamp
+#else
+#define PHASE_STAMP(i) do { } while (0)
+#define PHASE_STAMP_ARRAY nullptr
+#endif
+
+__device__ __forceinline__ void normalize4(double *q)
+{
+    const double nn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (nn > 0.0) { q[0] /= nn; q[1] /= nn; q[2] /= nn; q[3] /= nn; }
+}
 
 // One wavefront: acc(16x16) = A(16 x K) * B(K x 16) with A(i, k) = Ap[i*sai + k*sak] and
 // B(k, j) = Bp[k*sbk + j*sbj]. f64 MFMA operand layout: lane l carries A[l & 15][l >> 4] and

@@ -1,5 +1,6 @@
-// Host side of the EKF shared by ekf.hip (kernels, their launchers, the one-launch entries) and ekf_visit.hip (track visits, frame
-// loops, host-pointer staging): the filter object, the launch requests. Plain C++ and HIP host types, no kernel.
+// Host side of the EKF shared by the kernel families (ekf_predict.hip, ekf_update.hip, ekf_gate.hip, ekf_augment.hip: kernels, their
+// launchers, the one-launch entries), ekf.hip (create / destroy, accessors) and ekf_visit.hip (track visits, frame loops, host-pointer
+// staging): the filter object, the launch requests. Plain C++ and HIP host types, no kernel.
 #pragma once
 #include "hv_internal.hpp"
 
@@ -240,6 +241,13 @@ int ekf_launch_update(Ekf *e, const UpdateRequest &rq);
 int ekf_launch_update_paired(Ekf *e, const UpdateRequest &us, const UpdateRequest &b1, const UpdateRequest &b2, bool *done);
 int ekf_launch_gate_stream(Ekf *e, const GateStreamRequest &rq);
 int ekf_launch_sparse_gate(Ekf *e, const SparseGateRequest &rq);
+
+#ifdef HV_EKF_PHASE_STAMPS
+// the 16 stamps of one family file's own array (ekf_device.hpp), merged by hv_debug_ekf_phase_stamps
+hipError_t ekf_predict_phase_stamps(long long *out16);
+hipError_t ekf_update_phase_stamps(long long *out16);
+hipError_t ekf_gate_phase_stamps(long long *out16);
+#endif
 
 }  // namespace hv
 

@@ -1,6 +1,6 @@
 // Track visits and frame loops of the EKF (hv_ekf_visual_track* / hv_ekf_visual_frame*): which prepare, gate and update launches serve a
 // visit of a given shape, on which stream and in which order; the speculative and the batch loop; the host-pointer forms of these
-// entries. The kernels and their launchers live in ekf.hip (update, gates) and vu_prepare.hip (triangulation, prepare, fused gates);
+// entries. The kernels and their launchers live in ekf_update.hip, ekf_gate.hip and vu_prepare.hip (triangulation, prepare, fused gates);
 // the three small kernels here are launched by this file alone.
 #include <algorithm>
 #include <limits.h>

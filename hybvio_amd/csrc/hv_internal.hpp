@@ -253,7 +253,10 @@ int ransac5_init(Ctx *c);              // ransac5.hip: the kernel's dynamic-LDS 
 int ransac3_init(Ctx *c);              // ransac3.hip: likewise
 int detect_tail_init(Ctx *c);         // detect_tail.hip: likewise
 int pyramid_init(Ctx *c);             // pyramid.hip: likewise
-int ekf_kernels_init(Ctx *c);         // ekf.hip: likewise, every EKF kernel that carves dynamic LDS (lds_layout.hpp)
+int ekf_kernels_init(Ctx *c);         // ekf.hip: likewise, every EKF kernel that carves dynamic LDS (lds_layout.hpp), through ...
+int ekf_update_init(Ctx *c) __attribute__((visibility("hidden")));    // ... ekf_update.hip,
+int ekf_gate_init(Ctx *c) __attribute__((visibility("hidden")));      // ... ekf_gate.hip and
+int ekf_augment_init(Ctx *c) __attribute__((visibility("hidden")));   // ... ekf_augment.hip (hidden: the library's symbol list stays as it was)
 int vu_prepare_init(Ctx *c);          // vu_prepare.hip: likewise, the prepare / gate builds
 int rot_ransac_alloc_split(Ctx *c);     // rot_ransac.hip: the split form's record buffer, allocated and zeroed once per context
 int launch_vu_tri(Ctx *c, const VuPrepareArgs &a, hipStream_t stream = nullptr);       // the triangulation front of the split form

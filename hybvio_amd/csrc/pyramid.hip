@@ -357,7 +357,6 @@ __device__ __forceinline__ int fast_div(int i, int d, float rcp)
     return q;
 }
 __device__ __forceinline__ int tail_lwd(int w) { return (w + 8 + 3) >> 2; }
-__device__ __forceinline__ int tail_rows(int h) { return 4 * ((h + 3) >> 2) + 4; }
 
 // halo (and the ragged right end) of a level image in LDS from its interior
 __device__ __forceinline__ void tail_fill_halo(uint32_t *img, int w, int h, int lwd, int t)

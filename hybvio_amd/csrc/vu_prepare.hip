@@ -1,6 +1,6 @@
 // Per-track triangulation + prepareVisualUpdate on the device: builds the (H, y - f) of one
 // feature track per filter straight from the device-resident EKF mean, so that the chi2 gate and the visual update
-// (ekf.hip) run without the mean travelling to the host and a 2*nPoses x stateDim Jacobian travelling back.
+// (ekf_gate.hip, ekf_update.hip) run without the mean travelling to the host and a 2*nPoses x stateDim Jacobian travelling back.
 //
 // Reference: src/odometry/backend.cpp:1063-1148 (the per-track glue), src/odometry/triangulation.cpp:65-103
 // (extractCameraPoseTrail), :120-407 (Triangulator::triangulate, iterative PIVO method with derivatives),

@@ -1,4 +1,4 @@
-// Developer microbenchmark: the in-register 16x16 diagonal factor (+inverse) of ekf.hip in isolation,
+// Developer microbenchmark: the in-register 16x16 diagonal factor (+inverse) of ekf_update.hip and ekf_gate.hip (ekf_device.hpp) in isolation,
 // with pieces switched off to see which part of a column step costs what.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -75,7 +75,7 @@ int main()
     hipMalloc(&Tin, sizeof(h)); hipMalloc(&out, 64 * 8); hipMalloc(&cyc, 8);
     hipMemcpy(Tin, h, sizeof(h), hipMemcpyHostToDevice);
     long long c;
-    const char *names[] = {"full (as in ekf.hip)", "raw v_rsq_f64 (no refinement)", "no off-chain updates", "hand refinement without class test"};
+    const char *names[] = {"full (as in ekf_device.hpp)", "raw v_rsq_f64 (no refinement)", "no off-chain updates", "hand refinement without class test"};
     for (int rep = 0; rep < 2; rep++) {
         hipLaunchKernelGGL(k_diag<0>, dim3(1), dim3(64), 0, 0, Tin, out, cyc); hipMemcpy(&c, cyc, 8, hipMemcpyDeviceToHost); printf("%-40s %lld ticks\n", names[0], c);
         hipLaunchKernelGGL(k_diag<1>, dim3(1), dim3(64), 0, 0, Tin, out, cyc); hipMemcpy(&c, cyc, 8, hipMemcpyDeviceToHost); printf("%-40s %lld ticks\n", names[1], c);

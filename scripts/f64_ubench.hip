@@ -40,7 +40,7 @@ __global__ void k_mfma_ind(double *out, long long *cyc)
 }
 
 // 3 accumulators, 12 distinct A registers and 4 distinct B registers per block, operands from LDS
-// (the shape of the H P loop in ekf.hip)
+// (the shape of the H P loop in ekf_update.hip)
 __global__ void k_mfma_lds(double *out, long long *cyc)
 {
     __shared__ double hs[48 * 64];

@@ -194,7 +194,7 @@ def _set_knobs(ctx, knobs):
 
 
 def _stream_gate_serves(nr, l):
-    """ekf_launch_gate_stream's own admission rule (ekf.hip): at most 48 rows, and the zero-padded H area (16 ti x 16 lbk doubles) must
+    """ekf_launch_gate_stream's own admission rule (ekf_gate.hip): at most 48 rows, and the zero-padded H area (16 ti x 16 lbk doubles) must
     hold the 808 doubles of scratch that borrow it, within 96 KB of LDS. A declined shape falls through to the default gate kernel."""
     ti, lbk = (nr + 15) // 16, (l + 15) // 16
     rs = nr + 1
