@@ -99,6 +99,14 @@ __device__ __forceinline__ double lane_bcast(double v, int src_lane)
     return __hiloint2double(hi, lo);
 }
 
+// A value that is the same in every lane, moved to the scalar registers (it stays live across a loop without costing a VGPR pair).
+__device__ __forceinline__ double wave_uniform(double v)
+{
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+    const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
 // NW = 16, or 8 for a ragged last block of at most 8 columns: only NW column steps are run (the padding
 // columns are identity and every update they would receive is zero), W is still written 16 x 16.
 template <int NW>
@@ -173,12 +181,32 @@ __device__ __forceinline__ void lds_barrier()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// gate_factor_chi2's `exit_above` for a gate of nr rows: the rejection threshold where nobody reads chi2 (early_exit: the caller has no chi2
+// buffer), +inf otherwise. Called BEHIND the products of S: one scalar load of a table the whole grid reads, first needed when the first
+// block column is done -- a flag travels through the products instead of a value (the two-per-CU builds have no register pair for it).
+__device__ __forceinline__ double gate_exit_threshold(bool early_exit, int nr)
+{
+    nr = __builtin_amdgcn_readfirstlane(nr);
+    return (early_exit && nr < HV_CHI2INV95_N) ? d_chi2inv95[nr] : __builtin_huge_val();
+}
+
 // Second half of a chi2 gate, by one workgroup of NT threads: T holds the lower triangle of H P H' (column-major, stride Rs) and v' in row
 // nr; adds R = rd I, runs the blocked Cholesky of [S; v'] and returns chi2 = noise_scale z'z in every thread (a non-positive pivot leaves
 // inf / NaN in it). work: chol_scratch_doubles(NT / 64) doubles of LDS scratch. The caller has synchronised the workgroup behind its last write of T.
+// exit_above: the caller's rejection threshold when NOBODY reads chi2 itself, +inf ("never") otherwise. After block column j0 the entries
+// z[j0 .. j0 + w - 1] of z = L^-1 v are final (row nr of T) and chi2 = noise_scale sum z^2 only grows: once the prefix is above the
+// threshold the verdict is CHI2 whatever the remaining blocks hold (a later non-positive pivot is reported as CHI2 too), and the function
+// returns the prefix at once. The value returned is then a LOWER BOUND of chi2, not chi2. The factor (1 + 2^-20) is a condition, not a tuning
+// value: the full path sums the same squares in another order plus non-negative terms, i.e. lies within nr 2^-53 relative of something >= the
+// prefix, so it says CHI2 too. A NaN prefix (negative pivot) never exits and ends as `broken` below; an inf prefix (zero pivot) exits and is
+// `broken` in the caller. Every thread sums the same LDS values in the same order: the branch is workgroup-uniform without a reduction.
 template <int NT>
-__device__ __forceinline__ double gate_factor_chi2(double *T, int Rs, int nr, double rd, double noise_scale, double *work, long long *stamps = nullptr)
+__device__ __forceinline__ double gate_factor_chi2(double *T, int Rs, int nr, double rd, double noise_scale, double *work, long long *stamps = nullptr,
+                                                   double exit_above = __builtin_huge_val())
 {
+#ifdef HV_GATE_FULL_CHOLESKY                                    // comparison build only (never defined in the shipped library)
+    exit_above = __builtin_huge_val();
+#endif
 #ifdef HV_EKF_PHASE_STAMPS
 #define GATE_STAMP(i) do { if (stamps && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) stamps[i] = (long long)__builtin_readcyclecounter(); } while (0)
 #else
@@ -196,6 +224,7 @@ __device__ __forceinline__ double gate_factor_chi2(double *T, int Rs, int nr, do
     // their chains queue up on SIMD 0 while the other three idle.
     const int chol_wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x >> 8) & 3u));
     const int Rlim = nr + 1;
+    double prefix = 0.0;
     for (int j0 = 0; j0 < nr; j0 += 16) {
         const int w = min(16, nr - j0);
         const int ntile = (Rlim - j0 + 15) / 16;
@@ -223,6 +252,19 @@ __device__ __forceinline__ double gate_factor_chi2(double *T, int Rs, int nr, do
             }
         }
         lds_barrier();
+        if (j0 + 16 < nr && __builtin_amdgcn_readfirstlane((int)(exit_above < __builtin_huge_val()))) {     // (uniform) every block column but the last: w = 16
+            // (one LDS round trip for the 16 values and four short chains instead of one of 16 multiply-adds: an inlier pays this per block)
+            double zz[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int c = 0; c < 16; c++) { const double z = T[(size_t)(j0 + c) * Rs + nr]; zz[c & 3] += z * z; }
+            prefix = wave_uniform(prefix + ((zz[0] + zz[1]) + (zz[2] + zz[3])));
+            const double low = prefix * noise_scale;
+            if (__builtin_amdgcn_readfirstlane((int)(low > exit_above * (1.0 + 0x1p-20)))) {       // same value in every thread of the workgroup
+                GATE_STAMP(1);
+                GATE_STAMP(2);
+                return low;
+            }
+        }
     }
     GATE_STAMP(1);
     double sz = 0;
@@ -458,7 +500,7 @@ __device__ __forceinline__ void structured_S(const double *P, int N, const int *
 __device__ __forceinline__ int *gate_turn_lds() { __shared__ int turn[8]; return turn; }
 template <int TI, int NT, bool PIPE, bool TIGHT = false>
 __device__ __forceinline__ double sparse_gate(const double *P, int n, const int *acol, int na, const double *Hs, double *T, int Rs, int nr,
-                                              double rd, double noise_scale, double *work, long long *stamps = nullptr)
+                                              double rd, double noise_scale, double *work, long long *stamps = nullptr, bool early_exit = false)
 {
 #ifdef HV_EKF_PHASE_STAMPS
 #define GATE_STAMP(i) do { if (stamps && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) stamps[i] = (long long)__builtin_readcyclecounter(); } while (0)
@@ -688,7 +730,7 @@ __device__ __forceinline__ double sparse_gate(const double *P, int n, const int 
     }
     __syncthreads();
     GATE_STAMP(0);
-    return gate_factor_chi2<NT>(T, Rs, nr, rd, noise_scale, work, stamps);
+    return gate_factor_chi2<NT>(T, Rs, nr, rd, noise_scale, work, stamps, gate_exit_threshold(early_exit, nr));
 #undef GATE_STAMP
 }
 }  // namespace

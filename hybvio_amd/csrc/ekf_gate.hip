@@ -266,16 +266,18 @@ __device__ __forceinline__ void sparse_gate_kernel_body(const SparseGateArgs &a,
     __syncthreads();
     PHASE_STAMP(13);
     const double *Pb = a.P + (size_t)b * n * n;
+    // nobody reads chi2: the factorisation may stop once the track is certainly rejected (gate_exit_threshold, gate_factor_chi2)
+    const bool early_exit = a.chi2 == nullptr;
     double chi;
     if constexpr (!BIG) {
-        if (ti == 1)      chi = sparse_gate<1, NTH, true>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr);
-        else if (ti == 2) chi = sparse_gate<2, NTH, true>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr);
-        else              chi = sparse_gate<3, NTH, true>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr);
+        if (ti == 1)      chi = sparse_gate<1, NTH, true>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr, early_exit);
+        else if (ti == 2) chi = sparse_gate<2, NTH, true>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr, early_exit);
+        else              chi = sparse_gate<3, NTH, true>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr, early_exit);
     } else {
-        if (ti <= 4)      chi = sparse_gate<4, NTH, false>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr);
-        else if (ti == 5) chi = sparse_gate<5, NTH, false>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr);
-        else if (!tight)  chi = sparse_gate<6, NTH, false>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr);
-        else              chi = sparse_gate<6, NTH, false, true>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr);
+        if (ti <= 4)      chi = sparse_gate<4, NTH, false>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr, early_exit);
+        else if (ti == 5) chi = sparse_gate<5, NTH, false>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr, early_exit);
+        else if (!tight)  chi = sparse_gate<6, NTH, false>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr, early_exit);
+        else              chi = sparse_gate<6, NTH, false, true>(Pb, n, s_acol, na, Hs, T, Rs, nr, a.rd, a.noise_scale, Hs, BIG ? PHASE_STAMP_ARRAY : nullptr, early_exit);
     }
     if (t == 0) {
         const bool broken = !(chi < 1e300);                    // non-positive pivot: reported as CHI2 (ekf_update_kernel phase D)

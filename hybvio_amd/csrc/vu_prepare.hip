@@ -1093,12 +1093,14 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
                 return;
             }
         }
+        // nobody reads chi2: the factorisation may stop once the track is certainly rejected (gate_exit_threshold, gate_factor_chi2)
+        const bool early_exit = a.chi2 == nullptr;
         double chi;
         if constexpr (STRUCT) {
             lds_barrier();                                        // (v' is in row `rows` of the zeroed T)
             structured_S<VT, (VT > VT_THROUGHPUT)>(Pb, N, s_acol, na, n, ncam, rows, f_O4, f_DV, f_F4, f4s, f_WF, f_WFp, f_FA, f_DWF, f_FWF, f_G, g_cap, T, Rs, g_vu_stamp + 1);
             VU_STAMP(33);
-            chi = gate_factor_chi2<VT>(T, Rs, rows, rd_eff, a.noise_scale, f_G, g_vu_stamp + 33);
+            chi = gate_factor_chi2<VT>(T, Rs, rows, rd_eff, a.noise_scale, f_G, g_vu_stamp + 33, gate_exit_threshold(early_exit, rows));
             // every thread holds the same chi2: the inlier's compact Jacobian Hc = Dp + O4 F4, from the factor copies (intact: the gate's
             // scratch lies behind them)
             if (a.defer_h && chi < 1e300 && !((rows < HV_CHI2INV95_N) && chi > d_chi2inv95[rows])) {
@@ -1115,9 +1117,9 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
                 }
             }
         } else {
-            if (ti == 1)      chi = sparse_gate<1, VT, false>(Pb, N, s_acol, na, Hs, T, Rs, rows, rd_eff, a.noise_scale, Hs, g_vu_stamp + 33);
-            else if (ti == 2) chi = sparse_gate<2, VT, false>(Pb, N, s_acol, na, Hs, T, Rs, rows, rd_eff, a.noise_scale, Hs, g_vu_stamp + 33);
-            else              chi = sparse_gate<3, VT, false>(Pb, N, s_acol, na, Hs, T, Rs, rows, rd_eff, a.noise_scale, Hs, g_vu_stamp + 33);
+            if (ti == 1)      chi = sparse_gate<1, VT, false>(Pb, N, s_acol, na, Hs, T, Rs, rows, rd_eff, a.noise_scale, Hs, g_vu_stamp + 33, early_exit);
+            else if (ti == 2) chi = sparse_gate<2, VT, false>(Pb, N, s_acol, na, Hs, T, Rs, rows, rd_eff, a.noise_scale, Hs, g_vu_stamp + 33, early_exit);
+            else              chi = sparse_gate<3, VT, false>(Pb, N, s_acol, na, Hs, T, Rs, rows, rd_eff, a.noise_scale, Hs, g_vu_stamp + 33, early_exit);
         }
         if (tid == 0) {
             const bool broken = !(chi < 1e300);                   // non-positive pivot: reported as CHI2 (ekf_update_kernel phase D)
