@@ -30,7 +30,7 @@ f64p = C.POINTER(C.c_double)
 
 HV_MAX_LEVELS = 6
 (K_PYR_L0, K_PYR_LN, K_KLT, K_EKF_PREDICT, K_EKF_UPDATE, K_EKF_AUGMENT, K_GFTT, K_INGEST, K_VU_PREPARE, K_ROT_RANSAC, K_EKF_GATE, K_VU_TRI,
- K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL, K_TRACK_TABLE, K_RANSAC3, K_EKF_CONTROL) = range(19)
+ K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL, K_TRACK_TABLE, K_RANSAC3, K_EKF_CONTROL, K_TRAIL_INDEX) = range(20)
 RANSAC5_MAX_ITERS = 75
 RANSAC3_MAX_ITERS = 500
 # RansacResult::Type as reported by hv_ransac3_lk_batch_dev
@@ -44,6 +44,8 @@ ST_TRACKED, ST_NEW, ST_FAILED_FLOW, ST_RANSAC_OUTLIER, ST_FLOW_OUT_OF_RANGE = 0,
 ST_OUT_OF_RANGE, ST_FAILED_EPIPOLAR_CHECK, ST_CULLED, ST_BLACKLISTED = 5, 6, 7, 8
 DETECTION_FILTER_MAX_POINTS = 1024
 TRACKS_MAX_TRACKS = 1024
+TRAIL_MAX_POSES, TRAIL_MAX_VISITS = 64, 64
+TRACK_SAMPLING_GAP, TRACK_SAMPLING_ALL, TRACK_SAMPLING_RANDOM = 0, 1, 2
 DETECT_TAIL_MAX_KEYPOINTS, DETECT_TAIL_MAX_CORNERS, DETECT_TAIL_MAX_PREV, DETECT_TAIL_MAX_TRACKS = 16384, 32768, 4096, 4096
 
 
@@ -97,6 +99,22 @@ class TrackTable(C.Structure):
     """hv_track_table: device pointers owned by the caller (second_xy None = mono)."""
     _fields_ = [(k, C.c_void_p) for k in ("n_tracks", "ids", "xy", "second_xy", "status", "blacklist", "kf_xy", "kf_valid",
                                           "frame_num", "mask_steps", "mask_radius", "frame_flags")]
+
+
+class TrailIndexParams(C.Structure):
+    _fields_ = [(k, C.c_int) for k in (
+        "cameraTrailLength", "cameraTrailHanoiLength", "cameraTrailStridedLength", "cameraTrailStridedStride", "cameraTrailFixedScheme",
+        "trackSampling", "trackMinFrames", "scoreVisualUpdateTracks", "blacklistTracks", "maxVisualUpdates",
+        "maxSuccessfulVisualUpdates", "estimateImuCameraTimeShift", "useStereo", "maxTracks", "hybridMapSize",
+        "useIndependentStereoTriangulation", "fullPointCloud")]
+
+
+class TrailIndexTable(C.Structure):
+    """hv_trail_index: device pointers owned by the caller."""
+    _fields_ = [(k, C.c_void_p) for k in (
+        "n_keyframes", "frame_counter", "kf_row", "frame_number", "timestamp", "col_id", "col_len", "image_point", "norm_point",
+        "norm_velocity", "used", "n_blacklist", "blacklist_ids", "n_order", "n_skipped", "skipped_pos", "skipped_id", "cand_pos",
+        "cand_col")]
 
 
 class EkfControlParams(C.Structure):
@@ -243,6 +261,12 @@ PROTOTYPES = {
     "hv_ekf_control_init_dev": (C.c_int, [C.c_void_p, C.POINTER(EkfControlTable)]),
     "hv_ekf_imu_control_dev": (C.c_int, [C.c_void_p, C.POINTER(EkfControlParams), C.POINTER(EkfControlTable), C.c_void_p, C.c_void_p]),
     "hv_ekf_frame_control_dev": (C.c_int, [C.c_void_p, C.POINTER(EkfControlParams), C.POINTER(EkfControlTable)] + [C.c_void_p] * 7),
+    "hv_trail_index_default_params": (None, [C.POINTER(TrailIndexParams)]),
+    "hv_trail_init_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrailIndexParams), C.c_int, C.POINTER(TrailIndexTable)]),
+    "hv_trail_select_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrailIndexParams), C.c_int, C.POINTER(TrailIndexTable),
+                                            C.POINTER(TrackTable), C.c_void_p, C.c_void_p] + [C.c_void_p] * 13),
+    "hv_trail_finish_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrailIndexParams), C.c_int, C.POINTER(TrailIndexTable)]
+                                  + [C.c_void_p] * 11),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -548,6 +572,37 @@ class Context:
         self._chk(lib().hv_tracks_delete_batch_dev(self._h, C.byref(tp), n_sets, C.byref(table), max_ids, p(n_ids_dev), p(ids_dev)),
                   "hv_tracks_delete_batch_dev")
 
+    # ---- device pose-trail index: keyframes, visual-update track selection, blacklist ----
+    def trail_init_batch_dev(self, n_sets, trail: "TrailIndexTable", params: "TrailIndexParams" = None):
+        tp = params if params is not None else trail_index_default_params()
+        self._chk(lib().hv_trail_init_batch_dev(self._h, C.byref(tp), n_sets, C.byref(trail)), "hv_trail_init_batch_dev")
+
+    def trail_select_batch_dev(self, n_sets, trail: "TrailIndexTable", table: "TrackTable", cam0: "CameraModel", cam1: "CameraModel",
+                               keyframe_dev, full_update_dev, frame_num_dev, time_dev, draws_dev, draws_used_dev, n_poses_dev,
+                               pose_index_dev, features_dev, velocities_dev, y_dev, cand_id_dev, n_candidates_dev,
+                               params: "TrailIndexParams" = None):
+        """hv_trail_select_batch_dev (backend.cpp:793-800, 909-1052): pop and stamp, insert, prune, shuffle, score, filter, gather."""
+        tp = params if params is not None else trail_index_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_trail_select_batch_dev(self._h, C.byref(tp), n_sets, C.byref(trail), C.byref(table), C.addressof(cam0),
+                                                  C.addressof(cam1) if cam1 is not None else None, p(keyframe_dev), p(full_update_dev),
+                                                  p(frame_num_dev), p(time_dev), p(draws_dev), p(draws_used_dev), p(n_poses_dev),
+                                                  p(pose_index_dev), p(features_dev), p(velocities_dev), p(y_dev), p(cand_id_dev),
+                                                  p(n_candidates_dev)),
+                  "hv_trail_select_batch_dev")
+
+    def trail_finish_batch_dev(self, n_sets, trail: "TrailIndexTable", cand_id_dev, n_candidates_dev, status_dev, gate_status_dev,
+                               stationary_dev, delete_ids_dev, n_delete_dev, good_frame_dev, n_attempts_dev, n_success_dev,
+                               discarded_dev, params: "TrailIndexParams" = None):
+        """hv_trail_finish_batch_dev (backend.cpp:1189, 1204-1213, 1240-1243, 1269-1274, 804): marks, blacklist, counters, push."""
+        tp = params if params is not None else trail_index_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_trail_finish_batch_dev(self._h, C.byref(tp), n_sets, C.byref(trail), p(cand_id_dev), p(n_candidates_dev),
+                                                  p(status_dev), p(gate_status_dev), p(stationary_dev), p(delete_ids_dev),
+                                                  p(n_delete_dev), p(good_frame_dev), p(n_attempts_dev), p(n_success_dev),
+                                                  p(discarded_dev)),
+                  "hv_trail_finish_batch_dev")
+
     # ---- image ingest (f2): colour -> gray and the undistort / rectify remap in front of the pyramid ----
     def ingest_set_undistort_map(self, camera: int, pix_orig=None, valid=None):
         """pix_orig (h, w, 2) f64 = original-image position of every rectified pixel (None removes the table)."""
@@ -754,6 +809,32 @@ def track_table(**pointers) -> TrackTable:
     for k, v in pointers.items():
         setattr(t, k, v or None)
     return t
+
+
+def trail_index_default_params(**over) -> TrailIndexParams:
+    p = TrailIndexParams()
+    lib().hv_trail_index_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+class TrailIndex:
+    """hv_trail_index for n_sets sequences: torch tensors on the current device by member name (self.m) and the pointer table
+    over them (self.table). Uninitialised until trail_init_batch_dev."""
+
+    def __init__(self, n_sets: int, params: "TrailIndexParams"):
+        S, K, M, V = n_sets, params.cameraTrailLength + 1, params.maxTracks, params.maxVisualUpdates
+        Cn = 2 if params.useStereo else 1
+        i32, f64 = torch.int32, torch.float64
+        shapes = dict(n_keyframes=((S,), i32), frame_counter=((S,), i32), kf_row=((S, K), i32), frame_number=((S, K), i32),
+                      timestamp=((S, K), f64), col_id=((S, M), i32), col_len=((S, M), i32),
+                      image_point=((S, K, M, Cn, 2), torch.float32), norm_point=((S, K, M, Cn, 2), f64),
+                      norm_velocity=((S, K, M, Cn, 2), f64), used=((S, K, M), torch.uint8), n_blacklist=((S,), i32),
+                      blacklist_ids=((S, M), i32), n_order=((S,), i32), n_skipped=((S,), i32), skipped_pos=((S, M), i32),
+                      skipped_id=((S, M), i32), cand_pos=((S, V), i32), cand_col=((S, V), i32))
+        self.m = {k: torch.zeros(shape, dtype=dt, device="cuda") for k, (shape, dt) in shapes.items()}
+        self.table = TrailIndexTable(*(self.m[k].data_ptr() for k, _ in TrailIndexTable._fields_))
 
 
 def subpix_default_params(**over) -> SubpixParams:

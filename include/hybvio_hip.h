@@ -895,6 +895,126 @@ int hv_ekf_frame_control_dev(hv_ekf *ekf, const hv_ekf_control_params *p, const 
                              const int32_t *keyframe_dev, const unsigned char *full_update_dev, int32_t *keyframe_out_dev,
                              unsigned char *undo_active_dev, unsigned char *stationary_dev, unsigned char *applied_dev);
 
+/* ---- device pose-trail index: keyframes, visual-update track selection, blacklist (added within ABI 4) ----------------
+ * Replaces, for n_sets resident sequences, what Session does with odometry::EKFStateIndex between the track table and the
+ * filter (src/odometry/ekf_state_index.{hpp,cpp}; backend.cpp:793-805, 909-1052, 1189-1213, 1240-1243, 1269-1274): which
+ * observation of which track sits in which pose of the trail, which tracks visit the filter and in what order, the arrays
+ * hv_ekf_visual_frame_ragged_dev reads, the used / blacklist marks afterwards and the pose the augmentation drops. Equal,
+ * array for array, to the literal restatement in tests/trail_index_restatement.py: every rule is integer or single-rounded
+ * IEEE arithmetic (the pixel normalisation is Camera::normalizePixel of hv_camera_model, as in hv_ransac3*).
+ * The state is device memory owned by the caller. Keyframe push, pop and remove and the erasure of tracks are index
+ * permutations: kf_row maps a keyframe (0 = head) to the physical row of its observations, a live track owns one column,
+ * and because a track's observations are contiguous from keyframe 0 once prune() has run, col_len says which keyframes
+ * hold it. Between finish and the next select the head is the new, empty keyframe and a column's col_len
+ * observations sit in keyframes 1 .. col_len; after select they sit in keyframes 0 .. col_len - 1.
+ * All entries: one launch, one workgroup per set, asynchronous on the context stream, no allocation or synchronisation
+ * inside (capturable in a HIP graph). Checks made before the context is looked at: HV_ERR_INVALID for a NULL required
+ * pointer (a state member included), a negative size, maxTracks < 1, cameraTrailLength < 1, a negative Hanoi / strided
+ * length, cameraTrailHanoiLength + cameraTrailStridedLength + 1 >= maxSize (= cameraTrailLength + 1; the reference's
+ * constructor asserts), a strided stride < 1 with a strided part, a trackSampling that is no TrackSampling; then
+ * HV_ERR_UNSUPPORTED for n_sets > 65535, maxTracks > HV_TRACKS_MAX_TRACKS, maxSize > HV_TRAIL_MAX_POSES, maxVisualUpdates
+ * outside 1 .. HV_TRAIL_MAX_VISITS, TrackSampling::RANDOM (its draws depend on the visit outcomes), hybridMapSize > 0,
+ * useIndependentStereoTriangulation and fullPointCloud. Counts read from device memory are clamped to their capacity. */
+#define HV_TRAIL_MAX_POSES 64
+#define HV_TRAIL_MAX_VISITS 64
+enum { HV_TRACK_SAMPLING_GAP = 0, HV_TRACK_SAMPLING_ALL = 1, HV_TRACK_SAMPLING_RANDOM = 2 };
+typedef struct hv_trail_index_params {
+    int cameraTrailLength;                  /* 20   codegen/parameter_definitions.c */
+    int cameraTrailHanoiLength;             /* 3 */
+    int cameraTrailStridedLength;           /* 0 */
+    int cameraTrailStridedStride;           /* 2 */
+    int cameraTrailFixedScheme;             /* 0 */
+    int trackSampling;                      /* HV_TRACK_SAMPLING_GAP */
+    int trackMinFrames;                     /* 4 */
+    int scoreVisualUpdateTracks;            /* 1 */
+    int blacklistTracks;                    /* 1 */
+    int maxVisualUpdates;                   /* 20 */
+    int maxSuccessfulVisualUpdates;         /* 5 */
+    int estimateImuCameraTimeShift;         /* 1 */
+    int useStereo;                          /* 1 */
+    int maxTracks;                          /* 200 */
+    int hybridMapSize;                      /* 0; > 0 unsupported */
+    int useIndependentStereoTriangulation;  /* 0; unsupported */
+    int fullPointCloud;                     /* 0; unsupported */
+} hv_trail_index_params;
+void hv_trail_index_default_params(hv_trail_index_params *p);
+/* K = maxSize, M = maxTracks, C = useStereo ? 2 : 1, V = maxVisualUpdates; set s at s * (the size of one set) of every array. */
+typedef struct hv_trail_index {
+    int32_t *n_keyframes;    /* [n_sets]           keyframes.size() */
+    int32_t *frame_counter;  /* [n_sets]           EKFStateIndex::frameCounter */
+    int32_t *kf_row;         /* [n_sets][K]        keyframe -> physical row: a permutation of 0 .. K - 1, rows of no keyframe behind n_keyframes */
+    int32_t *frame_number;   /* [n_sets][K]        KeyFrame::frameNumber, by physical row */
+    double  *timestamp;      /* [n_sets][K]        KeyFrame::timestamp, by physical row */
+    int32_t *col_id;         /* [n_sets][M]        track ID of a column; -1 where col_len is 0 */
+    int32_t *col_len;        /* [n_sets][M]        keyframes that hold the track; 0 = free column */
+    float   *image_point;    /* [n_sets][K][M][C][2]  Feature::Frame::imagePoint (a binary32 corner, widened where it is used) */
+    double  *norm_point;     /* [n_sets][K][M][C][2]  normalizedImagePoint */
+    double  *norm_velocity;  /* [n_sets][K][M][C][2]  normalizedVelocity */
+    uint8_t *used;           /* [n_sets][K][M]     Feature::usedForVisualUpdate */
+    int32_t *n_blacklist;    /* [n_sets] */
+    int32_t *blacklist_ids;  /* [n_sets][M]        Session::blacklistedPrev, in the reference's order */
+    /* what select leaves for finish */
+    int32_t *n_order;        /* [n_sets]           trackOrder.size() */
+    int32_t *n_skipped;      /* [n_sets]           tracks skipped for the previous blacklist ... */
+    int32_t *skipped_pos;    /* [n_sets][M]        ... their positions in the order, ascending ... */
+    int32_t *skipped_id;     /* [n_sets][M]        ... and their IDs */
+    int32_t *cand_pos;       /* [n_sets][V]        position in the order of every candidate */
+    int32_t *cand_col;       /* [n_sets][V]        and its column */
+} hv_trail_index;
+/* The constructor (ekf_state_index.hpp:100-107): one keyframe (0, 0.0) without features, frame_counter 0, every column free,
+ * empty blacklist, kf_row the identity. */
+int hv_trail_init_batch_dev(hv_ctx *ctx, const hv_trail_index_params *p, int n_sets, const hv_trail_index *trail);
+/* Everything up to the visit loop (backend.cpp:793-800, 909-1052). table: n_tracks, ids, xy and (useStereo) second_xy of the
+ * hv_track_table after hv_tracks_append_batch_dev, with maxTracks slots per set; camera1 may be NULL without useStereo.
+ * keyframe_dev [n_sets] int32 = keyframe_out_dev of hv_ekf_frame_control_dev; full_update_dev [n_sets] uint8 (NULL: every frame
+ * is full); frame_num_dev [n_sets] int32 and time_dev [n_sets] double stamp the head; draws_dev [n_sets][maxTracks] = the next
+ * raw std::mt19937 outputs of each sequence, of which draws_used_dev [n_sets] = max(n - 1, 0) are consumed (n = trackOrder.size()).
+ * Per set, in this order:
+ * - pop and stamp: not a keyframe -> popHeadKeyframe (:33-39); with a single keyframe, where the reference asserts, nothing is
+ *   popped. The head takes frame_num and time.
+ * - insert, every table track in slot order: imagePoint = the corner; normalizePixel per camera (the second only with useStereo,
+ *   and not after a failure of the first); on success insertFeatureUnlessExists, updateVelocities (:361-384) when
+ *   estimateImuCameraTimeShift -- with its early returns on non-increasing timestamps and the rewrite of keyframe 1's velocity --
+ *   and the track enters trackOrder.
+ * - prune (:220-242): a track that is not in the head leaves every keyframe; its column is free.
+ * - shuffleDeterministic (util/util.hpp:39-44) over trackOrder.
+ * - trackScore (:41-87) per track: a binary32 sum, each term the binary64 L1 norm of the first camera's pixel difference, added
+ *   in binary64 and rounded to binary32 at every step; with scoreVisualUpdateTracks, minTrackScore = the element size / 2 of the
+ *   sorted int-truncated scores (-1 without tracks), else 0.
+ * - filter, in shuffled order, with createTrackIndex (:90-147): skipped when scoreVisualUpdateTracks and score < minTrackScore,
+ *   then when nValid < trackMinFrames, then on a frame that is not full, then (blacklistTracks) when the ID is in the previous
+ *   blacklist -- such a track is remembered with its position; every other track is a candidate, up to maxVisualUpdates of them.
+ * - gather, buildTrackVectors (:192-218) for candidate v, in the layout of hv_ekf_visual_frame_ragged_dev with n_tracks =
+ *   maxVisualUpdates and n_poses_max = maxSize: n_poses_dev [V][n_sets] (0: the set has no candidate v), pose_index_dev
+ *   [V][n_sets][K], features_dev / velocities_dev [V][n_sets][C * K][2] and y_dev [V][n_sets][2 * C * K], the first camera's poses
+ *   then the second's at the start of a record (the rest of a record is not written); cand_id_dev [V][n_sets] = the track ID
+ *   (-1: none), n_candidates_dev [n_sets]. */
+int hv_trail_select_batch_dev(hv_ctx *ctx, const hv_trail_index_params *p, int n_sets, const hv_trail_index *trail,
+                              const hv_track_table *table, const hv_camera_model *camera0, const hv_camera_model *camera1,
+                              const int32_t *keyframe_dev, const uint8_t *full_update_dev, const int32_t *frame_num_dev,
+                              const double *time_dev, const uint32_t *draws_dev, int32_t *draws_used_dev, int32_t *n_poses_dev,
+                              int32_t *pose_index_dev, double *features_dev, double *velocities_dev, double *y_dev,
+                              int32_t *cand_id_dev, int32_t *n_candidates_dev);
+/* The bookkeeping behind the visit loop (backend.cpp:1189, 1204-1213, 1240-1243, 1269-1274, 804). cand_id_dev / n_candidates_dev
+ * as select wrote them; status_dev [V][n_sets][2] and gate_status_dev [V][n_sets] as hv_ekf_visual_frame_ragged_dev wrote them;
+ * stationary_dev [n_sets] uint8 (NULL: 0) = stationary_dev of hv_ekf_frame_control_dev. Per set, the candidates in visit order:
+ * - visited = status[v][0] != HV_TRI_NOT_VISITED; a visited candidate with gate status 0 (INLIER) is a success: markTrackUsed
+ *   (:156-181); every other visited candidate is blacklisted and deleted when blacklistTracks.
+ * - the loop stopped at the candidate whose visit brought the successes to maxSuccessfulVisualUpdates (<= 0: no such limit) or
+ *   the attempts to maxVisualUpdates; candidates behind it are not counted. If it never stopped, the stop position is the end of
+ *   the order. A track skipped for the previous blacklist enters the new one exactly when its position precedes the stop position.
+ * - delete_ids_dev [n_sets][maxTracks] / n_delete_dev [n_sets]: the visited non-inliers in visit order (the input of
+ *   hv_tracks_delete_batch_dev with max_ids = maxTracks); the new blacklist replaces the state's, in the order of the reference.
+ * - good_frame_dev [n_sets] uint8 = (stationary || stopped) && !(attempts - successes > 5); n_attempts_dev, n_success_dev [n_sets].
+ * - pushHeadKeyframe (:23-31) with removeKeyframe (:244-281): free-slot rule, strided rule, Hanoi rule, frame_counter;
+ *   discarded_dev [n_sets] int32 = removedIdx - 1, the argument of hv_ekf_augment_dev / hv_ekf_symmetrize_augment_dev.
+ * Every output but delete_ids_dev, n_delete_dev and discarded_dev may be NULL. */
+int hv_trail_finish_batch_dev(hv_ctx *ctx, const hv_trail_index_params *p, int n_sets, const hv_trail_index *trail,
+                              const int32_t *cand_id_dev, const int32_t *n_candidates_dev, const int32_t *status_dev,
+                              const int32_t *gate_status_dev, const uint8_t *stationary_dev, int32_t *delete_ids_dev,
+                              int32_t *n_delete_dev, uint8_t *good_frame_dev, int32_t *n_attempts_dev, int32_t *n_success_dev,
+                              int32_t *discarded_dev);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
@@ -906,7 +1026,8 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3* */,
        HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev */,
-       HV_K_COUNT = 19 };
+       HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev */,
+       HV_K_COUNT = 20 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
 /* Synchronizes, then returns accumulated device milliseconds and launch count of a kernel class. */
