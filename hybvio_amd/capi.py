@@ -45,6 +45,7 @@ ST_OUT_OF_RANGE, ST_FAILED_EPIPOLAR_CHECK, ST_CULLED, ST_BLACKLISTED = 5, 6, 7, 
 DETECTION_FILTER_MAX_POINTS = 1024
 TRACKS_MAX_TRACKS = 1024
 TRAIL_MAX_POSES, TRAIL_MAX_VISITS = 64, 64
+FLOW_PREDICT_LEFT, FLOW_PREDICT_RIGHT, FLOW_PREDICT_STEREO = 0, 1, 2            # OpticalFlowPredictor::Type
 TRACK_SAMPLING_GAP, TRACK_SAMPLING_ALL, TRACK_SAMPLING_RANDOM = 0, 1, 2
 DETECT_TAIL_MAX_KEYPOINTS, DETECT_TAIL_MAX_CORNERS, DETECT_TAIL_MAX_PREV, DETECT_TAIL_MAX_TRACKS = 16384, 32768, 4096, 4096
 
@@ -115,6 +116,13 @@ class TrailIndexTable(C.Structure):
         "n_keyframes", "frame_counter", "kf_row", "frame_number", "timestamp", "col_id", "col_len", "image_point", "norm_point",
         "norm_velocity", "used", "n_blacklist", "blacklist_ids", "n_order", "n_skipped", "skipped_pos", "skipped_id", "cand_pos",
         "cand_col")]
+
+
+class FlowPredictParams(C.Structure):
+    """hv_flow_predict_params; cameraToImu / secondCameraToImu are the inverses of the two imuToCamera matrices."""
+    _fields_ = [("predictOpticalFlowMinTriangulationDistance", C.c_double), ("minBaselinePoses", C.c_int),
+                ("imuToCamera", C.c_double * 16), ("secondImuToCamera", C.c_double * 16),
+                ("cameraToImu", C.c_double * 16), ("secondCameraToImu", C.c_double * 16)]
 
 
 class EkfControlParams(C.Structure):
@@ -267,6 +275,9 @@ PROTOTYPES = {
                                             C.POINTER(TrackTable), C.c_void_p, C.c_void_p] + [C.c_void_p] * 13),
     "hv_trail_finish_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrailIndexParams), C.c_int, C.POINTER(TrailIndexTable)]
                                   + [C.c_void_p] * 11),
+    "hv_flow_predict_default_params": (None, [C.POINTER(FlowPredictParams)]),
+    "hv_flow_predict_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(FlowPredictParams), C.c_int, C.POINTER(TrailIndexParams),
+                                            C.POINTER(TrailIndexTable), C.POINTER(TrackTable)] + [C.c_void_p] * 5 + [C.c_int]),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -819,6 +830,20 @@ def trail_index_default_params(**over) -> TrailIndexParams:
     return p
 
 
+def flow_predict_default_params(imu_to_camera=None, second_imu_to_camera=None, **over) -> FlowPredictParams:
+    """hv_flow_predict_default_params; a given imuToCamera matrix is stored with its inverse (numpy.linalg.inv)."""
+    p = FlowPredictParams()
+    lib().hv_flow_predict_default_params(C.byref(p))
+    for T, name, inv in ((imu_to_camera, "imuToCamera", "cameraToImu"), (second_imu_to_camera, "secondImuToCamera", "secondCameraToImu")):
+        if T is not None:
+            T = np.asarray(T, np.float64).reshape(4, 4)
+            getattr(p, name)[:] = list(T.reshape(16))
+            getattr(p, inv)[:] = list(np.linalg.inv(T).reshape(16))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
 class TrailIndex:
     """hv_trail_index for n_sets sequences: torch tensors on the current device by member name (self.m) and the pointer table
     over them (self.table). Uninitialised until trail_init_batch_dev."""
@@ -1217,6 +1242,16 @@ class EkfBatch:
         """hv_ekf_frame_control_dev: the frame's keyframe counter, visual-stationarity ZUPT and undo mask."""
         a = [C.c_void_p(x) for x in (time_dev, keyframe_dev, full_update_dev, keyframe_out_dev, undo_active_dev, stationary_dev, applied_dev)]
         self._chk(lib().hv_ekf_frame_control_dev(self._h, C.byref(params), C.byref(ctl.table), *a), "hv_ekf_frame_control_dev")
+
+    def flow_predict_batch_dev(self, params: "FlowPredictParams", kind: int, trail_params: "TrailIndexParams", trail: "TrailIndexTable",
+                               table: "TrackTable", c0_dev, cam0: "CameraModel", cam1: "CameraModel", pred_xy_dev, distance_dev=0,
+                               reuse_distance=False):
+        """hv_flow_predict_batch_dev (backend.cpp:545-664): the LK start points of every table track of every filter's sequence.
+        kind: FLOW_PREDICT_LEFT / RIGHT / STEREO; cam1 may be None for LEFT; distance_dev 0: not kept."""
+        self._chk(lib().hv_flow_predict_batch_dev(self._h, C.byref(params), int(kind), C.byref(trail_params), C.byref(trail), C.byref(table),
+                                                  C.c_void_p(c0_dev), C.addressof(cam0), C.addressof(cam1) if cam1 is not None else None,
+                                                  C.c_void_p(pred_xy_dev), C.c_void_p(distance_dev), int(bool(reuse_distance))),
+                  "hv_flow_predict_batch_dev")
 
     def symmetrize(self):
         self._chk(lib().hv_ekf_symmetrize(self._h), "hv_ekf_symmetrize")

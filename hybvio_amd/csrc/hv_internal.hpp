@@ -269,6 +269,9 @@ int launch_vu_prepare(Ctx *c, const VuPrepareArgs &a, hipStream_t stream = nullp
 int launch_visit_order(Ctx *c, int visits, int batch, const int *np_rec_dev, int np_lo, int np_hi, int np_max, int *order_dev,
                        int *long_list_dev, int *long_count_dev);
 bool vu_fused_supported(const Ctx *c, int n_state, int np, int stereo, int batch);   // shapes the fused gate serves (else: dense path)
+// trail_index.hip: the HV_ERR_INVALID checks of hv_trail_index_params / hv_trail_index, shared with flow_predict.hip
+int trail_check_params(const hv_trail_index_params *p, int n_sets);
+int trail_check_state(const hv_trail_index *t);
 // capi.hip
 int build_levels_of_slot(Ctx *c, int slot);
 // klt.hip

@@ -536,6 +536,11 @@ void fill_common(TrailArgs &a, const hv_trail_index_params *p, int n_sets, const
 }
 
 }  // namespace
+
+// the HV_ERR_INVALID checks of the parameters and of the state, for flow_predict.hip, which reads the same state (hv_internal.hpp)
+int trail_check_params(const hv_trail_index_params *p, int n_sets) { return check_params(p, n_sets); }
+int trail_check_state(const hv_trail_index *t) { return check_trail(t); }
+
 }  // namespace hv
 
 using hv::Ctx;

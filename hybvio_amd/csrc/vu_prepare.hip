@@ -40,42 +40,7 @@ constexpr int MAXNP = 21;              // poses per camera: s_dpf is [MAXNP][21]
 constexpr int POSE_WORDS = 51;          // p[3] R[9] dR[4][9] baseline[3]
 constexpr int ITER_WORDS = 26;          // C[9] t[3] h[3] E[6] err[2] d[3]
 
-__device__ __forceinline__ void mm3(const double *A, const double *B, double *C)
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
-}
-__device__ __forceinline__ void mmT3(const double *A, const double *B, double *C)   // A B^T
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) C[3 * r + c] = A[3 * r] * B[3 * c] + A[3 * r + 1] * B[3 * c + 1] + A[3 * r + 2] * B[3 * c + 2];
-}
-__device__ __forceinline__ void mv3(const double *A, const double *x, double *y)
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r) y[r] = A[3 * r] * x[0] + A[3 * r + 1] * x[1] + A[3 * r + 2] * x[2];
-}
-__device__ __forceinline__ void mTv3(const double *A, const double *x, double *y)
-{
-#pragma unroll
-    for (int c = 0; c < 3; ++c) y[c] = A[c] * x[0] + A[3 + c] * x[1] + A[6 + c] * x[2];
-}
-
-__device__ void quat2rmat_d(const double *q, double *R, double *dR /* [4][9] */)    // util.cpp:10-47
-{
-    R[0] = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3]; R[1] = 2 * q[1] * q[2] - 2 * q[0] * q[3]; R[2] = 2 * q[1] * q[3] + 2 * q[0] * q[2];
-    R[3] = 2 * q[1] * q[2] + 2 * q[0] * q[3]; R[4] = q[0] * q[0] - q[1] * q[1] + q[2] * q[2] - q[3] * q[3]; R[5] = 2 * q[2] * q[3] - 2 * q[0] * q[1];
-    R[6] = 2 * q[1] * q[3] - 2 * q[0] * q[2]; R[7] = 2 * q[2] * q[3] + 2 * q[0] * q[1]; R[8] = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
-    const double a = 2 * q[0], b = 2 * q[1], c = 2 * q[2], d = 2 * q[3];
-    const double d0[9] = {a, -d, c, d, a, -b, -c, b, a}, d1[9] = {b, c, d, c, -b, -a, d, a, -b};
-    const double d2[9] = {-c, b, a, b, c, d, -a, d, -c}, d3[9] = {-d, -a, b, a, -d, c, b, c, d};
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { dR[k] = d0[k]; dR[9 + k] = d1[k]; dR[18 + k] = d2[k]; dR[27 + k] = d3[k]; }
-}
+#include "hv_geometry.hpp"   // mm3, mmT3, mv3, mTv3, quat2rmat_d, pinv32: compiled here under this file's contraction mode
 
 __device__ __forceinline__ void pos_ori(int i, int &pos, int &ori)                   // triangulation.cpp:989-998
 {
@@ -90,17 +55,7 @@ __device__ __forceinline__ void inverse_depth(const double *p, double *ip, doubl
     dip[0] = iz; dip[1] = 0; dip[2] = -ip[0] * iz; dip[3] = 0; dip[4] = iz; dip[5] = -ip[1] * iz; dip[6] = 0; dip[7] = 0; dip[8] = -ip[2] * iz;
 }
 
-// pseudo-inverse of the full-rank 3x2 A (row-major) and its derivative (Golub & Pereyra 4.12, triangulation.cpp:31-52)
-__device__ void pinv32(const double *A, double *iA)
-{
-    const double a = A[0] * A[0] + A[2] * A[2] + A[4] * A[4], b = A[0] * A[1] + A[2] * A[3] + A[4] * A[5];
-    const double d = A[1] * A[1] + A[3] * A[3] + A[5] * A[5], idet = 1.0 / (a * d - b * b);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        iA[c] = (d * A[2 * c] - b * A[2 * c + 1]) * idet;
-        iA[3 + c] = (-b * A[2 * c] + a * A[2 * c + 1]) * idet;
-    }
-}
+// derivative of the pseudo-inverse of the full-rank 3x2 A (Golub & Pereyra 4.12, triangulation.cpp:31-52)
 __device__ void dpinv(const double *A, const double *iA, const double *dA, double *out)
 {
     double iAiAT[4], iATiA[9], AiA[9], iAA[4], iAdA[4], t23[6], t23b[6];

@@ -1015,6 +1015,52 @@ int hv_trail_finish_batch_dev(hv_ctx *ctx, const hv_trail_index_params *p, int n
                               int32_t *n_delete_dev, uint8_t *good_frame_dev, int32_t *n_attempts_dev, int32_t *n_success_dev,
                               int32_t *discarded_dev);
 
+/* ---- device optical-flow predictor: LK start points from the filter mean and the pose-trail index (added within ABI 4) ----
+ * Replaces, for the hv_ekf_batch(ekf) resident sequences of a filter batch (set s is filter s), the OpticalFlowPredictor lambda of
+ * Session::applyTracker (src/odometry/backend.cpp:545-664), which Tracker::track calls before its temporal and its stereo LK
+ * call (src/tracker/tracker.cpp:58-62, predictOpticalFlow = true): pred_xy_dev is the next_xy of hv_klt_track_batch*_dev with
+ * use_initial_flow = 1. Per table track i < n_tracks[s], in binary64 and in the operation order of
+ * tests/flow_predict_restatement.py:
+ * - distance: EKFStateIndex::widestBaseline (ekf_state_index.cpp:312-339), the first and the last keyframe that hold the track's
+ *   ID; when they are at least minBaselinePoses apart, triangulateWithTwoCameras (triangulation.cpp:610-646) between the first
+ *   camera's poses of the two keyframes (extractCameraPoseTrail, :65-103, through imuToCamera: keyframe k is historyPosition(k - 1)
+ *   of the mean, keyframe 0 the current pose) on the first camera's norm_point, and |pf| when pf(2) > 0; otherwise -1; then
+ *   clamped from below at predictOpticalFlowMinTriangulationDistance. A track without a column (a new track, or one whose
+ *   normalizePixel failed) gets the minimum. All three types triangulate with the first camera, as the reference does.
+ * - prediction: pixelToRay(c0) * distance through camToWorld0 and worldToCam1 (util::toCameraToWorld / toWorldToCamera,
+ *   src/odometry/util.cpp:132-158, with the supplied inverse), rayToPixel, rounded to binary32; c0 itself when either camera call
+ *   fails. LEFT: history pose 0 -> current pose through imuToCamera, camera0 for both calls; RIGHT: the same through
+ *   secondImuToCamera with camera1; STEREO: current pose through imuToCamera -> current pose through secondImuToCamera, camera0
+ *   into camera1 (backend.cpp:575-612).
+ * The entry belongs between hv_trail_finish_batch_dev of the previous frame and hv_trail_select_batch_dev of this one (where
+ * applyTracker runs: after the frame's IMU predicts, the head keyframe empty), and reads the index as it is there: keyframe k
+ * holds a column's track exactly when 1 <= k <= col_len.
+ * c0_dev [n_sets][maxTracks][2] = the lambda's c0 (LEFT: table->xy; STEREO: the left corners the temporal LK produced);
+ * pred_xy_dev [n_sets][maxTracks][2]; distance_dev [n_sets][maxTracks] double or NULL. reuse_distance = 0 triangulates and writes
+ * distance_dev when it is given; 1 reads distance_dev instead (neither the index nor the mean changes between the two LK calls
+ * of a frame). Slots at and behind n_tracks[s] are not written. tp: maxTracks, cameraTrailLength and useStereo (the layout of the
+ * index) are read. A non-finite mean gives whatever this arithmetic yields in its own set and touches no other.
+ * One launch of one workgroup per set on the filter's context stream, timed under HV_K_TRAIL_INDEX, no allocation or
+ * synchronisation inside (capturable in a HIP graph). Checks made before the handle is looked at: HV_ERR_INVALID for a NULL
+ * required pointer (p, tp, trail and its members, table and its n_tracks / ids, c0_dev, camera0, pred_xy_dev; camera1 for RIGHT
+ * and STEREO), the parameter ranges of hv_trail_index_params, a type outside 0 .. 2, reuse_distance with a NULL distance_dev,
+ * minBaselinePoses < 1; then HV_ERR_UNSUPPORTED for maxTracks > HV_TRACKS_MAX_TRACKS or maxSize > HV_TRAIL_MAX_POSES; then
+ * HV_ERR_INVALID for a NULL handle and HV_ERR_UNSUPPORTED for a state of fewer than 20 + 7 * cameraTrailLength entries. Counts
+ * and indices read from device memory (n_tracks, n_keyframes, col_len, kf_row) are clamped to their capacity. */
+typedef struct hv_flow_predict_params {
+    double predictOpticalFlowMinTriangulationDistance;   /* 3.0  codegen/parameter_definitions.c:213 */
+    int    minBaselinePoses;                             /* 10   MIN_TWO_CAMERA_FLOW_TRIANGULATION_BASELINE, backend.cpp:627 */
+    double imuToCamera[16], secondImuToCamera[16];       /* row-major */
+    double cameraToImu[16], secondCameraToImu[16];       /* their inverses, formed once by the integrator (like
+                                                            hv_stereo_gate_params.cam0ToCam1): Eigen's 4x4 inverse is not restated on the device */
+} hv_flow_predict_params;
+void hv_flow_predict_default_params(hv_flow_predict_params *p);   /* the scalars as above, the four matrices identity */
+enum { HV_FLOW_PREDICT_LEFT = 0, HV_FLOW_PREDICT_RIGHT = 1, HV_FLOW_PREDICT_STEREO = 2 };   /* OpticalFlowPredictor::Type */
+int hv_flow_predict_batch_dev(hv_ekf *ekf, const hv_flow_predict_params *p, int type, const hv_trail_index_params *tp,
+                              const hv_trail_index *trail, const hv_track_table *table, const float *c0_dev,
+                              const hv_camera_model *camera0, const hv_camera_model *camera1, float *pred_xy_dev,
+                              double *distance_dev, int reuse_distance);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
@@ -1026,7 +1072,7 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3* */,
        HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev */,
-       HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev */,
+       HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev */,
        HV_K_COUNT = 20 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
