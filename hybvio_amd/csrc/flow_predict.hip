@@ -24,7 +24,8 @@
 namespace hv {
 namespace {
 
-#include "hv_geometry.hpp"
+#include "hv_geometry.hpp"    // mm3, mmT3, mv3, mTv3, quat2rmat, quat2rmat_d, pinv32
+#include "hv_workgroup.hpp"   // clampi, stage_cameras
 
 constexpr int FP_THREADS = 256;
 constexpr int FP_MAX = HV_TRACKS_MAX_TRACKS;
@@ -47,16 +48,6 @@ struct FlowArgs {
 };
 
 struct FlowCameras { hv_camera_model cam0, cam1; };
-
-__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// util::quat2rmat (util.cpp:10-26)
-__device__ inline void quat2rmat(const double *q, double *R)
-{
-    R[0] = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3]; R[1] = 2 * q[1] * q[2] - 2 * q[0] * q[3]; R[2] = 2 * q[1] * q[3] + 2 * q[0] * q[2];
-    R[3] = 2 * q[1] * q[2] + 2 * q[0] * q[3]; R[4] = q[0] * q[0] - q[1] * q[1] + q[2] * q[2] - q[3] * q[3]; R[5] = 2 * q[2] * q[3] - 2 * q[0] * q[1];
-    R[6] = 2 * q[1] * q[3] - 2 * q[0] * q[2]; R[7] = 2 * q[2] * q[3] + 2 * q[0] * q[1]; R[8] = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
-}
 
 // util::transformVec3ByMat4 (util.hpp:77-85)
 __device__ inline void transform_vec3(const double *T, const double *v, double *out)
@@ -98,13 +89,7 @@ __global__ __launch_bounds__(FP_THREADS) void flow_predict_kernel(FlowArgs a, Fl
     const int n = clampi(a.n_tracks[set], 0, M);
     const int n_kf = clampi(a.t.n_keyframes[set], 1, K);
     const double *m = a.m + (size_t)set * a.n_state;
-    {
-        static_assert(sizeof(hv_camera_model) % 4 == 0, "word copy");
-        constexpr int W = (int)(sizeof(hv_camera_model) / 4);
-        const int *src0 = reinterpret_cast<const int *>(&cams.cam0), *src1 = reinterpret_cast<const int *>(&cams.cam1);
-        int *dst = reinterpret_cast<int *>(s_cam);
-        for (int i = tid; i < 2 * W; i += FP_THREADS) dst[i] = i < W ? src0[i] : src1[i - W];
-    }
+    stage_cameras<FP_THREADS>(s_cam, cams.cam0, cams.cam1);    // published by the barrier that ends phase 2
     // ---- phase 1: the factors of the two transforms (util.cpp:132-158) on one lane, the pose trail (triangulation.cpp:65-103) on the
     // waves behind the first ----
     if (tid == 0) {

@@ -1,5 +1,6 @@
-// Device camera models shared by the RANSAC kernels (rot_ransac.hip, ransac5.hip): tracker::Camera's pixelToRay / rayToPixel
-// (src/tracker/camera.cpp:93-221 pinhole, :264-398 fisheye) in double precision, in the oracle's operation order.
+// Device camera models shared by the tracker-side kernels (rot_ransac.hip, ransac5.hip, ransac3.hip, stereo_gate.hip, trail_index.hip,
+// flow_predict.hip): tracker::Camera's pixelToRay / rayToPixel (src/tracker/camera.cpp:93-221 pinhole, :264-398 fisheye) and
+// normalizePixel (:471-476) in double precision, in the oracle's operation order.
 #pragma once
 
 #include "hv_internal.hpp"
@@ -114,6 +115,26 @@ __device__ inline bool ray_to_pixel(const hv_camera_model &c, const double *ray0
     const double u = r * dx, v = r * dy;
     pix[0] = c.fx * u + 0.0 * v + c.ppx;
     pix[1] = 0.0 * u + c.fy * v + c.ppy;
+    return true;
+}
+
+// Camera::normalizePixel (camera.cpp:471-476) of a binary32 corner, with the reference's test: `ray.z() <= 0` fails, so a NaN depth
+// passes (trail_index.hip)
+__device__ inline bool normalize_pixel(const hv_camera_model &c, float x, float y, double *out)
+{
+    double r[3];
+    if (!pixel_to_ray(c, (double)x, (double)y, r) || r[2] <= 0) return false;
+    out[0] = r[0] / r[2]; out[1] = r[1] / r[2];
+    return true;
+}
+// The same with the test of the RANSAC restatements (tests/ransac5_restatement.py: normalize, ransac3_restatement.py:
+// normalize_pixel): only `r[2] > 0` passes, so a NaN depth fails. The two differ on NaN alone and are not merged: the RANSAC kernels
+// equal their restatements, which drop such a point, and the trail keeps the reference's comparison.
+__device__ inline bool normalize_pixel_positive(const hv_camera_model &c, float x, float y, double *out)
+{
+    double r[3];
+    if (!(pixel_to_ray(c, (double)x, (double)y, r) && r[2] > 0)) return false;
+    out[0] = r[0] / r[2]; out[1] = r[1] / r[2];
     return true;
 }
 

@@ -1,10 +1,18 @@
-// Small binary64 geometry shared by the kernels that read camera poses from the EKF mean (vu_prepare.hip, flow_predict.hip): 3x3
-// products, odometry::util::quat2rmat_d (src/odometry/util.cpp:10-47) and the pseudo-inverse of a full-rank 3x2 matrix
-// (src/odometry/triangulation.cpp:1000-1002). 3x3 matrices are row-major double[9] (like oracle/triangulation_oracle.c).
+// Small binary64 geometry shared by the kernels that read camera poses from the EKF mean (vu_prepare.hip, flow_predict.hip) and by the
+// RANSAC kernels (rot_ransac.hip, ransac5.hip, ransac3.hip): 3-vector and 3x3 products, odometry::util::quat2rmat / quat2rmat_d
+// (src/odometry/util.cpp:10-47) and the pseudo-inverse of a full-rank 3x2 matrix (src/odometry/triangulation.cpp:1000-1002). 3x3
+// matrices are row-major double[9] (like oracle/triangulation_oracle.c).
 //
 // No include guard and no namespace of its own, on purpose: a translation unit includes it once, inside its anonymous namespace and
 // behind its own `#pragma clang fp contract(...)`, so the functions are compiled under the contraction mode of the file that uses
-// them (vu_prepare.hip: fast; flow_predict.hip: the build's -ffp-contract=off).
+// them (vu_prepare.hip: fast; the others: the build's -ffp-contract=off).
+
+// (a . b) with the first two products added first; a x b
+__device__ __forceinline__ double dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ void cross3(const double *a, const double *b, double *c)
+{
+    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
 
 __device__ __forceinline__ void mm3(const double *A, const double *B, double *C)
 {
@@ -31,11 +39,15 @@ __device__ __forceinline__ void mTv3(const double *A, const double *x, double *y
     for (int c = 0; c < 3; ++c) y[c] = A[c] * x[0] + A[3 + c] * x[1] + A[6 + c] * x[2];
 }
 
-__device__ void quat2rmat_d(const double *q, double *R, double *dR /* [4][9] */)    // util.cpp:10-47
+__device__ __forceinline__ void quat2rmat(const double *q, double *R)                // util.cpp:10-26
 {
     R[0] = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3]; R[1] = 2 * q[1] * q[2] - 2 * q[0] * q[3]; R[2] = 2 * q[1] * q[3] + 2 * q[0] * q[2];
     R[3] = 2 * q[1] * q[2] + 2 * q[0] * q[3]; R[4] = q[0] * q[0] - q[1] * q[1] + q[2] * q[2] - q[3] * q[3]; R[5] = 2 * q[2] * q[3] - 2 * q[0] * q[1];
     R[6] = 2 * q[1] * q[3] - 2 * q[0] * q[2]; R[7] = 2 * q[2] * q[3] + 2 * q[0] * q[1]; R[8] = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
+}
+[[maybe_unused]] __device__ void quat2rmat_d(const double *q, double *R, double *dR /* [4][9] */)    // util.cpp:10-47: R as above
+{
+    quat2rmat(q, R);
     const double a = 2 * q[0], b = 2 * q[1], c = 2 * q[2], d = 2 * q[3];
     const double d0[9] = {a, -d, c, d, a, -b, -c, b, a}, d1[9] = {b, c, d, c, -b, -a, d, a, -b};
     const double d2[9] = {-c, b, a, b, c, d, -a, d, -c}, d3[9] = {-d, -a, b, a, -d, c, b, c, d};
@@ -44,7 +56,7 @@ __device__ void quat2rmat_d(const double *q, double *R, double *dR /* [4][9] */)
 }
 
 // pseudo-inverse of the full-rank 3x2 A (row-major): (A'A)^-1 A', the determinant inverted once
-__device__ void pinv32(const double *A, double *iA)
+[[maybe_unused]] __device__ void pinv32(const double *A, double *iA)
 {
     const double a = A[0] * A[0] + A[2] * A[2] + A[4] * A[4], b = A[0] * A[1] + A[2] * A[3] + A[4] * A[5];
     const double d = A[1] * A[1] + A[3] * A[3] + A[5] * A[5], idet = 1.0 / (a * d - b * b);

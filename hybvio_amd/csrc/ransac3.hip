@@ -18,6 +18,7 @@
 // Arithmetic is binary64 in the operation order of the restatement (the library is built without FMA contraction).
 #include "hv_camera.hpp"
 #include "hv_internal.hpp"
+#include "ransac_lds.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -26,10 +27,11 @@
 namespace hv {
 namespace {
 
-constexpr int R3_THREADS = 256, R3_WAVES = R3_THREADS / 64;
+#include "hv_geometry.hpp"    // cross3, dot3
+#include "hv_workgroup.hpp"   // block_compact, block_gather_front, stage_cameras
+
 constexpr int R3_MAX_PTS = 1024;
-constexpr int R3_CHUNK = 64;                       // iterations per round; R3_CHUNK * 4 solutions = one lane each in phase d
-static_assert(R3_CHUNK * 4 == R3_THREADS, "one lane per (hypothesis, solution)");
+// R3_THREADS, R3_WAVES, R3_CHUNK (iterations per round): ransac_lds.hpp
 
 struct R3Args {
     int max_points, max_iters, min_iters, use_mle, cap, tail;
@@ -47,10 +49,22 @@ struct R3Args {
     hv_camera_model cam0, cam1;
 };
 
-__host__ __device__ constexpr size_t lds_bytes(int max_points)
+// a workgroup's LDS: the sections of Ransac3Lds as pointers, the staged cameras and secondToFirstCamera
+struct R3View {
+    double *wx, *wy, *wz, *fu, *fv, *mod, *cost, *best;
+    int *map, *vmap, *st, *idx, *chunk, *tri;
+    unsigned *draw;
+    int *cnt, *ctl;
+    const hv_camera_model *cam;
+    const double *T;
+};
+__device__ __forceinline__ R3View r3_view(unsigned char *base, const Ransac3Lds &L, const hv_camera_model *cam, const double *T)
 {
-    return sizeof(double) * ((size_t)5 * max_points + (size_t)R3_THREADS * 12 + R3_THREADS + 12) +
-           sizeof(int) * ((size_t)4 * max_points + (max_points + 63) / 64 + 1 + 3 * R3_CHUNK * 2 + R3_THREADS + 16);
+    auto d = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+    auto i = [&](size_t off) { return reinterpret_cast<int *>(base + off); };
+    return R3View{d(L.wx), d(L.wy), d(L.wz), d(L.fu), d(L.fv), d(L.mod), d(L.cost), d(L.best),
+                  i(L.map), i(L.vmap), i(L.st), i(L.idx), i(L.chunk), i(L.tri), reinterpret_cast<unsigned *>(base + L.draw),
+                  i(L.cnt), i(L.ctl), cam, T};
 }
 
 // ComputeMaxIterations for a sample of 3 (restatement: compute_max_iterations)
@@ -63,12 +77,6 @@ __host__ __device__ inline int max_iterations_for(double ratio, double logp, int
     v = v < (double)min_it ? (double)min_it : v;
     v = v > (double)max_it ? (double)max_it : v;
     return (int)v;
-}
-
-__device__ __forceinline__ double dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-__device__ __forceinline__ void cross3(const double *a, const double *b, double *c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 // triangulateStereoFeatureIdp (triangulation.cpp:711-764) and world_point = (idp.x, idp.y, 1) / idp.z (ransac_pipeline.cpp:244)
@@ -249,193 +257,151 @@ __device__ __forceinline__ double residual(const double *M, double X0, double X1
     return e0 * e0 + e1 * e1;
 }
 
-__global__ __launch_bounds__(R3_THREADS) void ransac3_kernel(R3Args a)
+// ---- the phases of ransac3_kernel (a .. f of the file header). Every thread of the workgroup calls every phase; each header says which
+// barriers the phase holds and what they publish ----
+
+// a. The correspondences of the n tracked features (ransac_pipeline.cpp:231-251): three normalizePixel calls and the triangulation per
+// lane, the m survivors compacted to the front (order kept), every status preset to RANSAC_OUTLIER (:235), the sampler's index vector and
+// the loop's control words {iteration, limit, best iteration, inliers} initialised. Returns m. Begins without a barrier (s_map, s_cam and
+// s_T are published by the caller). Barriers: one after the triangulation (publishes s_st and the points), block_compact's three,
+// block_gather_front's one; ends with one, which publishes the gathered points, s_st, s_idx and s_ctl.
+__device__ __forceinline__ int correspondences(const R3View &v, const float *pl, const float *pr, const float *cl, int n, int cap, int tid)
 {
-    extern __shared__ __attribute__((aligned(16))) double r3_lds[];
-    const int set = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int MP = a.max_points;
-    double *wx = r3_lds, *wy = wx + MP, *wz = wy + MP, *fu = wz + MP, *fv = fu + MP;
-    double *s_mod = fv + MP;                                   // [R3_THREADS][12]
-    double *s_cost = s_mod + R3_THREADS * 12;                  // [R3_THREADS] (phase c: the quartic's roots)
-    double *s_best = s_cost + R3_THREADS;                      // [12]
-    int *s_map = reinterpret_cast<int *>(s_best + 12);         // tracked k -> feature
-    int *s_vmap = s_map + MP, *s_st = s_vmap + MP, *s_idx = s_st + MP, *s_chunk = s_idx + MP;
-    int *s_tri = s_chunk + (MP + 63) / 64 + 1;                 // [R3_CHUNK][3]
-    unsigned *s_draw = reinterpret_cast<unsigned *>(s_tri + 3 * R3_CHUNK);
-    int *s_cnt = reinterpret_cast<int *>(s_draw + 3 * R3_CHUNK);   // [R3_THREADS] inlier count, -1 = no model
-    int *s_ctl = s_cnt + R3_THREADS;                           // [16]
-
-    __shared__ hv_camera_model s_cam[2];
-    __shared__ double s_T[16];
-    {
-        static_assert(sizeof(hv_camera_model) % 4 == 0, "word copy");
-        constexpr int W = (int)(sizeof(hv_camera_model) / 4);
-        const int *src0 = reinterpret_cast<const int *>(&a.cam0), *src1 = reinterpret_cast<const int *>(&a.cam1);
-        int *dst = reinterpret_cast<int *>(s_cam);
-        for (int i = tid; i < 2 * W; i += R3_THREADS) dst[i] = i < W ? src0[i] : src1[i - W];
-        if (tid < 16) s_T[tid] = a.T[tid];
-        __syncthreads();
-    }
-    const int n_all = min(max(a.n_points[set], 0), MP);
-    const float *pl = a.pl + (size_t)set * MP * 2, *pr = a.pr + (size_t)set * MP * 2, *cl = a.cl + (size_t)set * MP * 2;
-    int *ts = a.status + (size_t)set * MP;
-
-    auto compact = [&](auto pred, int *out, int count_in) -> int {
-        const int nch = (count_in + 63) / 64;
-        for (int ch = wave; ch < nch; ch += R3_WAVES) {
-            const int i = ch * 64 + lane;
-            const unsigned long long m = __ballot(i < count_in && pred(i));
-            if (lane == 0) s_chunk[ch] = __popcll(m);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int acc = 0;
-            for (int ch = 0; ch < nch; ++ch) { const int cnt = s_chunk[ch]; s_chunk[ch] = acc; acc += cnt; }
-            s_chunk[nch] = acc;
-        }
-        __syncthreads();
-        const int total = s_chunk[nch];
-        for (int ch = wave; ch < nch; ch += R3_WAVES) {
-            const int i = ch * 64 + lane;
-            const bool on = i < count_in && pred(i);
-            const unsigned long long m = __ballot(on);
-            if (on) out[s_chunk[ch] + __popcll(m & ((1ull << lane) - 1ull))] = i;
-        }
-        __syncthreads();
-        return total;
-    };
-    // ---- a. the correspondences (ransac_pipeline.cpp:231-251) ----
-    const int n = compact([&](int i) { return ts[i] == 0; }, s_map, n_all);
     for (int k = tid; k < n; k += R3_THREADS) {
-        const int src = s_map[k];
-        double r0[3], r1[3], r2[3], X[3];
-        bool ok = pixel_to_ray(s_cam[0], (double)pl[2 * src], (double)pl[2 * src + 1], r0) && r0[2] > 0;
-        ok = ok && pixel_to_ray(s_cam[1], (double)pr[2 * src], (double)pr[2 * src + 1], r1) && r1[2] > 0;
-        ok = ok && pixel_to_ray(s_cam[0], (double)cl[2 * src], (double)cl[2 * src + 1], r2) && r2[2] > 0;
-        ok = ok && triangulate_world(s_T, r0[0] / r0[2], r0[1] / r0[2], r1[0] / r1[2], r1[1] / r1[2], X);
-        s_st[k] = ok ? 1 : 0;
-        if (ok) { wx[k] = X[0]; wy[k] = X[1]; wz[k] = X[2]; fu[k] = r2[0] / r2[2]; fv[k] = r2[1] / r2[2]; }
+        const int src = v.map[k];
+        double h0[2], h1[2], h2[2], X[3];
+        bool ok = normalize_pixel_positive(v.cam[0], pl[2 * src], pl[2 * src + 1], h0);
+        ok = ok && normalize_pixel_positive(v.cam[1], pr[2 * src], pr[2 * src + 1], h1);
+        ok = ok && normalize_pixel_positive(v.cam[0], cl[2 * src], cl[2 * src + 1], h2);
+        ok = ok && triangulate_world(v.T, h0[0], h0[1], h1[0], h1[1], X);
+        v.st[k] = ok ? 1 : 0;
+        if (ok) { v.wx[k] = X[0]; v.wy[k] = X[1]; v.wz[k] = X[2]; v.fu[k] = h2[0]; v.fv[k] = h2[1]; }
     }
     __syncthreads();
-    const int m = compact([&](int k) { return s_st[k] != 0; }, s_vmap, n);
-    {
-        // gather the correspondences to the front (reads all done before the barrier, writes after)
-        static_assert(R3_MAX_PTS <= 4 * R3_THREADS, "four points per thread");
-        double hv[4][5];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = tid + q * R3_THREADS;
-            if (j < m) { const int k = s_vmap[j]; hv[q][0] = wx[k]; hv[q][1] = wy[k]; hv[q][2] = wz[k]; hv[q][3] = fu[k]; hv[q][4] = fv[k]; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = tid + q * R3_THREADS;
-            if (j < m) { wx[j] = hv[q][0]; wy[j] = hv[q][1]; wz[j] = hv[q][2]; fu[j] = hv[q][3]; fv[j] = hv[q][4]; }
-        }
-    }
-    for (int k = tid; k < n; k += R3_THREADS) s_st[k] = 3;                   // :235
-    for (int j = tid; j < m; j += R3_THREADS) s_idx[j] = j;
-    if (tid == 0) { s_ctl[0] = 0; s_ctl[1] = a.cap; s_ctl[2] = -1; s_ctl[3] = 0; }   // iteration, limit, best iteration, inliers
+    const int m = block_compact<R3_WAVES>([&](int k) { return v.st[k] != 0; }, v.vmap, n, v.chunk);
+    static_assert(R3_MAX_PTS <= 4 * R3_THREADS, "four points per thread");
+    double *const pts[5] = {v.wx, v.wy, v.wz, v.fu, v.fv};
+    block_gather_front<R3_THREADS>(pts, v.vmap, m);
+    for (int k = tid; k < n; k += R3_THREADS) v.st[k] = 3;
+    for (int j = tid; j < m; j += R3_THREADS) v.idx[j] = j;
+    if (tid == 0) { v.ctl[0] = 0; v.ctl[1] = cap; v.ctl[2] = -1; v.ctl[3] = 0; }
     __syncthreads();
+    return m;
+}
 
-    const bool run = m >= 3;
-    if (run) {
-        int i0 = 0, i1 = 1, i2 = 2;                                          // lane 0: positions 0..2 of the index vector
-        double best_cost = DBL_MAX;                                          // lane 0
-        const uint32_t *draws = a.draws + (size_t)set * 3 * a.max_iters;
-        for (;;) {
-            const int it0 = s_ctl[0], limit = s_ctl[1];
-            if (it0 >= limit) break;
-            const int h = min(R3_CHUNK, a.cap - it0);
-            if (tid < 3 * h) s_draw[tid] = draws[3 * it0 + tid];
-            __syncthreads();
-            // ---- b. the sampler: idx[i] <-> idx[i + raw % (m - i)], i = 0, 1, 2 ----
-            if (tid == 0) {
-                for (int k = 0; k < h; ++k) {
+// positions 0..2 of the sampler's index vector, kept in registers by lane 0 (the rest is s_idx)
+struct R3Head { int i0, i1, i2; };
+
+// b. The sampler for the h iterations from it0: the raw draws go to LDS, a barrier publishes them, then lane 0 replays the partial
+// shuffle idx[i] <-> idx[i + raw % (m - i)], i = 0, 1, 2, and hands each sample over in ascending index order. Ends with a barrier,
+// which publishes s_tri.
+__device__ __forceinline__ void sampler(const R3View &v, const uint32_t *draws, int it0, int h, int m, R3Head &hd, int tid)
+{
+    if (tid < 3 * h) v.draw[tid] = draws[3 * it0 + tid];
+    __syncthreads();
+    if (tid == 0) {
+        int &i0 = hd.i0, &i1 = hd.i1, &i2 = hd.i2;
+        for (int k = 0; k < h; ++k) {
 #pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        const int j = i + (int)(s_draw[3 * k + i] % (unsigned)(m - i));
-                        int &mine = i == 0 ? i0 : i == 1 ? i1 : i2;
-                        if (j >= 3) { const int o = s_idx[j]; s_idx[j] = mine; mine = o; }
-                        else { int &other = j == 0 ? i0 : j == 1 ? i1 : i2; const int o = other; other = mine; mine = o; }
-                    }
-                    // the solver's canonical order: ascending indices (a repeated triple repeats its models bit for bit)
-                    const int lo = min(i0, min(i1, i2)), hi = max(i0, max(i1, i2));
-                    s_tri[3 * k] = lo; s_tri[3 * k + 1] = i0 + i1 + i2 - lo - hi; s_tri[3 * k + 2] = hi;
-                }
+            for (int i = 0; i < 3; ++i) {
+                const int j = i + (int)(v.draw[3 * k + i] % (unsigned)(m - i));
+                int &mine = i == 0 ? i0 : i == 1 ? i1 : i2;
+                if (j >= 3) { const int o = v.idx[j]; v.idx[j] = mine; mine = o; }
+                else { int &other = j == 0 ? i0 : j == 1 ? i1 : i2; const int o = other; other = mine; mine = o; }
             }
-            __syncthreads();
-            // ---- c. one P3P per lane ----
-            if (tid < h) {
-                double Pw[3][3], F[3][2];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const int s = s_tri[3 * tid + q];
-                    Pw[q][0] = wx[s]; Pw[q][1] = wy[s]; Pw[q][2] = wz[s]; F[q][0] = fu[s]; F[q][1] = fv[s];
-                }
-                p3p_lane(Pw, F, s_cost + 4 * tid, s_cnt + 4 * tid, s_mod + 48 * tid);
-            }
-            __syncthreads();
-            // ---- d. cost and inlier count of (hypothesis, solution) = lane ----
-            {
-                const bool have = (tid >> 2) < h && s_cnt[tid] != 0;
-                double cost = 0.0;
-                int cnt = -1;
-                if (have) {
-                    double M[12];
-#pragma unroll
-                    for (int i = 0; i < 12; ++i) M[i] = s_mod[12 * tid + i];
-                    cnt = 0;
-                    for (int j = 0; j < m; ++j) {
-                        const double r = residual(M, wx[j], wy[j], wz[j], fu[j], fv[j]);
-                        const bool in = r < a.thr;
-                        cnt += in ? 1 : 0;
-                        cost = cost + (in ? r : a.thr);
-                    }
-                    if (!a.use_mle) cost = (double)(m - cnt);
-                }
-                s_cnt[tid] = cnt; s_cost[tid] = cost;                        // (over the lane's own flag and root)
-            }
-            __syncthreads();
-            // ---- e. the loop's rule over the stored costs ----
-            if (tid == 0) {
-                int it = it0, lim = limit;
-                for (int k = 0; k < h && it < lim; ++k, ++it)
-                    for (int s = 0; s < 4; ++s) {
-                        const int w = 4 * k + s, cnt = s_cnt[w];
-                        if (cnt >= 0 && s_cost[w] < best_cost) {
-                            best_cost = s_cost[w];
-                            for (int i = 0; i < 12; ++i) s_best[i] = s_mod[12 * w + i];
-                            s_ctl[2] = it; s_ctl[3] = cnt;
-                            const double ratio = (double)cnt / (double)m;
-                            if (!(ratio < 3.0 / (double)m)) lim = min(max_iterations_for(ratio, a.logp, a.min_iters, a.max_iters), lim);
-                        }
-                    }
-                s_ctl[0] = it; s_ctl[1] = lim;
-            }
-            __syncthreads();
+            // the solver's canonical order: ascending indices (a repeated triple repeats its models bit for bit)
+            const int lo = min(i0, min(i1, i2)), hi = max(i0, max(i1, i2));
+            v.tri[3 * k] = lo; v.tri[3 * k + 1] = i0 + i1 + i2 - lo - hi; v.tri[3 * k + 2] = hi;
         }
     }
-    const int iters = s_ctl[0], best_it = s_ctl[2];
+    __syncthreads();
+}
+
+// c. One P3P per lane, lanes 0 .. h - 1: up to four (R, c) into s_mod, their flags into s_cnt (s_cost holds the quartic's roots). Ends
+// with a barrier, which publishes the models and the flags.
+__device__ __forceinline__ void p3p_round(const R3View &v, int h, int tid)
+{
+    if (tid < h) {
+        double Pw[3][3], F[3][2];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int s = v.tri[3 * tid + q];
+            Pw[q][0] = v.wx[s]; Pw[q][1] = v.wy[s]; Pw[q][2] = v.wz[s]; F[q][0] = v.fu[s]; F[q][1] = v.fv[s];
+        }
+        p3p_lane(Pw, F, v.cost + 4 * tid, v.cnt + 4 * tid, v.mod + 48 * tid);
+    }
+    __syncthreads();
+}
+
+// d. Cost and inlier count of (hypothesis, solution) = lane over all m correspondences, added in order, into s_cost and s_cnt (-1: no
+// model) over the lane's own flag and root. Ends with a barrier, which publishes both.
+__device__ __forceinline__ void cost_and_count(const R3View &v, int h, int m, double thr, int use_mle, int tid)
+{
+    const bool have = (tid >> 2) < h && v.cnt[tid] != 0;
+    double cost = 0.0;
+    int cnt = -1;
+    if (have) {
+        double M[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) M[i] = v.mod[12 * tid + i];
+        cnt = 0;
+        for (int j = 0; j < m; ++j) {
+            const double r = residual(M, v.wx[j], v.wy[j], v.wz[j], v.fu[j], v.fv[j]);
+            const bool in = r < thr;
+            cnt += in ? 1 : 0;
+            cost = cost + (in ? r : thr);
+        }
+        if (!use_mle) cost = (double)(m - cnt);
+    }
+    v.cnt[tid] = cnt; v.cost[tid] = cost;
+    __syncthreads();
+}
+
+// e. The loop's rule, replayed by lane 0 over the stored costs of the round: strict `<`, adaptive limit; the best model goes to s_best,
+// the control words are brought up to date. Ends with a barrier, which publishes s_ctl (the loop's condition reads it) and s_best.
+__device__ __forceinline__ void loop_rule(const R3View &v, const R3Args &a, int it0, int limit, int h, int m, double &best_cost, int tid)
+{
+    if (tid == 0) {
+        int it = it0, lim = limit;
+        for (int k = 0; k < h && it < lim; ++k, ++it)
+            for (int s = 0; s < 4; ++s) {
+                const int w = 4 * k + s, cnt = v.cnt[w];
+                if (cnt >= 0 && v.cost[w] < best_cost) {
+                    best_cost = v.cost[w];
+                    for (int i = 0; i < 12; ++i) v.best[i] = v.mod[12 * w + i];
+                    v.ctl[2] = it; v.ctl[3] = cnt;
+                    const double ratio = (double)cnt / (double)m;
+                    if (!(ratio < 3.0 / (double)m)) lim = min(max_iterations_for(ratio, a.logp, a.min_iters, a.max_iters), lim);
+                }
+            }
+        v.ctl[0] = it; v.ctl[1] = lim;
+    }
+    __syncthreads();
+}
+
+// f. The best model's inliers go back to TRACKED (:265-268); statuses, pose, summary and the tail of compute (:139-144). Two barriers:
+// one publishes the zeroed counter s_ctl[4], one the inlier count and s_st. Begins and ends without one.
+__device__ __forceinline__ void inliers_and_outputs(const R3View &v, const R3Args &a, int set, int *ts, int n_all, int n, int m, bool run,
+                                                    int tid)
+{
+    const int iters = v.ctl[0], best_it = v.ctl[2];
     const bool success = run && best_it >= 0;
-    // ---- f. the best model's inliers go back to TRACKED (:265-268) ----
-    if (tid == 0) s_ctl[4] = 0;
+    if (tid == 0) v.ctl[4] = 0;
     __syncthreads();
     if (success) {
         double M[12];
 #pragma unroll
-        for (int i = 0; i < 12; ++i) M[i] = s_best[i];
+        for (int i = 0; i < 12; ++i) M[i] = v.best[i];
         int cnt = 0;
         for (int j = tid; j < m; j += R3_THREADS)
-            if (residual(M, wx[j], wy[j], wz[j], fu[j], fv[j]) < a.thr) { s_st[s_vmap[j]] = 0; ++cnt; }
-        if (cnt) atomicAdd(&s_ctl[4], cnt);
+            if (residual(M, v.wx[j], v.wy[j], v.wz[j], v.fu[j], v.fv[j]) < a.thr) { v.st[v.vmap[j]] = 0; ++cnt; }
+        if (cnt) atomicAdd(&v.ctl[4], cnt);
     }
     __syncthreads();
-    const int count = s_ctl[4];
+    const int count = v.ctl[4];
     if (tid == 0) {
         if (a.pose)
-            for (int i = 0; i < 12; ++i) a.pose[12 * (size_t)set + i] = success ? s_best[i] : 0.0;
+            for (int i = 0; i < 12; ++i) a.pose[12 * (size_t)set + i] = success ? v.best[i] : 0.0;
         if (a.summary) {
             int *sm = a.summary + 4 * (size_t)set;
             sm[0] = count; sm[1] = success ? best_it : -1; sm[2] = run ? iters : 0; sm[3] = m;
@@ -444,7 +410,7 @@ __global__ __launch_bounds__(R3_THREADS) void ransac3_kernel(R3Args a)
     if (a.tail && !success) {                                                // SKIPPED: every track is cleared (:139-144)
         for (int i = tid; i < n_all; i += R3_THREADS) ts[i] = 3;
     } else {
-        for (int k = tid; k < n; k += R3_THREADS) ts[s_map[k]] = s_st[k];
+        for (int k = tid; k < n; k += R3_THREADS) ts[v.map[k]] = v.st[k];
     }
     if (a.tail && tid == 0) {
         a.result[2 * (size_t)set] = success ? 2 : 0;
@@ -453,6 +419,45 @@ __global__ __launch_bounds__(R3_THREADS) void ransac3_kernel(R3Args a)
         a.score[set] = n ? (double)r2count / (double)n : 0.0;
     }
 }
+
+__global__ __launch_bounds__(R3_THREADS) void ransac3_kernel(R3Args a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char r3_lds[];
+    __shared__ hv_camera_model s_cam[2];
+    __shared__ double s_T[16];
+    const int set = blockIdx.x, tid = threadIdx.x;
+    const int MP = a.max_points;
+    const R3View v = r3_view(r3_lds, ransac3_lds(MP), s_cam, s_T);
+    stage_cameras<R3_THREADS>(s_cam, a.cam0, a.cam1);
+    if (tid < 16) s_T[tid] = a.T[tid];
+    __syncthreads();                                            // publishes s_cam and s_T
+    const int n_all = min(max(a.n_points[set], 0), MP);
+    const float *pl = a.pl + (size_t)set * MP * 2, *pr = a.pr + (size_t)set * MP * 2, *cl = a.cl + (size_t)set * MP * 2;
+    int *ts = a.status + (size_t)set * MP;
+
+    // the set: TRACKED features in feature order
+    const int n = block_compact<R3_WAVES>([&](int i) { return ts[i] == 0; }, v.map, n_all, v.chunk);
+    const int m = correspondences(v, pl, pr, cl, n, a.cap, tid);            // a
+    // m, and the control words that the loop reads behind a barrier, are the same in every thread: the conditions below are uniform
+    // over the workgroup, so the barriers inside the phases are met by every thread or by none
+    const bool run = m >= 3;
+    if (run) {
+        R3Head head{0, 1, 2};                                               // lane 0
+        double best_cost = DBL_MAX;                                         // lane 0
+        const uint32_t *draws = a.draws + (size_t)set * 3 * a.max_iters;
+        for (;;) {                                                          // rounds of up to R3_CHUNK iterations
+            const int it0 = v.ctl[0], limit = v.ctl[1];
+            if (it0 >= limit) break;
+            const int h = min(R3_CHUNK, a.cap - it0);
+            sampler(v, draws, it0, h, m, head, tid);                        // b
+            p3p_round(v, h, tid);                                           // c
+            cost_and_count(v, h, m, a.thr, a.use_mle, tid);                 // d
+            loop_rule(v, a, it0, limit, h, m, best_cost, tid);              // e
+        }
+    }
+    inliers_and_outputs(v, a, set, ts, n_all, n, m, run, tid);              // f
+}
+
 
 // the host-side checks, made before the context is looked at
 int check_params(const hv_ransac3_params *p, int max_points, int n_sets)
@@ -478,7 +483,7 @@ void fill_common(R3Args &a, const hv_ransac3_params *p, int max_points, const hv
 
 int launch(Ctx *c, int n_sets, const R3Args &a)
 {
-    hipLaunchKernelGGL(ransac3_kernel, dim3((unsigned)n_sets), dim3(R3_THREADS), lds_bytes(a.max_points), c->stream, a);
+    hipLaunchKernelGGL(ransac3_kernel, dim3((unsigned)n_sets), dim3(R3_THREADS), ransac3_lds(a.max_points).end, c->stream, a);
     HV_HIP(c, hipGetLastError());
     return HV_OK;
 }
@@ -487,7 +492,7 @@ int launch(Ctx *c, int n_sets, const R3Args &a)
 
 int ransac3_init(Ctx *c)
 {
-    HV_HIP(c, set_lds_limit(ransac3_kernel, lds_bytes(R3_MAX_PTS)));
+    HV_HIP(c, set_lds_limit(ransac3_kernel, ransac3_lds(R3_MAX_PTS).end));
     return HV_OK;
 }
 

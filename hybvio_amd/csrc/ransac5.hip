@@ -23,6 +23,7 @@
 // in the last bit.
 #include "hv_camera.hpp"
 #include "hv_internal.hpp"
+#include "ransac_lds.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -31,13 +32,13 @@
 namespace hv {
 namespace {
 
-constexpr int R5_THREADS = 256, R5_WAVES = R5_THREADS / 64;
+#include "hv_geometry.hpp"    // cross3, dot3
+#include "hv_workgroup.hpp"   // block_compact, block_gather_front, stage_cameras
+
 constexpr int R5_MAX_PTS = 1024;
 constexpr int R5_MAX_ITERS = HV_RANSAC5_MAX_ITERS;
 constexpr int DK_ITERS = 300;                                   // cv::solvePoly's default maxIters
-// per-hypothesis record (doubles): null basis EE[4][9], B[3][13], det polynomial c[11], roots re[10], im[10]
-constexpr int REC_EE = 0, REC_B = 36, REC_C = 75, REC_RE = 86, REC_IM = 96, REC = 106;
-constexpr int WS_EET = 0, WS_A = 90, WS = 290;                  // per-wave scratch: E E^T quadratics (later the minors), A[10][20]
+// R5_THREADS, R5_WAVES, the per-hypothesis record REC_* and the per-wave scratch WS_*: ransac_lds.hpp
 
 // quadratic monomial of two linear ones ([x, y, z, 1]); cubic column (Nister's order) of quadratic q times linear b
 __device__ constexpr int IDX2[4][4] = {{0, 1, 2, 3}, {1, 4, 5, 6}, {2, 5, 7, 8}, {3, 6, 8, 9}};
@@ -60,10 +61,18 @@ struct R5Args {
     hv_camera_model cam1, cam2;
 };
 
-__host__ __device__ constexpr size_t lds_bytes(int max_points, int iters)
+// a workgroup's LDS: the sections of Ransac5Lds as pointers (ws: this wavefront's scratch) and the staged cameras
+struct R5View {
+    double *px1, *py1, *px2, *py2, *recs, *ws;
+    int *good, *sub, *nroot, *ok, *map, *vmap, *st, *chunk, *misc;
+    const hv_camera_model *cam;
+};
+__device__ __forceinline__ R5View r5_view(unsigned char *base, const Ransac5Lds &L, int wave, const hv_camera_model *cam)
 {
-    return sizeof(double) * ((size_t)4 * max_points + (size_t)iters * REC + (size_t)R5_WAVES * WS) +
-           sizeof(int) * ((size_t)iters * 17 + (size_t)3 * max_points + (max_points + 63) / 64 + 1 + 16);
+    auto d = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+    auto i = [&](size_t off) { return reinterpret_cast<int *>(base + off); };
+    return R5View{d(L.px1), d(L.py1), d(L.px2), d(L.py2), d(L.recs), d(L.ws) + wave * WS,
+                  i(L.good), i(L.sub), i(L.nroot), i(L.ok), i(L.map), i(L.vmap), i(L.st), i(L.chunk), i(L.misc), cam};
 }
 
 // RANSACUpdateNumIters (ptsetreg.cpp:58-79), model points 5
@@ -93,17 +102,14 @@ __device__ bool model_of_root(const double *rec, int nroot, int r, double *E)
         row[j][2] = (((b[8] * z4 + b[9] * z3) + b[10] * z2) + b[11] * z1) + b[12];
     }
     // null vector of B(z): the longest cross product of two rows (pairs 01, 02, 12; first maximum)
-    auto cross = [](const double *a, const double *b, double *c) {
-        c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-    };
     double best[3], c[3];
-    cross(row[0], row[1], best);
-    double bs = (best[0] * best[0] + best[1] * best[1]) + best[2] * best[2];
-    cross(row[0], row[2], c);
-    double s = (c[0] * c[0] + c[1] * c[1]) + c[2] * c[2];
+    cross3(row[0], row[1], best);
+    double bs = dot3(best, best);
+    cross3(row[0], row[2], c);
+    double s = dot3(c, c);
     if (s > bs) { best[0] = c[0]; best[1] = c[1]; best[2] = c[2]; bs = s; }
-    cross(row[1], row[2], c);
-    s = (c[0] * c[0] + c[1] * c[1]) + c[2] * c[2];
+    cross3(row[1], row[2], c);
+    s = dot3(c, c);
     if (s > bs) { best[0] = c[0]; best[1] = c[1]; best[2] = c[2]; bs = s; }
     const double nrm = sqrt(bs);
     if (!(nrm > 0)) return false;
@@ -178,435 +184,411 @@ __device__ void durand_kerner(const double *d_lds, int n, double *re_out, double
     for (int i = 0; i < 10; ++i) { re_out[i] = rr[i]; im_out[i] = ri[i]; }
 }
 
-__global__ __launch_bounds__(R5_THREADS) void ransac5_kernel(R5Args a)
+// ---- the phases of ransac5_kernel, in the terms of tests/ransac5_restatement.py. Every thread of the workgroup calls every phase;
+// each header says which barriers the phase holds and what they publish ----
+
+// normalizePixel of both frames (camera.cpp:471-476) for the n tracked features, the valid ones compacted to the front (doRansac5
+// :331-343); returns their number m. Begins without a barrier (s_map and s_cam are published by the caller). Barriers: one after the
+// normalisation (publishes s_st and the points), block_compact's three, block_gather_front's one. Ends WITHOUT one: the gathered
+// points are published by the caller's next barrier (draw_subsets').
+__device__ __forceinline__ int normalise_set(const R5View &v, const float *c1, const float *c2, int n, int tid)
 {
-    extern __shared__ __attribute__((aligned(16))) double r5_lds[];
-    const int set = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int MP = a.max_points, IT = a.max_iters;
-    double *px1 = r5_lds, *py1 = px1 + MP, *px2 = py1 + MP, *py2 = px2 + MP;
-    double *recs = py2 + MP;
-    double *ws = recs + (size_t)IT * REC + wave * WS;
-    int *s_good = reinterpret_cast<int *>(r5_lds + 4 * MP + (size_t)IT * REC + R5_WAVES * WS);
-    int *s_sub = s_good + IT * 10, *s_nroot = s_sub + IT * 5, *s_ok = s_nroot + IT;
-    int *s_map = s_ok + IT, *s_vmap = s_map + MP, *s_st = s_vmap + MP, *s_chunk = s_st + MP, *s_misc = s_chunk + (MP + 63) / 64 + 1;
-
-    // the camera models go to LDS: read through kernel arguments they would occupy scalar registers for the whole kernel
-    __shared__ hv_camera_model s_cam[2];
-    {
-        static_assert(sizeof(hv_camera_model) % 4 == 0, "word copy");
-        constexpr int W = (int)(sizeof(hv_camera_model) / 4);
-        const int *src0 = reinterpret_cast<const int *>(&a.cam1), *src1 = reinterpret_cast<const int *>(&a.cam2);
-        int *dst = reinterpret_cast<int *>(s_cam);
-        for (int i = tid; i < 2 * W; i += R5_THREADS) dst[i] = i < W ? src0[i] : src1[i - W];
-        __syncthreads();
-    }
-    const int n_all = min(max(a.n_points[set], 0), MP);
-    const float *c1 = a.c1 + (size_t)set * MP * 2, *c2 = a.c2 + (size_t)set * MP * 2;
-    const bool hybrid = a.track_status != nullptr;
-    int *ts = hybrid ? a.track_status + (size_t)set * MP : nullptr;
-
-    // ---- 1. the set: TRACKED features in feature order (ransac_pipeline.cpp:106-112) ----
-    auto compact = [&](auto pred, int *out, int count_in) -> int {
-        const int nch = (count_in + 63) / 64;
-        for (int ch = wave; ch < nch; ch += R5_WAVES) {
-            const int i = ch * 64 + lane;
-            const unsigned long long m = __ballot(i < count_in && pred(i));
-            if (lane == 0) s_chunk[ch] = __popcll(m);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int acc = 0;
-            for (int ch = 0; ch < nch; ++ch) { const int cnt = s_chunk[ch]; s_chunk[ch] = acc; acc += cnt; }
-            s_chunk[nch] = acc;
-        }
-        __syncthreads();
-        const int total = s_chunk[nch];
-        for (int ch = wave; ch < nch; ch += R5_WAVES) {
-            const int i = ch * 64 + lane;
-            const bool on = i < count_in && pred(i);
-            const unsigned long long m = __ballot(on);
-            if (on) out[s_chunk[ch] + __popcll(m & ((1ull << lane) - 1ull))] = i;
-        }
-        __syncthreads();
-        return total;
-    };
-    const int n = compact([&](int i) { return !hybrid || ts[i] == 0; }, s_map, n_all);
-
-    // hybrid: RANSAC2's outcome and the skip rule (ransac_pipeline.cpp:165-167)
-    const int r2count = hybrid && n >= 2 ? a.r2_summary[2 * set] : 0;
-    const bool use_r2 = hybrid && (double)r2count > a.skip5 * (double)n;
-    const bool want5 = n >= 5 && !use_r2;
-
-    // ---- normalizePixel of both frames (camera.cpp:471-476), valid points compacted (doRansac5 :331-343) ----
-    auto normalized = [&](int k, double *h) -> bool {
-        const int src = s_map[k];
-        double r1[3], r2[3];
-        const bool ok1 = pixel_to_ray(s_cam[0], (double)c1[2 * src], (double)c1[2 * src + 1], r1) && r1[2] > 0;
-        const bool ok2 = pixel_to_ray(s_cam[1], (double)c2[2 * src], (double)c2[2 * src + 1], r2) && r2[2] > 0;
-        if (!(ok1 && ok2)) return false;
-        h[0] = r1[0] / r1[2]; h[1] = r1[1] / r1[2]; h[2] = r2[0] / r2[2]; h[3] = r2[1] / r2[2];
-        return true;
-    };
-    int m = 0;
-    if (want5) {
-        for (int k = tid; k < n; k += R5_THREADS) {
-            double h[4];
-            s_st[k] = normalized(k, h) ? 1 : 0;
-            if (s_st[k]) { px1[k] = h[0]; py1[k] = h[1]; px2[k] = h[2]; py2[k] = h[3]; }
-        }
-        __syncthreads();
-        m = compact([&](int k) { return s_st[k] != 0; }, s_vmap, n);
-        // gather the valid points to the front (reads all done before the barrier, writes after)
-        static_assert(R5_MAX_PTS <= 4 * R5_THREADS, "four points per thread");
-        double hv[4][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = tid + q * R5_THREADS;
-            if (j < m) { const int k = s_vmap[j]; hv[q][0] = px1[k]; hv[q][1] = py1[k]; hv[q][2] = px2[k]; hv[q][3] = py2[k]; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = tid + q * R5_THREADS;
-            if (j < m) { px1[j] = hv[q][0]; py1[j] = hv[q][1]; px2[j] = hv[q][2]; py2[j] = hv[q][3]; }
-        }
-    }
-    const bool run5 = want5 && m >= 5;
-    const int H = m == 5 ? 1 : IT;
-    int best = 0, bh = -1, br = -1, iters = 0;
-    if (run5) {
-        // ---- 2. getSubset with cv::RNG((uint64)-1) (ptsetreg.hpp:79-125, 142) ----
-        if (tid == 0) {
-            if (m == 5) {
-                for (int i = 0; i < 5; ++i) s_sub[i] = i;
-            } else {
-                unsigned long long state = ~0ull;
-                for (int h = 0; h < H; ++h)
-                    for (int i = 0; i < 5; ++i) {
-                        int v;
-                        for (;;) {
-                            state = (unsigned long long)(unsigned)state * 4164903690ull + (unsigned)(state >> 32);
-                            v = (int)((unsigned)state % (unsigned)m);
-                            int j = 0;
-                            while (j < i && s_sub[5 * h + j] != v) ++j;
-                            if (j == i) break;
-                        }
-                        s_sub[5 * h + i] = v;
-                    }
-            }
-        }
-        __syncthreads();
-
-        // ---- 3. minimal solves, one hypothesis per wavefront ----
-        const int rounds = (H + R5_WAVES - 1) / R5_WAVES;
-        for (int rb = 0; rb < rounds; ++rb) {
-            const int h = rb * R5_WAVES + wave;
-            const bool act = h < H;
-            double *rec = recs + (size_t)(act ? h : 0) * REC;
-            // 3a. Householder QR of M = Q^T (9 x 5): lanes 0..4 hold the columns of M, lanes 5..13 the columns of
-            // P = H4 ... H0 (rows 5..8 of P = the null basis)
-            double col[9];
-            if (lane < 5) {
-                const int s = act ? s_sub[5 * h + lane] : 0;
-                const double x1 = act ? px1[s] : 0.0, y1 = act ? py1[s] : 0.0, x2 = act ? px2[s] : 0.0, y2 = act ? py2[s] : 0.0;
-                col[0] = x1 * x2; col[1] = y1 * x2; col[2] = x2; col[3] = x1 * y2; col[4] = y1 * y2; col[5] = y2;
-                col[6] = x1; col[7] = y1; col[8] = 1.0;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 9; ++i) col[i] = (lane - 5 == i) ? 1.0 : 0.0;
-            }
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                double v[9];
-#pragma unroll
-                for (int i = k; i < 9; ++i) v[i] = __shfl(col[i], k);
-                double s = v[k] * v[k];
-#pragma unroll
-                for (int i = k + 1; i < 9; ++i) s = s + v[i] * v[i];
-                const double nrm = sqrt(s);
-                const double alpha = v[k] >= 0 ? -nrm : nrm;
-                v[k] = v[k] - alpha;
-                double vv = v[k] * v[k];
-#pragma unroll
-                for (int i = k + 1; i < 9; ++i) vv = vv + v[i] * v[i];
-                if (((lane > k && lane < 5) || (lane >= 5 && lane < 14)) && vv > 0) {
-                    double d = v[k] * col[k];
-#pragma unroll
-                    for (int i = k + 1; i < 9; ++i) d = d + v[i] * col[i];
-                    const double f = (d + d) / vv;
-#pragma unroll
-                    for (int i = k; i < 9; ++i) col[i] = col[i] - f * v[i];
-                }
-            }
-            if (act && lane >= 5 && lane < 14) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) rec[REC_EE + 9 * j + (lane - 5)] = col[5 + j];
-            }
-            __syncthreads();
-            // 3b. E E^T (quadratics), one entry per lane
-            const double *N = rec + REC_EE;
-            auto Elin = [&](int r, int c, double *p) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) p[q] = N[9 * q + 3 * r + c];
-            };
-            if (act && lane < 9) {
-                const int i = lane / 3, k = lane % 3;
-                double acc[10];
-#pragma unroll
-                for (int t = 0; t < 10; ++t) acc[t] = 0.0;
-#pragma unroll
-                for (int mm = 0; mm < 3; ++mm) {
-                    double p[4], q[4];
-                    Elin(i, mm, p); Elin(k, mm, q);
-#pragma unroll
-                    for (int x = 0; x < 4; ++x)
-#pragma unroll
-                        for (int y = 0; y < 4; ++y) acc[IDX2[x][y]] = acc[IDX2[x][y]] + p[x] * q[y];
-                }
-#pragma unroll
-                for (int t = 0; t < 10; ++t) ws[WS_EET + 10 * lane + t] = acc[t];
-            }
-            __syncthreads();
-            // 3c. rows of A: (E E^T - tr(E E^T) / 2) E (rows 0..8), det E (row 9)
-            if (act && lane < 9) {
-                const int i = lane / 3, j = lane % 3;
-                double acc[20];
-#pragma unroll
-                for (int t = 0; t < 20; ++t) acc[t] = 0.0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    double Mq[10], e[4];
-#pragma unroll
-                    for (int t = 0; t < 10; ++t) {
-                        const double x = ws[WS_EET + 10 * (3 * i + k) + t];
-                        const double ht = 0.5 * ((ws[WS_EET + t] + ws[WS_EET + 40 + t]) + ws[WS_EET + 80 + t]);
-                        Mq[t] = i == k ? x - ht : x;
-                    }
-                    Elin(k, j, e);
-#pragma unroll
-                    for (int t = 0; t < 10; ++t)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) acc[IDX3[t][b]] = acc[IDX3[t][b]] + Mq[t] * e[b];
-                }
-#pragma unroll
-                for (int t = 0; t < 20; ++t) ws[WS_A + 20 * lane + t] = acc[t];
-            } else if (act && lane == 9) {
-                double acc[20];
-#pragma unroll
-                for (int t = 0; t < 20; ++t) acc[t] = 0.0;
-                auto minor = [&](int r0, int c0, int r1, int c1_, int r2, int c2_, int r3, int c3, double *mo) {
-                    double p[4], q[4], r[4], s[4];
-                    Elin(r0, c0, p); Elin(r1, c1_, q); Elin(r2, c2_, r); Elin(r3, c3, s);
-#pragma unroll
-                    for (int t = 0; t < 10; ++t) mo[t] = 0.0;
-#pragma unroll
-                    for (int x = 0; x < 4; ++x)
-#pragma unroll
-                        for (int y = 0; y < 4; ++y) mo[IDX2[x][y]] = mo[IDX2[x][y]] + p[x] * q[y];
-#pragma unroll
-                    for (int x = 0; x < 4; ++x)
-#pragma unroll
-                        for (int y = 0; y < 4; ++y) mo[IDX2[x][y]] = mo[IDX2[x][y]] - r[x] * s[y];
-                };
-#pragma unroll
-                for (int term = 0; term < 3; ++term) {
-                    double mo[10], e[4];
-                    if (term == 0) minor(1, 1, 2, 2, 1, 2, 2, 1, mo);
-                    else if (term == 1) minor(1, 0, 2, 2, 1, 2, 2, 0, mo);
-                    else minor(1, 0, 2, 1, 1, 1, 2, 0, mo);
-                    Elin(0, term, e);
-#pragma unroll
-                    for (int x = 0; x < 4; ++x)
-#pragma unroll
-                        for (int t = 0; t < 10; ++t) {
-                            const int c = IDX3[t][x];
-                            acc[c] = term == 1 ? acc[c] - e[x] * mo[t] : acc[c] + e[x] * mo[t];
-                        }
-                }
-#pragma unroll
-                for (int t = 0; t < 20; ++t) ws[WS_A + 20 * 9 + t] = acc[t];
-            }
-            __syncthreads();
-            // 3d. elimination with partial pivoting, one column of A per lane (0..19), solved against columns 10..19
-            double cl[10];
-#pragma unroll
-            for (int r = 0; r < 10; ++r) cl[r] = lane < 20 ? ws[WS_A + 20 * r + lane] : 0.0;
-            bool ok = true;
-#pragma unroll
-            for (int k = 0; k < 10; ++k) {
-                double ck[10];
-#pragma unroll
-                for (int r = k; r < 10; ++r) ck[r] = __shfl(cl[r], k);
-                int p = k;
-                double bestv = fabs(ck[k]);
-#pragma unroll
-                for (int r = k + 1; r < 10; ++r)
-                    if (fabs(ck[r]) > bestv) { bestv = fabs(ck[r]); p = r; }
-#pragma unroll
-                for (int r = k + 1; r < 10; ++r)
-                    if (r == p) {
-                        double t = cl[k]; cl[k] = cl[r]; cl[r] = t;
-                        t = ck[k]; ck[k] = ck[r]; ck[r] = t;
-                    }
-                const double piv = ck[k];
-                ok = ok && piv != 0;
-                const double pivs = piv != 0 ? piv : 1.0;
-                if (lane > k && lane < 20) {
-#pragma unroll
-                    for (int r = k + 1; r < 10; ++r) {
-                        const double l = ck[r] / pivs;
-                        cl[r] = cl[r] - l * cl[k];
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 9; i >= 0; --i) {
-                double s = cl[i];
-#pragma unroll
-                for (int j = i + 1; j < 10; ++j) s = s - __shfl(cl[i], j) * cl[j];
-                const double u = __shfl(cl[i], i);
-                const double x = s / (u != 0 ? u : 1.0);
-                if (lane >= 10 && lane < 20) cl[i] = x;
-            }
-            if (act && lane >= 10 && lane < 20) {
-#pragma unroll
-                for (int r = 4; r < 10; ++r) ws[WS_A + 20 * r + lane] = cl[r];
-            }
-            if (act && lane == 0) s_ok[h] = ok ? 1 : 0;
-            __syncthreads();
-            // 3e. B: row i = <2i+4> - z <2i+5> (five_point.cpp:75-95)
-            if (act && lane < 39) {
-                const int i = lane / 13, t = lane % 13;
-                const int m1 = t == 0 || t == 4 || t == 8 ? -1 : t < 4 ? t - 1 : t < 8 ? t - 2 : t - 3;
-                const int m2 = t == 3 || t == 7 || t == 12 ? -1 : t < 3 ? t : t < 7 ? t - 1 : t - 2;
-                const double v1 = m1 >= 0 ? ws[WS_A + 20 * (2 * i + 4) + 10 + m1] : 0.0;
-                const double v2 = m2 >= 0 ? ws[WS_A + 20 * (2 * i + 5) + 10 + m2] : 0.0;
-                rec[REC_B + lane] = v1 - v2;
-            }
-            __syncthreads();
-            // 3f. det B(z): the three 2 x 2 minors (one coefficient per lane), then the degree-10 polynomial
-            const double *B = rec + REC_B;
-            auto bpoly = [&](int j, int part, int i) -> double {      // ascending coefficient i of x / y / 1 of row j
-                return part == 0 ? (i < 4 ? B[13 * j + 3 - i] : 0.0) : part == 1 ? (i < 4 ? B[13 * j + 7 - i] : 0.0)
-                                                                                 : (i < 5 ? B[13 * j + 12 - i] : 0.0);
-            };
-            auto plen = [](int part) { return part == 2 ? 5 : 4; };
-            if (act && lane < 23) {
-                const int which = lane < 8 ? 0 : lane < 16 ? 1 : 2, k = lane < 8 ? lane : lane < 16 ? lane - 8 : lane - 16;
-                // m0 = y1 c2 - c1 y2, m1 = x1 c2 - c1 x2, m2 = x1 y2 - y1 x2
-                const int pa = which == 0 ? 1 : 0, qa = which == 2 ? 1 : 2, ra = which == 2 ? 1 : 2, sa = which == 0 ? 1 : 0;
-                double acc = 0.0;
-                for (int i = 0; i < plen(pa); ++i) {
-                    const int j = k - i;
-                    if (j >= 0 && j < plen(qa)) acc = acc + bpoly(1, pa, i) * bpoly(2, qa, j);
-                }
-                for (int i = 0; i < plen(ra); ++i) {
-                    const int j = k - i;
-                    if (j >= 0 && j < plen(sa)) acc = acc - bpoly(1, ra, i) * bpoly(2, sa, j);
-                }
-                ws[WS_EET + 8 * which + k] = acc;
-            }
-            __syncthreads();
-            if (act && lane < 11) {
-                const int k = lane;
-                double acc = 0.0;
-                for (int i = 0; i < 4; ++i) { const int j = k - i; if (j >= 0 && j < 8) acc = acc + bpoly(0, 0, i) * ws[WS_EET + j]; }
-                for (int i = 0; i < 4; ++i) { const int j = k - i; if (j >= 0 && j < 8) acc = acc - bpoly(0, 1, i) * ws[WS_EET + 8 + j]; }
-                for (int i = 0; i < 5; ++i) { const int j = k - i; if (j >= 0 && j < 7) acc = acc + bpoly(0, 2, i) * ws[WS_EET + 16 + j]; }
-                rec[REC_C + k] = acc;
-            }
-            __syncthreads();
-        }
-
-        // ---- 4. cv::solvePoly, one hypothesis per lane ----
-        for (int h = tid; h < H; h += R5_THREADS) {
-            double *rec = recs + (size_t)h * REC;
-            int nr = 0;
-            if (s_ok[h]) {
-                nr = 10;
-                while (nr > 1 && !(fabs(rec[REC_C + nr]) > DBL_EPSILON)) --nr;
-                double re[10], im[10];
-                durand_kerner(rec + REC_C, nr, re, im);
-#pragma unroll
-                for (int i = 0; i < 10; ++i) { rec[REC_RE + i] = re[i]; rec[REC_IM + i] = im[i]; }
-            }
-            s_nroot[h] = nr;
-        }
-        __syncthreads();
-
-        // ---- 5. models and their inlier counts, one (hypothesis, root) per lane ----
-        if (m > 5) {
-            for (int w = tid; w < H * 10; w += R5_THREADS) {
-                const int h = w / 10, r = w - 10 * h;
-                double E[9];
-                int g = -1;
-                if (model_of_root(recs + (size_t)h * REC, s_nroot[h], r, E)) {
-                    g = 0;
-                    for (int j = 0; j < m; ++j) g += sampson_inlier(E, px1[j], py1[j], px2[j], py2[j], a.thr2) ? 1 : 0;
-                }
-                s_good[w] = g;
-            }
-            __syncthreads();
-            // ---- 6. the registrator loop (ptsetreg.hpp:176-199) over the stored counts ----
-            if (tid == 0) {
-                int niters = max(IT, 1), it = 0;
-                for (; it < niters; ++it)
-                    for (int r = 0; r < 10; ++r) {
-                        const int g = s_good[10 * it + r];
-                        if (g >= 0 && g > max(best, 4)) {
-                            best = g; bh = it; br = r;
-                            niters = update_num_iters(a.prob, (double)(m - g) / (double)m, niters);
-                        }
-                    }
-                s_misc[0] = best; s_misc[1] = bh; s_misc[2] = br; s_misc[3] = it;
-            }
-            __syncthreads();
-            best = s_misc[0]; bh = s_misc[1]; br = s_misc[2]; iters = s_misc[3];
-        }
-        // the mask: the best model's inliers; without one the pre-filled all-1 mask stays (doRansac5 :345)
-        double Eb[9];
-        const bool have = best > 0 && model_of_root(recs + (size_t)bh * REC, s_nroot[bh], br, Eb);
-        for (int k = tid; k < n; k += R5_THREADS) s_st[k] = 3;
-        __syncthreads();
-        for (int j = tid; j < m; j += R5_THREADS)
-            s_st[s_vmap[j]] = (!have || sampson_inlier(Eb, px1[j], py1[j], px2[j], py2[j], a.thr2)) ? 0 : 3;
-        if (tid == 0) {
-            double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            if (have) {
-                for (int i = 0; i < 9; ++i) E[i] = Eb[i];
-            } else if (m == 5) {                                       // count == modelPoints: the kernel's first model
-                for (int r = 0; r < 10; ++r)
-                    if (model_of_root(recs, s_nroot[0], r, E)) break;
-                    else for (int i = 0; i < 9; ++i) E[i] = 0.0;
-            }
-            if (a.E) for (int i = 0; i < 9; ++i) a.E[9 * (size_t)set + i] = E[i];
-        }
-    } else {
-        for (int k = tid; k < n; k += R5_THREADS) s_st[k] = 3;
-        if (tid == 0 && a.E)
-            for (int i = 0; i < 9; ++i) a.E[9 * (size_t)set + i] = 0.0;
+    for (int k = tid; k < n; k += R5_THREADS) {
+        const int src = v.map[k];
+        double h1[2], h2[2];
+        const bool ok1 = normalize_pixel_positive(v.cam[0], c1[2 * src], c1[2 * src + 1], h1);
+        const bool ok2 = normalize_pixel_positive(v.cam[1], c2[2 * src], c2[2 * src + 1], h2);
+        v.st[k] = ok1 && ok2 ? 1 : 0;
+        if (v.st[k]) { v.px1[k] = h1[0]; v.py1[k] = h1[1]; v.px2[k] = h2[0]; v.py2[k] = h2[1]; }
     }
     __syncthreads();
-    // inlier count of the RANSAC5 result (ransac_pipeline.cpp:390-394)
-    if (tid == 0) s_misc[4] = 0;
+    const int m = block_compact<R5_WAVES>([&](int k) { return v.st[k] != 0; }, v.vmap, n, v.chunk);
+    static_assert(R5_MAX_PTS <= 4 * R5_THREADS, "four points per thread");
+    double *const pts[4] = {v.px1, v.py1, v.px2, v.py2};
+    block_gather_front<R5_THREADS>(pts, v.vmap, m);
+    return m;
+}
+
+// getSubset with cv::RNG((uint64)-1) (ptsetreg.hpp:79-125, 142) on thread 0: H x 5 indices into s_sub. Ends with a barrier, which
+// publishes s_sub and the gathered points of normalise_set.
+__device__ __forceinline__ void draw_subsets(const R5View &v, int m, int H, int tid)
+{
+    if (tid == 0) {
+        if (m == 5) {
+            for (int i = 0; i < 5; ++i) v.sub[i] = i;
+        } else {
+            unsigned long long state = ~0ull;
+            for (int h = 0; h < H; ++h)
+                for (int i = 0; i < 5; ++i) {
+                    int x;
+                    for (;;) {
+                        state = (unsigned long long)(unsigned)state * 4164903690ull + (unsigned)(state >> 32);
+                        x = (int)((unsigned)state % (unsigned)m);
+                        int j = 0;
+                        while (j < i && v.sub[5 * h + j] != x) ++j;
+                        if (j == i) break;
+                    }
+                    v.sub[5 * h + i] = x;
+                }
+        }
+    }
+    __syncthreads();
+}
+
+// linear polynomial ([x, y, z, 1]) of entry (r, c) of E over the null basis N
+__device__ __forceinline__ void e_lin(const double *N, int r, int c, double *p)
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) p[q] = N[9 * q + 3 * r + c];
+}
+
+// 3a. Householder QR of M = Q^T (9 x 5) of hypothesis h, one per wavefront: lanes 0..4 hold the columns of M, lanes 5..13 the columns
+// of P = H4 ... H0 (rows 5..8 of P = the null basis, into rec[REC_EE]). Ends with a barrier, which publishes the null basis.
+__device__ __forceinline__ void null_basis(const R5View &v, double *rec, int h, bool act, int lane)
+{
+    double col[9];
+    if (lane < 5) {
+        const int s = act ? v.sub[5 * h + lane] : 0;
+        const double x1 = act ? v.px1[s] : 0.0, y1 = act ? v.py1[s] : 0.0, x2 = act ? v.px2[s] : 0.0, y2 = act ? v.py2[s] : 0.0;
+        col[0] = x1 * x2; col[1] = y1 * x2; col[2] = x2; col[3] = x1 * y2; col[4] = y1 * y2; col[5] = y2;
+        col[6] = x1; col[7] = y1; col[8] = 1.0;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) col[i] = (lane - 5 == i) ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        double u[9];
+#pragma unroll
+        for (int i = k; i < 9; ++i) u[i] = __shfl(col[i], k);
+        double s = u[k] * u[k];
+#pragma unroll
+        for (int i = k + 1; i < 9; ++i) s = s + u[i] * u[i];
+        const double nrm = sqrt(s);
+        const double alpha = u[k] >= 0 ? -nrm : nrm;
+        u[k] = u[k] - alpha;
+        double vv = u[k] * u[k];
+#pragma unroll
+        for (int i = k + 1; i < 9; ++i) vv = vv + u[i] * u[i];
+        if (((lane > k && lane < 5) || (lane >= 5 && lane < 14)) && vv > 0) {
+            double d = u[k] * col[k];
+#pragma unroll
+            for (int i = k + 1; i < 9; ++i) d = d + u[i] * col[i];
+            const double f = (d + d) / vv;
+#pragma unroll
+            for (int i = k; i < 9; ++i) col[i] = col[i] - f * u[i];
+        }
+    }
+    if (act && lane >= 5 && lane < 14) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rec[REC_EE + 9 * j + (lane - 5)] = col[5 + j];
+    }
+    __syncthreads();
+}
+
+// 3b + 3c. The 10 x 20 cubic-constraint matrix A into the wave's scratch: E E^T (quadratics, one entry per lane), a barrier that
+// publishes them, then the rows of A: (E E^T - tr(E E^T) / 2) E (rows 0..8, lanes 0..8) and det E (row 9, lane 9). Ends with a barrier,
+// which publishes A.
+__device__ __forceinline__ void coeff_matrix(const R5View &v, const double *rec, bool act, int lane)
+{
+    double *ws = v.ws;
+    const double *N = rec + REC_EE;
+    if (act && lane < 9) {
+        const int i = lane / 3, k = lane % 3;
+        double acc[10];
+#pragma unroll
+        for (int t = 0; t < 10; ++t) acc[t] = 0.0;
+#pragma unroll
+        for (int mm = 0; mm < 3; ++mm) {
+            double p[4], q[4];
+            e_lin(N, i, mm, p); e_lin(N, k, mm, q);
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) acc[IDX2[x][y]] = acc[IDX2[x][y]] + p[x] * q[y];
+        }
+#pragma unroll
+        for (int t = 0; t < 10; ++t) ws[WS_EET + 10 * lane + t] = acc[t];
+    }
+    __syncthreads();
+    if (act && lane < 9) {
+        const int i = lane / 3, j = lane % 3;
+        double acc[20];
+#pragma unroll
+        for (int t = 0; t < 20; ++t) acc[t] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            double Mq[10], e[4];
+#pragma unroll
+            for (int t = 0; t < 10; ++t) {
+                const double x = ws[WS_EET + 10 * (3 * i + k) + t];
+                const double ht = 0.5 * ((ws[WS_EET + t] + ws[WS_EET + 40 + t]) + ws[WS_EET + 80 + t]);
+                Mq[t] = i == k ? x - ht : x;
+            }
+            e_lin(N, k, j, e);
+#pragma unroll
+            for (int t = 0; t < 10; ++t)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[IDX3[t][b]] = acc[IDX3[t][b]] + Mq[t] * e[b];
+        }
+#pragma unroll
+        for (int t = 0; t < 20; ++t) ws[WS_A + 20 * lane + t] = acc[t];
+    } else if (act && lane == 9) {
+        double acc[20];
+#pragma unroll
+        for (int t = 0; t < 20; ++t) acc[t] = 0.0;
+        auto minor = [&](int r0, int c0, int r1, int c1_, int r2, int c2_, int r3, int c3, double *mo) {
+            double p[4], q[4], r[4], s[4];
+            e_lin(N, r0, c0, p); e_lin(N, r1, c1_, q); e_lin(N, r2, c2_, r); e_lin(N, r3, c3, s);
+#pragma unroll
+            for (int t = 0; t < 10; ++t) mo[t] = 0.0;
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) mo[IDX2[x][y]] = mo[IDX2[x][y]] + p[x] * q[y];
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) mo[IDX2[x][y]] = mo[IDX2[x][y]] - r[x] * s[y];
+        };
+#pragma unroll
+        for (int term = 0; term < 3; ++term) {
+            double mo[10], e[4];
+            if (term == 0) minor(1, 1, 2, 2, 1, 2, 2, 1, mo);
+            else if (term == 1) minor(1, 0, 2, 2, 1, 2, 2, 0, mo);
+            else minor(1, 0, 2, 1, 1, 1, 2, 0, mo);
+            e_lin(N, 0, term, e);
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int t = 0; t < 10; ++t) {
+                    const int c = IDX3[t][x];
+                    acc[c] = term == 1 ? acc[c] - e[x] * mo[t] : acc[c] + e[x] * mo[t];
+                }
+        }
+#pragma unroll
+        for (int t = 0; t < 20; ++t) ws[WS_A + 20 * 9 + t] = acc[t];
+    }
+    __syncthreads();
+}
+
+// 3d. Gaussian elimination with partial pivoting of the left block of A, one column per lane (0..19), solved against columns 10..19;
+// rows 4..9 of the solution go back into A, the pivots' verdict into s_ok[h]. Ends with a barrier, which publishes both.
+__device__ __forceinline__ void eliminate(const R5View &v, int h, bool act, int lane)
+{
+    double *ws = v.ws;
+    double cl[10];
+#pragma unroll
+    for (int r = 0; r < 10; ++r) cl[r] = lane < 20 ? ws[WS_A + 20 * r + lane] : 0.0;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+        double ck[10];
+#pragma unroll
+        for (int r = k; r < 10; ++r) ck[r] = __shfl(cl[r], k);
+        int p = k;
+        double bestv = fabs(ck[k]);
+#pragma unroll
+        for (int r = k + 1; r < 10; ++r)
+            if (fabs(ck[r]) > bestv) { bestv = fabs(ck[r]); p = r; }
+#pragma unroll
+        for (int r = k + 1; r < 10; ++r)
+            if (r == p) {
+                double t = cl[k]; cl[k] = cl[r]; cl[r] = t;
+                t = ck[k]; ck[k] = ck[r]; ck[r] = t;
+            }
+        const double piv = ck[k];
+        ok = ok && piv != 0;
+        const double pivs = piv != 0 ? piv : 1.0;
+        if (lane > k && lane < 20) {
+#pragma unroll
+            for (int r = k + 1; r < 10; ++r) {
+                const double l = ck[r] / pivs;
+                cl[r] = cl[r] - l * cl[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 9; i >= 0; --i) {
+        double s = cl[i];
+#pragma unroll
+        for (int j = i + 1; j < 10; ++j) s = s - __shfl(cl[i], j) * cl[j];
+        const double u = __shfl(cl[i], i);
+        const double x = s / (u != 0 ? u : 1.0);
+        if (lane >= 10 && lane < 20) cl[i] = x;
+    }
+    if (act && lane >= 10 && lane < 20) {
+#pragma unroll
+        for (int r = 4; r < 10; ++r) ws[WS_A + 20 * r + lane] = cl[r];
+    }
+    if (act && lane == 0) v.ok[h] = ok ? 1 : 0;
+    __syncthreads();
+}
+
+// 3e. B (3 x 13) into rec[REC_B], one entry per lane: row i = <2i+4> - z <2i+5> (five_point.cpp:75-95). Ends with a barrier, which
+// publishes B.
+__device__ __forceinline__ void b_matrix(const R5View &v, double *rec, bool act, int lane)
+{
+    const double *ws = v.ws;
+    if (act && lane < 39) {
+        const int i = lane / 13, t = lane % 13;
+        const int m1 = t == 0 || t == 4 || t == 8 ? -1 : t < 4 ? t - 1 : t < 8 ? t - 2 : t - 3;
+        const int m2 = t == 3 || t == 7 || t == 12 ? -1 : t < 3 ? t : t < 7 ? t - 1 : t - 2;
+        const double v1 = m1 >= 0 ? ws[WS_A + 20 * (2 * i + 4) + 10 + m1] : 0.0;
+        const double v2 = m2 >= 0 ? ws[WS_A + 20 * (2 * i + 5) + 10 + m2] : 0.0;
+        rec[REC_B + lane] = v1 - v2;
+    }
+    __syncthreads();
+}
+
+// ascending coefficient i of the x / y / 1 polynomial (part 0 / 1 / 2) of row j of B, and the polynomial's length
+__device__ __forceinline__ double b_poly(const double *B, int j, int part, int i)
+{
+    return part == 0 ? (i < 4 ? B[13 * j + 3 - i] : 0.0) : part == 1 ? (i < 4 ? B[13 * j + 7 - i] : 0.0)
+                                                                     : (i < 5 ? B[13 * j + 12 - i] : 0.0);
+}
+__device__ __forceinline__ int b_poly_len(int part) { return part == 2 ? 5 : 4; }
+
+// 3f. det B(z) into rec[REC_C] by polynomial convolution: the three 2 x 2 minors of rows 1 and 2 (one coefficient per lane, into the
+// wave's scratch), a barrier that publishes them, then the degree-10 polynomial (one coefficient per lane). Ends with a barrier, which
+// publishes the polynomial and frees the scratch for the next round.
+__device__ __forceinline__ void det_poly(const R5View &v, double *rec, bool act, int lane)
+{
+    double *ws = v.ws;
+    const double *B = rec + REC_B;
+    if (act && lane < 23) {
+        const int which = lane < 8 ? 0 : lane < 16 ? 1 : 2, k = lane < 8 ? lane : lane < 16 ? lane - 8 : lane - 16;
+        // m0 = y1 c2 - c1 y2, m1 = x1 c2 - c1 x2, m2 = x1 y2 - y1 x2
+        const int pa = which == 0 ? 1 : 0, qa = which == 2 ? 1 : 2, ra = which == 2 ? 1 : 2, sa = which == 0 ? 1 : 0;
+        double acc = 0.0;
+        for (int i = 0; i < b_poly_len(pa); ++i) {
+            const int j = k - i;
+            if (j >= 0 && j < b_poly_len(qa)) acc = acc + b_poly(B, 1, pa, i) * b_poly(B, 2, qa, j);
+        }
+        for (int i = 0; i < b_poly_len(ra); ++i) {
+            const int j = k - i;
+            if (j >= 0 && j < b_poly_len(sa)) acc = acc - b_poly(B, 1, ra, i) * b_poly(B, 2, sa, j);
+        }
+        ws[WS_EET + 8 * which + k] = acc;
+    }
+    __syncthreads();
+    if (act && lane < 11) {
+        const int k = lane;
+        double acc = 0.0;
+        for (int i = 0; i < 4; ++i) { const int j = k - i; if (j >= 0 && j < 8) acc = acc + b_poly(B, 0, 0, i) * ws[WS_EET + j]; }
+        for (int i = 0; i < 4; ++i) { const int j = k - i; if (j >= 0 && j < 8) acc = acc - b_poly(B, 0, 1, i) * ws[WS_EET + 8 + j]; }
+        for (int i = 0; i < 5; ++i) { const int j = k - i; if (j >= 0 && j < 7) acc = acc + b_poly(B, 0, 2, i) * ws[WS_EET + 16 + j]; }
+        rec[REC_C + k] = acc;
+    }
+    __syncthreads();
+}
+
+// 4. cv::solvePoly on the trimmed polynomial, one hypothesis per lane: roots into the record, their number into s_nroot (0: the
+// elimination met a zero pivot). Ends with a barrier, which publishes both.
+__device__ __forceinline__ void solve_poly(const R5View &v, int H, int tid)
+{
+    for (int h = tid; h < H; h += R5_THREADS) {
+        double *rec = v.recs + (size_t)h * REC;
+        int nr = 0;
+        if (v.ok[h]) {
+            nr = 10;
+            while (nr > 1 && !(fabs(rec[REC_C + nr]) > DBL_EPSILON)) --nr;
+            double re[10], im[10];
+            durand_kerner(rec + REC_C, nr, re, im);
+#pragma unroll
+            for (int i = 0; i < 10; ++i) { rec[REC_RE + i] = re[i]; rec[REC_IM + i] = im[i]; }
+        }
+        v.nroot[h] = nr;
+    }
+    __syncthreads();
+}
+
+// 5. models_from_roots and their inlier counts over all m points, one (hypothesis, root) per lane, into s_good (-1: no model). Ends
+// with a barrier, which publishes s_good.
+__device__ __forceinline__ void score_models(const R5View &v, int H, int m, float thr2, int tid)
+{
+    for (int w = tid; w < H * 10; w += R5_THREADS) {
+        const int h = w / 10, r = w - 10 * h;
+        double E[9];
+        int g = -1;
+        if (model_of_root(v.recs + (size_t)h * REC, v.nroot[h], r, E)) {
+            g = 0;
+            for (int j = 0; j < m; ++j) g += sampson_inlier(E, v.px1[j], v.py1[j], v.px2[j], v.py2[j], thr2) ? 1 : 0;
+        }
+        v.good[w] = g;
+    }
+    __syncthreads();
+}
+
+// what the registrator loop leaves: bestInlierCount, the best model's hypothesis and root, the iterations made
+struct R5Best { int best, bh, br, iters; };
+
+// 6. registrator_runs: the loop of RANSACPointSetRegistrator::run (ptsetreg.hpp:176-199) replayed by thread 0 over the stored counts
+// (strict `>`, adaptive niters). Ends with a barrier, which publishes the outcome through s_misc[0..3]; every thread returns it.
+__device__ __forceinline__ R5Best registrator_runs(const R5View &v, int IT, int m, double prob, int tid)
+{
+    if (tid == 0) {
+        int best = 0, bh = -1, br = -1;
+        int niters = max(IT, 1), it = 0;
+        for (; it < niters; ++it)
+            for (int r = 0; r < 10; ++r) {
+                const int g = v.good[10 * it + r];
+                if (g >= 0 && g > max(best, 4)) {
+                    best = g; bh = it; br = r;
+                    niters = update_num_iters(prob, (double)(m - g) / (double)m, niters);
+                }
+            }
+        v.misc[0] = best; v.misc[1] = bh; v.misc[2] = br; v.misc[3] = it;
+    }
+    __syncthreads();
+    return R5Best{v.misc[0], v.misc[1], v.misc[2], v.misc[3]};
+}
+
+// The mask and E: every lane rebuilds the best model and classifies its points into s_st (0 inlier / 3 outlier, by tracked index);
+// without a model the pre-filled all-1 mask stays (doRansac5 :345). Thread 0 writes E (E_out may be NULL). One barrier, between the
+// fill of s_st and the scattered inlier writes. Ends WITHOUT one: s_st is published by the caller's next barrier.
+__device__ __forceinline__ void mask_and_E(const R5View &v, const R5Best &b, int n, int m, float thr2, double *E_out, int tid)
+{
+    double Eb[9];
+    const bool have = b.best > 0 && model_of_root(v.recs + (size_t)b.bh * REC, v.nroot[b.bh], b.br, Eb);
+    for (int k = tid; k < n; k += R5_THREADS) v.st[k] = 3;
+    __syncthreads();
+    for (int j = tid; j < m; j += R5_THREADS)
+        v.st[v.vmap[j]] = (!have || sampson_inlier(Eb, v.px1[j], v.py1[j], v.px2[j], v.py2[j], thr2)) ? 0 : 3;
+    if (tid == 0) {
+        double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (have) {
+            for (int i = 0; i < 9; ++i) E[i] = Eb[i];
+        } else if (m == 5) {                                       // count == modelPoints: the kernel's first model
+#pragma unroll 1                                                   // (a rare path on one lane: ten inlined copies of the model only grow the kernel)
+            for (int r = 0; r < 10; ++r)
+                if (model_of_root(v.recs, v.nroot[0], r, E)) break;
+                else for (int i = 0; i < 9; ++i) E[i] = 0.0;
+        }
+        if (E_out) for (int i = 0; i < 9; ++i) E_out[i] = E[i];
+    }
+}
+
+// The inlier count of the RANSAC5 result (ransac_pipeline.cpp:390-394), 0 when it did not run. Begins with a barrier (s_st complete),
+// a second one publishes the zeroed counter, the last one the sum.
+__device__ __forceinline__ int count_inliers(const R5View &v, bool run5, int n, int tid)
+{
+    __syncthreads();
+    if (tid == 0) v.misc[4] = 0;
     __syncthreads();
     if (run5) {
         int cnt = 0;
-        for (int k = tid; k < n; k += R5_THREADS) cnt += s_st[k] == 0;
-        if (cnt) atomicAdd(&s_misc[4], cnt);
+        for (int k = tid; k < n; k += R5_THREADS) cnt += v.st[k] == 0;
+        if (cnt) atomicAdd(&v.misc[4], cnt);
     }
     __syncthreads();
-    const int r5count = s_misc[4];
-    if (tid == 0 && a.summary) {
-        int *sm = a.summary + 4 * (size_t)set;
-        sm[0] = run5 ? r5count : 0; sm[1] = run5 ? bh : -1; sm[2] = run5 ? iters : 0; sm[3] = m;
-    }
-    if (!hybrid) {
-        int *st = a.status + (size_t)set * MP;
-        for (int k = tid; k < n; k += R5_THREADS) st[k] = s_st[k];
-        return;
-    }
-    // ---- hybrid selection (ransac_pipeline.cpp:158-195) and the status rewrite (:29-40, 139-144) ----
+    return v.misc[4];
+}
+
+// hybrid_select (ransac_pipeline.cpp:158-195) and the status rewrite (:29-40, 139-144). No barrier.
+__device__ __forceinline__ void hybrid_select(const R5Args &a, const R5View &v, int set, int *ts, int n_all, int n, int r2count,
+                                              int r5count, bool use_r2, bool run5, int tid)
+{
     bool r2_done = n >= 2, r5_done = run5;
     const double f5 = (double)r5count / (double)n, f2 = (double)r2count / (double)n;
     if (f5 < a.min_frac) r5_done = false;
@@ -619,10 +601,10 @@ __global__ __launch_bounds__(R5_THREADS) void ransac5_kernel(R5Args a)
     if (type == 0) {
         for (int i = tid; i < n_all; i += R5_THREADS) ts[i] = 3;
     } else {
-        const int *r2s = a.r2_status + (size_t)set * MP;
+        const int *r2s = a.r2_status + (size_t)set * a.max_points;
         for (int k = tid; k < n; k += R5_THREADS) {
-            const int src = s_map[k];
-            const bool inl = type == 1 ? r2s[src] == 0 : s_st[k] == 0;
+            const int src = v.map[k];
+            const bool inl = type == 1 ? r2s[src] == 0 : v.st[k] == 0;
             if (!inl) ts[src] = 3;
         }
     }
@@ -632,6 +614,71 @@ __global__ __launch_bounds__(R5_THREADS) void ransac5_kernel(R5Args a)
         a.score[set] = n ? (double)r2count / (double)n : 0.0;
     }
 }
+
+__global__ __launch_bounds__(R5_THREADS) void ransac5_kernel(R5Args a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char r5_lds[];
+    __shared__ hv_camera_model s_cam[2];
+    const int set = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int MP = a.max_points, IT = a.max_iters;
+    const R5View v = r5_view(r5_lds, ransac5_lds(MP, IT), wave, s_cam);
+    stage_cameras<R5_THREADS>(s_cam, a.cam1, a.cam2);
+    __syncthreads();                                            // publishes s_cam
+    const int n_all = min(max(a.n_points[set], 0), MP);
+    const float *c1 = a.c1 + (size_t)set * MP * 2, *c2 = a.c2 + (size_t)set * MP * 2;
+    const bool hybrid = a.track_status != nullptr;
+    int *ts = hybrid ? a.track_status + (size_t)set * MP : nullptr;
+
+    // 1. the set: TRACKED features in feature order (ransac_pipeline.cpp:106-112)
+    const int n = block_compact<R5_WAVES>([&](int i) { return !hybrid || ts[i] == 0; }, v.map, n_all, v.chunk);
+    // hybrid: RANSAC2's outcome and the skip rule (ransac_pipeline.cpp:165-167)
+    const int r2count = hybrid && n >= 2 ? a.r2_summary[2 * set] : 0;
+    const bool use_r2 = hybrid && (double)r2count > a.skip5 * (double)n;
+    const bool want5 = n >= 5 && !use_r2;
+    // Every condition below is uniform over the workgroup -- n, m, r2count and the parameters are the same in all of its threads --
+    // so the barriers inside the phases are met by every thread or by none.
+    int m = 0;
+    if (want5) m = normalise_set(v, c1, c2, n, tid);
+    const bool run5 = want5 && m >= 5;
+    const int H = m == 5 ? 1 : IT;
+    R5Best b{0, -1, -1, 0};
+    if (run5) {
+        draw_subsets(v, m, H, tid);                             // 2
+        const int rounds = (H + R5_WAVES - 1) / R5_WAVES;       // 3. the minimal solves, one hypothesis per wavefront
+        for (int rb = 0; rb < rounds; ++rb) {                   // (every wavefront makes every round: an idle one has act = false)
+            const int h = rb * R5_WAVES + wave;
+            const bool act = h < H;
+            double *rec = v.recs + (size_t)(act ? h : 0) * REC;
+            null_basis(v, rec, h, act, lane);                   // 3a
+            coeff_matrix(v, rec, act, lane);                    // 3b, 3c
+            eliminate(v, h, act, lane);                         // 3d
+            b_matrix(v, rec, act, lane);                        // 3e
+            det_poly(v, rec, act, lane);                        // 3f
+        }
+        solve_poly(v, H, tid);                                  // 4
+        if (m > 5) {                                            // m == 5 is count == modelPoints: no loop, the first model is taken
+            score_models(v, H, m, a.thr2, tid);                 // 5
+            b = registrator_runs(v, IT, m, a.prob, tid);        // 6
+        }
+        mask_and_E(v, b, n, m, a.thr2, a.E ? a.E + 9 * (size_t)set : nullptr, tid);
+    } else {
+        for (int k = tid; k < n; k += R5_THREADS) v.st[k] = 3;
+        if (tid == 0 && a.E)
+            for (int i = 0; i < 9; ++i) a.E[9 * (size_t)set + i] = 0.0;
+    }
+    const int r5count = count_inliers(v, run5, n, tid);
+    if (tid == 0 && a.summary) {
+        int *sm = a.summary + 4 * (size_t)set;
+        sm[0] = run5 ? r5count : 0; sm[1] = run5 ? b.bh : -1; sm[2] = run5 ? b.iters : 0; sm[3] = m;
+    }
+    if (!hybrid) {
+        int *st = a.status + (size_t)set * MP;
+        for (int k = tid; k < n; k += R5_THREADS) st[k] = v.st[k];
+        return;
+    }
+    hybrid_select(a, v, set, ts, n_all, n, r2count, r5count, use_r2, run5, tid);
+}
+
 
 // the host-side checks, made before the context is looked at: HV_ERR_INVALID for what OpenCV asserts on or what cannot be a set,
 // HV_ERR_UNSUPPORTED for what the kernel's LDS plan does not cover
@@ -655,7 +702,7 @@ void fill_common(R5Args &a, const hv_ransac5_params *p, int max_points, const hv
 
 int launch(Ctx *c, int n_sets, const R5Args &a)
 {
-    const size_t bytes = lds_bytes(a.max_points, a.max_iters);
+    const size_t bytes = ransac5_lds(a.max_points, a.max_iters).end;
     hipLaunchKernelGGL(ransac5_kernel, dim3((unsigned)n_sets), dim3(R5_THREADS), bytes, c->stream, a);
     HV_HIP(c, hipGetLastError());
     return HV_OK;
@@ -665,8 +712,7 @@ int launch(Ctx *c, int n_sets, const R5Args &a)
 
 int ransac5_init(Ctx *c)
 {
-    HV_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(ransac5_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_bytes(R5_MAX_PTS, R5_MAX_ITERS)));
+    HV_HIP(c, set_lds_limit(ransac5_kernel, ransac5_lds(R5_MAX_PTS, R5_MAX_ITERS).end));
     return HV_OK;
 }
 

@@ -50,12 +50,10 @@ struct RansacArgs {
     hv_camera_model cam1, cam2;
 };
 
-// ---- R = V U^T of H (reflection fixed): Kabsch through the Jacobi eigen-decomposition of H^T H, see the oracle header ----
-__device__ void cross3(const double *a, const double *b, double *c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
+#include "hv_geometry.hpp"    // cross3
+#include "hv_workgroup.hpp"   // block_compact
 
+// ---- R = V U^T of H (reflection fixed): Kabsch through the Jacobi eigen-decomposition of H^T H, see the oracle header ----
 template <int P, int Q>
 __device__ __forceinline__ void jacobi_step(double *A, double *V)
 {
@@ -175,35 +173,16 @@ __global__ __launch_bounds__(RT) void rot_ransac_kernel(RansacArgs a)
     const int n_all = min(max(a.n_points[set], 0), a.max_points);      // a device-supplied count never indexes past the set's arrays
     const float *c1 = a.c1 + (size_t)set * a.max_points * 2, *c2 = a.c2 + (size_t)set * a.max_points * 2;
     int *status = a.status + (size_t)set * a.max_points;
-    // ---- "Pick the left camera features for which track was found" (ransac_pipeline.cpp:106-112), in feature order:
-    // 64-feature chunks counted with a ballot, chunk offsets by a short serial scan ----
+    // ---- "Pick the left camera features for which track was found" (ransac_pipeline.cpp:106-112), in feature order; either way a
+    // barrier publishes s_map ----
     int n = n_all;
     if (a.lk_status) {
         const uint8_t *ls = a.lk_status + (size_t)set * a.max_points;
-        const int nchunk = (n_all + 63) / 64, wave = tid >> 6, lane = tid & 63;
-        for (int ch = wave; ch < nchunk; ch += RT / 64) {
-            const int i = ch * 64 + lane;
-            const unsigned long long m = __ballot(i < n_all && ls[i] == a.lk_tracked);
-            if (lane == 0) s_chunk[ch] = __popcll(m);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int acc = 0;
-            for (int ch = 0; ch < nchunk; ++ch) { const int cnt = s_chunk[ch]; s_chunk[ch] = acc; acc += cnt; }
-            s_chunk[nchunk] = acc;
-        }
-        __syncthreads();
-        n = s_chunk[nchunk];
-        for (int ch = wave; ch < nchunk; ch += RT / 64) {
-            const int i = ch * 64 + lane;
-            const bool on = i < n_all && ls[i] == a.lk_tracked;
-            const unsigned long long m = __ballot(on);
-            if (on) s_map[s_chunk[ch] + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)i;
-        }
+        n = block_compact<RT / 64>([&](int i) { return ls[i] == a.lk_tracked; }, s_map, n_all, s_chunk);
     } else {
         for (int i = tid; i < n_all; i += RT) s_map[i] = (unsigned short)i;
+        __syncthreads();
     }
-    __syncthreads();
     if (n < 2) {                                                             // ransac_pipeline.cpp:209: nothing to fit
         if (tid == 0 && k_lo == 0) { a.summary[2 * set] = 0; a.summary[2 * set + 1] = 0; }
         return;

@@ -49,7 +49,7 @@ struct TableArgs {
     int32_t *n_added;
 };
 
-__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+#include "hv_workgroup.hpp"   // clampi
 
 // computeDist2 (tracker.cpp:16-19): binary32 differences widened to binary64, two rounded products, one rounded sum
 __device__ inline double dist2(float2 a, float2 b)

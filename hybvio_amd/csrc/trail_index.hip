@@ -56,7 +56,7 @@ struct TrailArgs {
 
 struct TrailCameras { hv_camera_model cam0, cam1; };
 
-__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+#include "hv_workgroup.hpp"   // clampi, block_compact, stage_cameras
 
 // index of the [2] record of (row, column, camera) in the observation arrays, and of the `used` byte
 __device__ inline size_t obs_at(const TrailArgs &a, int set, int row, int col, int cam)
@@ -64,43 +64,6 @@ __device__ inline size_t obs_at(const TrailArgs &a, int set, int row, int col, i
     return ((((size_t)set * a.K + row) * a.M + col) * a.ncam + cam) * 2;
 }
 __device__ inline size_t used_at(const TrailArgs &a, int set, int row, int col) { return ((size_t)set * a.K + row) * a.M + col; }
-
-// The items i < count with pred(i), in order, into out[]; returns their number. s_chunk: TI_CHUNKS + 1 ints. Ends with a barrier.
-template <class Pred> __device__ inline int compact(Pred pred, int *out, int count, int *s_chunk)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nch = (count + 63) / 64;
-    for (int ch = wave; ch < nch; ch += TI_WAVES) {
-        const int i = ch * 64 + lane;
-        const unsigned long long m = __ballot(i < count && pred(i));
-        if (lane == 0) s_chunk[ch] = __popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        for (int ch = 0; ch < nch; ++ch) { const int c = s_chunk[ch]; s_chunk[ch] = acc; acc += c; }
-        s_chunk[nch] = acc;
-    }
-    __syncthreads();
-    const int total = s_chunk[nch];
-    for (int ch = wave; ch < nch; ch += TI_WAVES) {
-        const int i = ch * 64 + lane;
-        const bool on = i < count && pred(i);
-        const unsigned long long m = __ballot(on);
-        if (on) out[s_chunk[ch] + __popcll(m & ((1ull << lane) - 1ull))] = i;
-    }
-    __syncthreads();
-    return total;
-}
-
-// Camera::normalizePixel (camera.cpp:471-476) of a binary32 corner
-__device__ inline bool normalize_pixel(const hv_camera_model &c, float x, float y, double *out)
-{
-    double r[3];
-    if (!pixel_to_ray(c, (double)x, (double)y, r) || r[2] <= 0) return false;
-    out[0] = r[0] / r[2]; out[1] = r[1] / r[2];
-    return true;
-}
 
 __global__ __launch_bounds__(TI_THREADS) void trail_init_kernel(TrailArgs a)
 {
@@ -142,13 +105,7 @@ __global__ __launch_bounds__(TI_THREADS) void trail_select_kernel(TrailArgs a, T
 
     const int set = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int M = a.M, K = a.K, ncam = a.ncam;
-    {
-        static_assert(sizeof(hv_camera_model) % 4 == 0, "word copy");
-        constexpr int W = (int)(sizeof(hv_camera_model) / 4);
-        const int *src0 = reinterpret_cast<const int *>(&cams.cam0), *src1 = reinterpret_cast<const int *>(&cams.cam1);
-        int *dst = reinterpret_cast<int *>(s_cam);
-        for (int i = tid; i < 2 * W; i += TI_THREADS) dst[i] = i < W ? src0[i] : src1[i - W];
-    }
+    stage_cameras<TI_THREADS>(s_cam, cams.cam0, cams.cam1);     // published by the barrier behind the s_row fill below
     const int n = clampi(a.n_tracks[set], 0, M);
     const int n_kf_in = clampi(a.t.n_keyframes[set], 1, K);
     const int n_prev = a.blacklist ? clampi(a.t.n_blacklist[set], 0, M) : 0;
@@ -191,8 +148,8 @@ __global__ __launch_bounds__(TI_THREADS) void trail_select_kernel(TrailArgs a, T
         if (c >= 0) s_hit[c] = i;
     }
     __syncthreads();
-    const int n_free = compact([&](int c) { return s_hit[c] < 0; }, s_free, M, s_chunk);
-    const int n_new = compact([&](int i) { return s_col[i] < 0; }, s_list, n, s_chunk);
+    const int n_free = block_compact<TI_WAVES>([&](int c) { return s_hit[c] < 0; }, s_free, M, s_chunk);
+    const int n_new = block_compact<TI_WAVES>([&](int i) { return s_col[i] < 0; }, s_list, n, s_chunk);
     for (int k = tid; k < n_new && k < n_free; k += TI_THREADS) s_col[s_list[k]] = s_free[k];   // n_new <= n_free: a slot has one column
     for (int c = tid; c < M; c += TI_THREADS) s_len[c] = 0;     // prune (:220-242): a column that is not inserted below is free
     __syncthreads();
@@ -274,7 +231,7 @@ __global__ __launch_bounds__(TI_THREADS) void trail_select_kernel(TrailArgs a, T
     }
 
     // ---- trackOrder, the draws, minTrackScore (backend.cpp:976-992) ----
-    const int n_ord = compact([&](int i) { return s_old[i] >= 0; }, s_list, n, s_chunk);
+    const int n_ord = block_compact<TI_WAVES>([&](int i) { return s_old[i] >= 0; }, s_list, n, s_chunk);
     // step k of the shuffle is i = n - 1 - k, so every draw % (i + 1) is known before the chain starts
     for (int k = tid; k < n_ord - 1; k += TI_THREADS) s_free[k] = (int)(a.draws[(size_t)set * M + k] % (unsigned)(n_ord - k));
     for (int p = tid; p < n_ord; p += TI_THREADS) s_state[p] = (int)s_score[s_list[p]];   // static_cast<int> (backend.cpp:988)
@@ -320,8 +277,8 @@ __global__ __launch_bounds__(TI_THREADS) void trail_select_kernel(TrailArgs a, T
         s_state[p] = st;
     }
     __syncthreads();
-    const int n_skip = compact([&](int p) { return s_state[p] == 1; }, s_hit, n_ord, s_chunk);
-    const int n_pass = compact([&](int p) { return s_state[p] == 2; }, s_free, n_ord, s_chunk);
+    const int n_skip = block_compact<TI_WAVES>([&](int p) { return s_state[p] == 1; }, s_hit, n_ord, s_chunk);
+    const int n_pass = block_compact<TI_WAVES>([&](int p) { return s_state[p] == 2; }, s_free, n_ord, s_chunk);
     const int n_cand = min(n_pass, a.V);
     for (int k = tid; k < n_skip; k += TI_THREADS) {
         a.t.skipped_pos[(size_t)set * M + k] = s_hit[k];

@@ -1,10 +1,12 @@
 // Stand-alone test of hybvio_amd/csrc/lds_layout.hpp (plain g++ -std=c++17, no HIP): the stride rule, and for every layout that the
 // regions are in order and disjoint, aligned where the kernels need it, add up to the total, hold every record a launch may carry and
 // stay within the kernel's dynamic-LDS limit; then the byte counts of known shapes, worked out by hand from the launchers' formulas.
+// Likewise ransac_lds.hpp, the layouts of the two RANSAC kernels.
 // Run by tests/test_lds_layout.py.
 #include <cstdio>
 #include <initializer_list>
 #include "../../hybvio_amd/csrc/lds_layout.hpp"
+#include "../../hybvio_amd/csrc/ransac_lds.hpp"
 
 using namespace hv;
 
@@ -119,6 +121,42 @@ static void test_augment(int n)
     CHECK(lds_bytes(L) <= LDS_AUGMENT_LIMIT, "n %d: %zu bytes", n, lds_bytes(L));
 }
 
+// The RANSAC kernels' layouts (ransac_lds.hpp, byte offsets): the sections ascend and do not overlap, the double sections are 8-byte
+// aligned (the int sections 4-byte), and the total is the closed form that ransac5.hip / ransac3.hip carried before the layouts.
+struct Section { const char *name; size_t at, bytes; };
+template <size_t N> static void check_sections(const char *what, const Section (&s)[N], size_t n_doubles, size_t end, int mp, int it)
+{
+    for (size_t i = 0; i < N; i++) {
+        CHECK(s[i].at % (i < n_doubles ? 8 : 4) == 0, "%s mp %d it %d: %s at %zu", what, mp, it, s[i].name, s[i].at);
+        const size_t next = i + 1 < N ? s[i + 1].at : end;
+        CHECK(s[i].bytes > 0 && s[i].at + s[i].bytes == next, "%s mp %d it %d: %s [%zu, +%zu) then %zu", what, mp, it, s[i].name, s[i].at, s[i].bytes, next);
+    }
+    CHECK(s[0].at == 0, "%s mp %d it %d", what, mp, it);
+}
+
+static void test_ransac(int mp, int it)
+{
+    const size_t m = (size_t)mp, t = (size_t)it, chunk = 4 * ((m + 63) / 64 + 1);
+    const Ransac5Lds L = ransac5_lds(mp, it);
+    const Section s5[] = {{"px1", L.px1, 8 * m}, {"py1", L.py1, 8 * m}, {"px2", L.px2, 8 * m}, {"py2", L.py2, 8 * m},
+                          {"recs", L.recs, 8 * t * 106}, {"ws", L.ws, 8 * 4 * 290},
+                          {"good", L.good, 4 * t * 10}, {"sub", L.sub, 4 * t * 5}, {"nroot", L.nroot, 4 * t}, {"ok", L.ok, 4 * t},
+                          {"map", L.map, 4 * m}, {"vmap", L.vmap, 4 * m}, {"st", L.st, 4 * m}, {"chunk", L.chunk, chunk}, {"misc", L.misc, 4 * 16}};
+    check_sections("ransac5", s5, 6, L.end, mp, it);
+    CHECK(L.end == 8 * (4 * m + t * 106 + 4 * 290) + 4 * (t * 17 + 3 * m + (m + 63) / 64 + 1 + 16), "ransac5 mp %d it %d: %zu", mp, it, L.end);
+    CHECK(REC == 106 && WS == 290 && R5_WAVES == 4 && REC_EE + 36 == REC_B && REC_B + 39 == REC_C && REC_C + 11 == REC_RE && REC_RE + 10 == REC_IM &&
+          REC_IM + 10 == REC && WS_EET + 90 == WS_A && WS_A + 200 == WS, "ransac5 record and scratch");
+    if (it != 1) return;                                           // (ransac3's layout does not depend on the iteration count)
+    const Ransac3Lds K = ransac3_lds(mp);
+    const Section s3[] = {{"wx", K.wx, 8 * m}, {"wy", K.wy, 8 * m}, {"wz", K.wz, 8 * m}, {"fu", K.fu, 8 * m}, {"fv", K.fv, 8 * m},
+                          {"mod", K.mod, 8 * 256 * 12}, {"cost", K.cost, 8 * 256}, {"best", K.best, 8 * 12},
+                          {"map", K.map, 4 * m}, {"vmap", K.vmap, 4 * m}, {"st", K.st, 4 * m}, {"idx", K.idx, 4 * m}, {"chunk", K.chunk, chunk},
+                          {"tri", K.tri, 4 * 3 * 64}, {"draw", K.draw, 4 * 3 * 64}, {"cnt", K.cnt, 4 * 256}, {"ctl", K.ctl, 4 * 16}};
+    check_sections("ransac3", s3, 8, K.end, mp, 0);
+    CHECK(K.end == 8 * (5 * m + 256 * 12 + 256 + 12) + 4 * (4 * m + (m + 63) / 64 + 1 + 3 * 64 * 2 + 256 + 16), "ransac3 mp %d: %zu", mp, K.end);
+    CHECK(R3_THREADS == 256 && R3_CHUNK == 64, "ransac3 constants");
+}
+
 // byte counts and decisions of known shapes, worked out by hand from the launchers' formulas as they stood before the layouts
 static void test_pinned()
 {
@@ -158,6 +196,10 @@ int main()
     }
     for (int ncam = 1; ncam <= 2; ncam++)
         for (int np = 2; np <= 21; np++) test_sparse_gate(np, ncam);
+    for (int mp : {1, 5, 63, 64, 65, 1024})
+        for (int it : {1, 4, 5, 75}) test_ransac(mp, it);
+    // the largest shapes (1024 points; 75 iterations, HV_RANSAC5_MAX_ITERS) beside the kernels' static LDS (two camera models, T)
+    CHECK(ransac5_lds(1024, 75).end + 2048 <= LDS_CU_BYTES && ransac3_lds(1024).end + 2048 <= LDS_CU_BYTES, "the largest RANSAC shapes fit a CU");
     test_pinned();
     if (failures) { std::printf("%d checks failed\n", failures); return 1; }
     std::printf("all lds layout tests passed\n");

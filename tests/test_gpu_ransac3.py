@@ -297,3 +297,53 @@ def test_profile_class_counts_the_launches(oracle):
         ms, n = ctx.profile_read(capi.K_RANSAC3)
         assert n == 3 and ms > 0
         assert ctx.profile_read(capi.K_RANSAC5)[1] == 0 and ctx.profile_read(capi.K_ROT_RANSAC)[1] == 0
+
+
+EDGE_COUNTS = [0, 1, 4, 5, 6, 63, 64, 65, 128, 129, 769, 1023, 1024]
+
+
+def test_compaction_and_gather_at_the_chunk_edges(oracle):
+    """The ordered compaction (TRACKED features, then correspondences) and the gather behind it at their edges: one launch of
+    hv_ransac3_lk_batch_dev with max_points = 1024, point counts around the 64-feature chunks and the 256-thread strides, and
+    per count three masks: all TRACKED, every second feature, feature 0 and the last feature of every 64-feature chunk.
+    Noise-free sets with 20 % outliers; counts from 63 up carry features whose triangulation is rejected, so the gather moves
+    the correspondences behind them. Every set must equal the restatement's compute, none exempted."""
+    import torch
+    ocam, gcam = _cams(oracle, "pinhole_radial")
+    rng = np.random.default_rng(78)
+    MP = 1024
+    sets = []
+    for k, n in enumerate(EDGE_COUNTS):
+        extra = 6 if n >= 63 else 0
+        base = R.make_set(rng, ocam, n - extra, 0.2, 0.0, 0, extra, 0)
+        i = np.arange(n)
+        for j, mask in enumerate([np.ones(n, bool), i % 2 == 0, (i % 64 == 63) | (i == 0)]):
+            d = dict(base, n=n, status=np.where(mask, 0, 2).astype(np.int32), draws=oracle.mt19937_draws(7000 + 3 * k + j, 3 * R.MAX_ITERS))
+            d["r2count"] = int(mask.sum()) // 2
+            sets.append(d)
+    S = len(sets)
+    xy, st, cnt, draws = _pack(sets, MP)
+    r2s = np.zeros((S, 2), np.int32); r2s[:, 0] = [d["r2count"] for d in sets]
+    with capi.Context(width=752, height=480) as ctx:
+        d_xy, d_st, d_n, d_dr, d_r2s = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (xy, st, cnt, draws, r2s))
+        d_res = torch.full((S, 2), -1, dtype=torch.int32, device="cuda"); d_score = torch.full((S,), -1.0, dtype=torch.float64, device="cuda")
+        d_pose = torch.full((S, 12), 7.0, dtype=torch.float64, device="cuda"); d_sm = torch.full((S, 4), -5, dtype=torch.int32, device="cuda")
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        ctx.ransac3_lk_batch_dev(S, MP, d_n.data_ptr(), d_xy[0].data_ptr(), d_xy[1].data_ptr(), d_xy[2].data_ptr(), d_st.data_ptr(),
+                                 d_r2s.data_ptr(), gcam, gcam, T, d_dr.data_ptr(), d_res.data_ptr(), d_score.data_ptr(), d_pose.data_ptr(),
+                                 d_sm.data_ptr())
+        torch.cuda.synchronize()
+        g_st, g_res, g_score, g_pose, g_sm = (t.cpu().numpy() for t in (d_st, d_res, d_score, d_pose, d_sm))
+    types, moved = [], 0
+    for s, d in enumerate(sets):
+        n = d["n"]
+        want_ts, typ, count, score, summ = R.compute(d["status"], d["prev_left"], d["prev_right"], d["cur_left"], ocam, ocam, T, d["draws"], d["r2count"])
+        pose = R.do_ransac3(d["status"], d["prev_left"], d["prev_right"], d["cur_left"], ocam, ocam, T, d["draws"])[3]
+        print("set", s, "n", n, "tracked", int((d["status"] == 0).sum()), "type", typ, "count", count, "summary", list(summ), "gpu", g_res[s], g_sm[s])
+        assert np.array_equal(g_st[s, :n], want_ts) and (g_st[s, n:] == -9).all(), (s, n)
+        assert g_res[s].tolist() == [typ, count] and g_score[s] == score and g_sm[s].tolist() == list(summ), (s, n, g_res[s], g_sm[s], typ, count, summ)
+        assert np.abs(g_pose[s] - pose).max() <= 1e-9, (s, n)
+        types.append(typ)
+        moved += 3 <= summ[3] < int((d["status"] == 0).sum())
+    assert {R.TYPE_R3, R.TYPE_SKIPPED} <= set(types), types                     # (by the restatement: both outcomes are reached,
+    assert moved >= 10                                                         # and sets where correspondences < TRACKED features)

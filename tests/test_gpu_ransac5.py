@@ -244,3 +244,68 @@ def test_profile_class_counts_the_launches(oracle):
         assert n == 3 and ms > 0
         ms2, n2 = ctx.profile_read(capi.K_ROT_RANSAC)
         assert n2 == 0
+
+
+EDGE_COUNTS = [0, 1, 4, 5, 6, 63, 64, 65, 128, 129, 769, 1023, 1024]
+
+
+def _edge_masks(n):
+    """All TRACKED; every second feature; feature 0 and the last feature of every 64-feature chunk."""
+    i = np.arange(n)
+    return [np.ones(n, bool), i % 2 == 0, (i % 64 == 63) | (i == 0)]
+
+
+def test_compaction_and_gather_at_the_chunk_edges(oracle):
+    """The ordered compaction (TRACKED features, then valid points) and the gather behind it at their edges: one launch of the
+    hybrid entry with max_points = 1024, point counts around the 64-feature chunks and the 256-thread strides, three
+    track-status masks per count. Noise-free general scenes with 20 % outliers, so the inlier counts are far from a tie and
+    pow / log of the iteration update cannot fork: every set must equal the restatement (statuses, type, count, score,
+    summary; E as in the well-separated test), none exempted. Counts from 63 up carry features whose second corner is outside
+    the fisheye's valid field of view: normalizePixel fails there and the gather moves the points behind them."""
+    import torch
+    ocam, gcam, f, spec = _cams(oracle, "fisheye")
+    rng = np.random.default_rng(77)
+    MP = 1024
+    sets = []
+    for n in EDGE_COUNTS:
+        c1, c2 = (R.make_set(rng, (ocam, spec), n, 0.2, 0.0)[:2]) if n else (np.zeros((0, 2), np.float32),) * 2
+        if n >= 63:
+            c2 = c2.copy()
+            c2[[i for i in (2, 63, 2 * (n // 4)) if i < n]] = (-150.0, -120.0)
+        for mask in _edge_masks(n):
+            sel = np.nonzero(mask)[0]
+            r2 = np.full(n, 3, np.int32)
+            r2[sel[::2]] = 0                                                   # RANSAC2 "found" every second tracked feature
+            sets.append(dict(n=n, c1=c1, c2=c2, sel=sel, ts=np.where(mask, 0, 2).astype(np.int32), r2=r2,
+                             r2count=len(sel[::2]) if len(sel) >= 2 else 0))    # doRansac2 does not run below two tracks
+    S = len(sets)
+    c1 = np.zeros((S, MP, 2), np.float32); c2 = np.zeros((S, MP, 2), np.float32)
+    ts = np.full((S, MP), -9, np.int32); r2 = np.full((S, MP), -7, np.int32)
+    cnt = np.array([d["n"] for d in sets], np.int32); r2s = np.zeros((S, 2), np.int32)
+    for s, d in enumerate(sets):
+        n = d["n"]
+        c1[s, :n], c2[s, :n], ts[s, :n], r2[s, :n], r2s[s, 0] = d["c1"], d["c2"], d["ts"], d["r2"], d["r2count"]
+    with capi.Context(width=752, height=480) as ctx:
+        d_c1, d_c2, d_ts, d_r2, d_n, d_r2s = (torch.from_numpy(x).cuda() for x in (c1, c2, ts, r2, cnt, r2s))
+        d_res = torch.full((S, 2), -1, dtype=torch.int32, device="cuda"); d_score = torch.full((S,), -1.0, dtype=torch.float64, device="cuda")
+        d_E = torch.full((S, 9), 7.0, dtype=torch.float64, device="cuda"); d_sm = torch.full((S, 4), -5, dtype=torch.int32, device="cuda")
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        ctx.hybrid_ransac_lk_batch_dev(S, MP, d_n.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(), d_ts.data_ptr(), d_r2.data_ptr(),
+                                       d_r2s.data_ptr(), gcam, gcam, d_res.data_ptr(), d_score.data_ptr(), d_E.data_ptr(), d_sm.data_ptr())
+        torch.cuda.synchronize()
+        g_ts, g_res, g_score, g_E, g_sm = (t.cpu().numpy() for t in (d_ts, d_res, d_score, d_E, d_sm))
+    norm = [R.normalize(d["c1"][d["sel"]], d["c2"][d["sel"]], ocam, ocam) for d in sets]
+    runs = R.registrator_runs([(h1, h2, R.threshold(f, f)) for h1, h2, _ in norm])
+    types, moved = [], 0
+    for s, d in enumerate(sets):
+        n, sel = d["n"], d["sel"]
+        want_ts, typ, count, score = R.hybrid_pipeline(d["ts"], d["c1"], d["c2"], d["r2"], d["r2count"], ocam, ocam, f, f, run=runs[s])
+        done, _, E_r, sm_r, _ = R.do_ransac5(d["c1"][sel], d["c2"][sel], ocam, ocam, f, f, run=runs[s])
+        print("set", s, "n", n, "tracked", len(sel), "type", typ, "count", count, "summary", sm_r, "gpu", g_res[s], g_sm[s])
+        assert np.array_equal(g_ts[s, :n], want_ts) and (g_ts[s, n:] == -9).all(), (s, n)
+        assert g_res[s].tolist() == [typ, count] and g_score[s] == score and g_sm[s].tolist() == list(sm_r), (s, n, g_res[s], g_sm[s], typ, count, sm_r)
+        assert (_e_dist(g_E[s], E_r) <= 1e-7) if E_r.any() else not g_E[s].any(), (s, n)
+        types.append(typ)
+        moved += 5 <= sm_r[3] < len(sel)
+    assert {R.TYPE_SKIPPED, R.TYPE_R2, R.TYPE_R5} <= set(types), types          # (by the restatement: the batch reaches every outcome,
+    assert moved >= 10                                                         # and sets where valid points < TRACKED features)

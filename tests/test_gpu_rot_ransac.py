@@ -205,3 +205,47 @@ def test_lk_output_feeds_ransac_on_the_device(oracle):
         st_o, R_o, best_o, used_o = oracle.rot_ransac_fit(pts[s][keep], nxt[s][keep], ocam, ocam, draws[s], thr)
         assert np.array_equal(st[s][keep], st_o) and (st[s][ost == 0] == -7).all()
         assert summ[s].tolist() == [best_o, used_o // 2] and np.array_equal(R[s].view(np.uint32), R_o.reshape(-1).view(np.uint32))
+
+
+@pytest.mark.parametrize("threads", [0, 256])               # 21 sets: auto = 1024 threads (16 wavefronts compact), 256 = 4 wavefronts
+def test_lk_status_compaction_at_the_chunk_edges(oracle, threads):
+    """The ordered compaction of the LK-status entry at its edges: point counts around the 64-feature chunks and per count three
+    masks: all tracked, every second feature, feature 0 and the last feature of every chunk. Statuses (at the original feature
+    numbers), R and the summary must be bit-equal to the oracle on the compacted set; everything else stays untouched."""
+    import torch
+    ocam, gcam = _cams(oracle, "pinhole")
+    rng = np.random.default_rng(31)
+    M, sets = 192, []
+    for k, n in enumerate([0, 1, 2, 63, 64, 65, 129]):
+        c1, c2 = _scene(ocam, rng, n, n // 5) if n else (np.zeros((0, 2), np.float32),) * 2
+        i = np.arange(n)
+        for j, mask in enumerate([np.ones(n, bool), i % 2 == 0, (i % 64 == 63) | (i == 0)]):
+            sets.append(dict(n=n, c1=c1, c2=c2, keep=np.nonzero(mask)[0], draws=oracle.mt19937_draws(4649 + 3 * k + j, 200)))
+    S = len(sets)
+    c1 = np.zeros((S, M, 2), np.float32); c2 = np.zeros((S, M, 2), np.float32); lk = np.zeros((S, M), np.uint8)
+    for s, d in enumerate(sets):
+        c1[s, :d["n"]], c2[s, :d["n"]] = d["c1"], d["c2"]
+        lk[s, d["keep"]] = 1
+    lk[:, 150:] = 1                                          # "tracked" entries beyond every set's count must not be picked up
+    with capi.Context(width=752, height=480) as ctx:
+        dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        d_n, d_c1, d_c2, d_lk = dev(np.array([d["n"] for d in sets], np.int32)), dev(c1), dev(c2), dev(lk)
+        d_draws = dev(np.stack([d["draws"] for d in sets]).astype(np.uint32))
+        st = torch.full((S, M), -7, dtype=torch.int32, device="cuda")
+        R = torch.full((S, 9), 7.0, dtype=torch.float32, device="cuda"); summ = torch.full((S, 2), -1, dtype=torch.int32, device="cuda")
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        ctx.set_knob("rot_ransac_threads", threads)
+        ctx.rot_ransac_lk_batch_dev(S, M, d_n.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(), d_lk.data_ptr(), 1, gcam, gcam,
+                                    d_draws.data_ptr(), THR, st.data_ptr(), R.data_ptr(), summ.data_ptr())
+        torch.cuda.synchronize()
+        st, R, summ = st.cpu().numpy(), R.cpu().numpy(), summ.cpu().numpy()
+    for s, d in enumerate(sets):
+        keep = d["keep"]
+        rest = np.ones(M, bool); rest[keep] = False
+        assert (st[s][rest] == -7).all(), s                  # untracked features and the padding
+        if len(keep) < 2:                                    # ransac_pipeline.cpp:209: nothing to fit
+            assert summ[s].tolist() == [0, 0] and (st[s] == -7).all() and (R[s] == 7.0).all(), s
+            continue
+        st_o, R_o, best_o, used_o = oracle.rot_ransac_fit(d["c1"][keep], d["c2"][keep], ocam, ocam, d["draws"], THR)
+        assert np.array_equal(st[s][keep], st_o) and summ[s].tolist() == [best_o, used_o // 2], (s, d["n"], len(keep))
+        assert np.array_equal(R[s].view(np.uint32), R_o.reshape(-1).view(np.uint32)), (s, d["n"], len(keep))
