@@ -136,6 +136,20 @@ class EkfControlTable(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("zupt_time", "init_zupt_time", "was_stationary", "frames_since_keyframe")]
 
 
+class SessionParams(C.Structure):
+    _fields_ = [("targetFps", C.c_double), ("visualUpdateForEveryNFrame", C.c_int), ("goodFramesTimeWindowSeconds", C.c_double),
+                ("goodFramesToTracking", C.c_double), ("goodFramesToTrackingFailed", C.c_double), ("resetUntilInitSucceeds", C.c_int),
+                ("resetOnFailedTracking", C.c_int), ("resetAfterTrackingFailsToInitialize", C.c_double),
+                ("freezeOnFailedTracking", C.c_int)]
+
+
+class SessionState(C.Structure):
+    """hv_session: device pointers owned by the caller."""
+    _fields_ = [(k, C.c_void_p) for k in ("good_ring", "ring_head", "ring_entries", "tracking_status", "control_status",
+                                          "last_reset_time", "first_sample", "first_sample_t", "prev_sample_t", "time",
+                                          "initialized_orientation")]
+
+
 class HvError(RuntimeError):
     pass
 
@@ -278,6 +292,13 @@ PROTOTYPES = {
     "hv_flow_predict_default_params": (None, [C.POINTER(FlowPredictParams)]),
     "hv_flow_predict_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(FlowPredictParams), C.c_int, C.POINTER(TrailIndexParams),
                                             C.POINTER(TrailIndexTable), C.POINTER(TrackTable)] + [C.c_void_p] * 5 + [C.c_int]),
+    "hv_session_default_params": (None, [C.POINTER(SessionParams)]),
+    "hv_session_init_dev": (C.c_int, [C.c_void_p, C.POINTER(SessionParams), C.POINTER(SessionState)]),
+    "hv_session_imu_dev": (C.c_int, [C.c_void_p, C.POINTER(SessionState), C.c_int] + [C.c_void_p] * 5),
+    "hv_session_status_dev": (C.c_int, [C.c_void_p, C.POINTER(SessionParams), C.POINTER(SessionState)] + [C.c_void_p] * 5),
+    "hv_session_reset_dev": (C.c_int, [C.c_void_p, C.POINTER(SessionParams), C.POINTER(SessionState), C.POINTER(EkfControlTable),
+                                       C.POINTER(TrackTableParams), C.POINTER(TrackTable), C.POINTER(TrailIndexParams),
+                                       C.POINTER(TrailIndexTable), C.c_void_p]),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -907,6 +928,38 @@ class EkfControl:
         self.table = EkfControlTable(*(getattr(self, k).data_ptr() for k, _ in EkfControlTable._fields_))
 
 
+def session_default_params(**over) -> SessionParams:
+    p = SessionParams()
+    lib().hv_session_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def session_window(params: SessionParams) -> int:
+    """The ring size W of hv_session (backend.cpp:195-197)."""
+    return int(float(params.targetFps) / float(params.visualUpdateForEveryNFrame) * params.goodFramesTimeWindowSeconds)
+
+
+class Session:
+    """hv_session for n_sets sequences with a ring of W flags: torch tensors on `device` by member name (self.m) and the pointer
+    table over them (self.table). Uninitialised until session_init_dev."""
+
+    def __init__(self, n_sets: int, W: int, device="cuda"):
+        S, i32, f64, u8 = n_sets, torch.int32, torch.float64, torch.uint8
+        shapes = dict(good_ring=((S, W), torch.float32), ring_head=((S,), i32), ring_entries=((S,), i32), tracking_status=((S,), i32),
+                      control_status=((S,), i32), last_reset_time=((S,), f64), first_sample=((S,), u8), first_sample_t=((S,), f64),
+                      prev_sample_t=((S,), f64), time=((S,), f64), initialized_orientation=((S,), u8))
+        self.n_sets, self.W = n_sets, W
+        self.m = {k: torch.zeros(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
+        self.table = SessionState(*(self.m[k].data_ptr() for k, _ in SessionState._fields_))
+
+
+def session_state(n_sets: int, W: int, device="cuda") -> Session:
+    """Allocates an hv_session (the allocator beside track_table and TrailIndex)."""
+    return Session(n_sets, W, device)
+
+
 def _f(a):
     return np.ascontiguousarray(a, np.float64)
 
@@ -1242,6 +1295,28 @@ class EkfBatch:
         """hv_ekf_frame_control_dev: the frame's keyframe counter, visual-stationarity ZUPT and undo mask."""
         a = [C.c_void_p(x) for x in (time_dev, keyframe_dev, full_update_dev, keyframe_out_dev, undo_active_dev, stationary_dev, applied_dev)]
         self._chk(lib().hv_ekf_frame_control_dev(self._h, C.byref(params), C.byref(ctl.table), *a), "hv_ekf_frame_control_dev")
+
+    def session_init_dev(self, params: "SessionParams", st: "Session"):
+        """hv_session_init_dev: a Control and its first Session; the filter is not touched."""
+        self._chk(lib().hv_session_init_dev(self._h, C.byref(params), C.byref(st.table)), "hv_session_init_dev")
+
+    def session_imu_dev(self, st: "Session", n_samples, t_dev, acc_dev, dt_dev, time_dev, active_dev=0):
+        """hv_session_imu_dev: orientation on the first sample and the sample clock; t_dev, dt_dev, time_dev [n][batch], acc_dev [n][batch][3]."""
+        a = [C.c_void_p(x) for x in (t_dev, acc_dev, active_dev, dt_dev, time_dev)]
+        self._chk(lib().hv_session_imu_dev(self._h, C.byref(st.table), int(n_samples), *a), "hv_session_imu_dev")
+
+    def session_status_dev(self, params: "SessionParams", st: "Session", good_frame_dev, reset_kind_dev, full_update_dev=0, status_dev=0,
+                           frozen_dev=0):
+        """hv_session_status_dev: the good-frame ring, the tracking status and the reset decision of a frame."""
+        a = [C.c_void_p(x) for x in (good_frame_dev, full_update_dev, status_dev, frozen_dev, reset_kind_dev)]
+        self._chk(lib().hv_session_status_dev(self._h, C.byref(params), C.byref(st.table), *a), "hv_session_status_dev")
+
+    def session_reset_dev(self, params: "SessionParams", st: "Session", ctl: "EkfControl", tracks_params: "TrackTableParams",
+                          table: "TrackTable", trail_params: "TrailIndexParams", trail: "TrailIndexTable", reset_kind_dev):
+        """hv_session_reset_dev: Control::reset in place for the sets whose reset kind is 1 (fresh) or 2 (keep the pose)."""
+        self._chk(lib().hv_session_reset_dev(self._h, C.byref(params), C.byref(st.table), C.byref(ctl.table), C.byref(tracks_params),
+                                             C.byref(table), C.byref(trail_params), C.byref(trail), C.c_void_p(reset_kind_dev)),
+                  "hv_session_reset_dev")
 
     def flow_predict_batch_dev(self, params: "FlowPredictParams", kind: int, trail_params: "TrailIndexParams", trail: "TrailIndexTable",
                                table: "TrackTable", c0_dev, cam0: "CameraModel", cam1: "CameraModel", pred_xy_dev, distance_dev=0,

@@ -15,7 +15,8 @@
 //   ekf_augment.hip   pose augmentation, undo, symmetrise, normalise, transform, map points and their hv_ekf_* entries
 //   ekf.hip           (this file) what launches no kernel of its own: parameters, create / destroy, state accessors, the
 //                     host-pointer update entries (through ekf_launch_update), the families' LDS limits, the phase-stamp entry
-// ekf_visit.hip (track visits, frame loops) and ekf_control.hip (ZUPT, pseudo-velocity, block updates) sit on top of these.
+// ekf_visit.hip (track visits, frame loops), ekf_control.hip (ZUPT, pseudo-velocity, block updates) and session.hip (sample clock,
+// tracking status, resets in place) sit on top of these.
 #include <new>
 
 #include "ekf_device.hpp"
@@ -82,27 +83,12 @@ int hv_ekf_create(hv_ctx *ctx, const hv_ekf_params *par, int batch, hv_ekf **out
     if (!ok) { hv_ekf_destroy(h); return HV_ERR_NOMEM; }
 
     // initial state and covariance: EKFImplementation ctor, ekf.cpp:153-296
+    // (dydx is zero until the first predict writes it: a reset filter and a new one are then equal in every array)
     std::vector<double> m0(n, 0.0), P0(nn, 0.0), Q0(144, 0.0);
-    auto sq = [](double x) { return x * x; };
-    m0[hv::ORI] = 1.0; m0[hv::BAT] = m0[hv::BAT + 1] = m0[hv::BAT + 2] = 1.0;
-    for (int i = 0; i < 3; i++) {
-        P0[(size_t)(hv::POS + i) * n + hv::POS + i] = sq(par->noiseInitialPos);
-        P0[(size_t)(hv::VEL + i) * n + hv::VEL + i] = sq(par->noiseInitialVel);
-        P0[(size_t)(hv::BGA + i) * n + hv::BGA + i] = sq(par->noiseInitialBGA);
-        P0[(size_t)(hv::BAA + i) * n + hv::BAA + i] = sq(par->noiseInitialBAA);
-        P0[(size_t)(hv::BAT + i) * n + hv::BAT + i] = sq(par->noiseInitialBAT);
-    }
-    for (int i = 0; i < 4; i++) P0[(size_t)(hv::ORI + i) * n + hv::ORI + i] = 1.0;
-    P0[(size_t)hv::SFT * n + hv::SFT] = sq(par->noiseInitialSFT);
-    for (int cidx = 0; cidx < e->cam; cidx++) {
-        const int b0 = hv::CAM + cidx * hv::POSE;
-        for (int i = 0; i < 3; i++) P0[(size_t)(b0 + i) * n + b0 + i] = sq(par->noiseInitialPosTrail);
-        for (int i = 3; i < 7; i++) P0[(size_t)(b0 + i) * n + b0 + i] = sq(par->noiseInitialOriTrail);
-    }
-    for (int i = 0; i < 3; i++) { Q0[(hv::Q_ACC + i) * 13] = sq(par->noiseProcessAcc); Q0[(hv::Q_GYRO + i) * 13] = sq(par->noiseProcessGyro); }
-    for (auto &x : P0) x *= e->noise_scale;
-    for (auto &x : Q0) x *= e->noise_scale;
-    int rc = HV_OK;
+    const hv::EkfFresh fresh = hv::ekf_fresh(*par, n, e->noise_scale);
+    for (int i = 0; i < n; i++) { m0[i] = fresh.mean(i); P0[(size_t)i * n + i] = fresh.p_diag(i); }
+    for (int i = 0; i < hv::QD; i++) Q0[i * (hv::QD + 1)] = fresh.q_diag(i);
+    int rc = hipMemset(e->fixed.dydx, 0, sizeof(double) * 400 * batch) == hipSuccess ? HV_OK : HV_ERR_HIP;
     for (int b = 0; b < batch && rc == HV_OK; b++) {
         rc = hv_ekf_set_state(h, b, m0.data(), P0.data());
         if (rc == HV_OK) rc = hv_ekf_set_process_noise(h, b, Q0.data());

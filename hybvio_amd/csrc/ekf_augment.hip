@@ -338,18 +338,7 @@ __global__ void ekf_normalize_kernel(int n, int map_dim, double *mall, int only_
 // block-diagonal A = diag(pC, pC, qC, I_10, {pC, qC} x poses [, I]); one thread per block pair.
 struct TransformArgs { int n, cam_poses; double *m, *P; double pC[9], qC[16], tr[3]; };   // row-major blocks
 
-__device__ __forceinline__ void blk_of(int idx, int cam_poses, int &start, int &size, int &kind)
-{
-    // kind 0: identity 1x1, 1: pC (3x3), 2: qC (4x4)
-    if (idx == 0) { start = POS; size = 3; kind = 1; return; }
-    if (idx == 1) { start = VEL; size = 3; kind = 1; return; }
-    if (idx == 2) { start = ORI; size = 4; kind = 2; return; }
-    if (idx < 13) { start = BGA + (idx - 3); size = 1; kind = 0; return; }
-    const int p = idx - 13;
-    if (p < 2 * cam_poses) { start = CAM + POSE * (p >> 1) + ((p & 1) ? 3 : 0); size = (p & 1) ? 4 : 3; kind = (p & 1) ? 2 : 1; return; }
-    start = CAM + POSE * cam_poses + (p - 2 * cam_poses); size = 1; kind = 0;
-}
-
+// (blk_of, the blocks of A: ekf_device.hpp)
 __global__ __launch_bounds__(256) void ekf_transform_kernel(TransformArgs a)
 {
     const int n = a.n, nblk = 13 + 2 * a.cam_poses + (n - CAM - POSE * a.cam_poses);

@@ -15,6 +15,7 @@
 
 #include "ekf_device.hpp"
 #include "ekf_host.hpp"
+#include "fresh_state.hpp"
 
 // (as ekf_update.hip: the EKF is judged against a relative tolerance; the library's default is -ffp-contract=off)
 #pragma clang fp contract(fast)
@@ -176,13 +177,12 @@ __device__ __forceinline__ bool unit_block_update(double *m, double *P, int odd_
     return true;
 }
 
-// the values of a fresh odometry::EKF (ekf.hpp: ZUPTtime = initZUPTtime = -1, wasStationary false) and of Session (framesSinceKeyframe 0)
+// every filter's control block as fresh_state.hpp defines it
 __global__ void ekf_control_init_kernel(int batch, hv_ekf_control ctl)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
-    ctl.zupt_time[b] = -1.0; ctl.init_zupt_time[b] = -1.0;
-    ctl.was_stationary[b] = 0; ctl.frames_since_keyframe[b] = 0;
+    ekf_control_fresh(ctl, b);
 }
 
 template <int NT>
@@ -288,6 +288,9 @@ void fill_control(hv::ControlArgs &a, const Ekf *e, const hv_ekf_control_params 
 }
 
 }  // namespace
+
+// the HV_ERR_INVALID check of the control block, for session.hip (hv_internal.hpp)
+int hv::ekf_control_check(const hv_ekf_control *ctl) { return control_complete(ctl) ? HV_OK : HV_ERR_INVALID; }
 
 void hv_ekf_control_default_params(hv_ekf_control_params *p)
 {

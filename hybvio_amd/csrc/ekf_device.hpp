@@ -16,6 +16,55 @@ namespace {
 enum { POS = 0, VEL = 3, ORI = 6, BGA = 10, BAA = 13, BAT = 16, SFT = 19, CAM = 20, INER = 20, POSE = 7, QD = 12 };
 enum { Q_ACC = 0, Q_GYRO = 3, Q_BGA_DRIFT = 6, Q_BAA_DRIFT = 9 };
 
+// The constructor values of odometry::EKF (ekf.cpp:153-225), scaled by noiseScale^2 as the constructor's last step scales them: the
+// one definition a new filter is written from, by hv_ekf_create on the host and by the session reset (session.hip) on the device.
+struct EkfFresh {
+    int n, cam_poses;
+    double pos, vel, ori, bga, baa, bat, sft, pos_trail, ori_trail;   // P's diagonal by state block (ori: the constructor's placeholder 1)
+    double q_acc, q_gyro;                                              // Q's diagonal
+    double ori_init;                                                   // initializeOrientation's variance (ekf.cpp:316)
+    __host__ __device__ double mean(int i) const { return (i == ORI || (i >= BAT && i < BAT + 3)) ? 1.0 : 0.0; }
+    __host__ __device__ double p_diag(int i) const
+    {
+        if (i < VEL) return pos;
+        if (i < ORI) return vel;
+        if (i < BGA) return ori;
+        if (i < BAA) return bga;
+        if (i < BAT) return baa;
+        if (i < SFT) return bat;
+        if (i == SFT) return sft;
+        if (i >= CAM + POSE * cam_poses) return 0.0;                   // map points
+        return (i - CAM) % POSE < 3 ? pos_trail : ori_trail;
+    }
+    __host__ __device__ double q_diag(int i) const { return i < Q_ACC + 3 ? q_acc : (i < Q_GYRO + 3 ? q_gyro : 0.0); }
+};
+inline EkfFresh ekf_fresh(const hv_ekf_params &par, int n, double noise_scale)
+{
+    auto sq = [&](double x) { return (x * x) * noise_scale; };
+    EkfFresh f;
+    f.n = n; f.cam_poses = par.cameraTrailLength;
+    f.pos = sq(par.noiseInitialPos); f.vel = sq(par.noiseInitialVel); f.ori = 1.0 * noise_scale;
+    f.bga = sq(par.noiseInitialBGA); f.baa = sq(par.noiseInitialBAA); f.bat = sq(par.noiseInitialBAT); f.sft = sq(par.noiseInitialSFT);
+    f.pos_trail = sq(par.noiseInitialPosTrail); f.ori_trail = sq(par.noiseInitialOriTrail);
+    f.q_acc = sq(par.noiseProcessAcc); f.q_gyro = sq(par.noiseProcessGyro);
+    f.ori_init = sq(par.noiseInitialOri);
+    return f;
+}
+
+// The diagonal blocks of transformTo's A = diag(pC, pC, qC, I_10, {pC, qC} x poses [, I]) (ekf.cpp:704-758), numbered in state order:
+// 13 + 2 * cam_poses + map entries of them (ekf_transform_kernel in ekf_augment.hip, the keep-pose reset in session.hip).
+__device__ __forceinline__ void blk_of(int idx, int cam_poses, int &start, int &size, int &kind)
+{
+    // kind 0: identity 1x1, 1: pC (3x3), 2: qC (4x4)
+    if (idx == 0) { start = POS; size = 3; kind = 1; return; }
+    if (idx == 1) { start = VEL; size = 3; kind = 1; return; }
+    if (idx == 2) { start = ORI; size = 4; kind = 2; return; }
+    if (idx < 13) { start = BGA + (idx - 3); size = 1; kind = 0; return; }
+    const int p = idx - 13;
+    if (p < 2 * cam_poses) { start = CAM + POSE * (p >> 1) + ((p & 1) ? 3 : 0); size = (p & 1) ? 4 : 3; kind = (p & 1) ? 2 : 1; return; }
+    start = CAM + POSE * cam_poses + (p - 2 * cam_poses); size = 1; kind = 0;
+}
+
 typedef double double4v __attribute__((ext_vector_type(4)));
 
 __device__ const double d_chi2inv95[HV_CHI2INV95_N] = { HV_CHI2INV95_VALUES };

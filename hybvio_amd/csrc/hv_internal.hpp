@@ -272,6 +272,10 @@ bool vu_fused_supported(const Ctx *c, int n_state, int np, int stereo, int batch
 // trail_index.hip: the HV_ERR_INVALID checks of hv_trail_index_params / hv_trail_index, shared with flow_predict.hip
 int trail_check_params(const hv_trail_index_params *p, int n_sets);
 int trail_check_state(const hv_trail_index *t);
+// track_table.hip, ekf_control.hip: the HV_ERR_INVALID checks of hv_track_table (with its parameters) and of hv_ekf_control, shared
+// with session.hip, whose reset writes the same state
+int tracks_check_table(const hv_track_table_params *p, int n_sets, const hv_track_table *t);
+int ekf_control_check(const hv_ekf_control *ctl);
 // capi.hip
 int build_levels_of_slot(Ctx *c, int slot);
 // klt.hip

@@ -14,7 +14,7 @@
 // the smallest keys. Each thread forms the key of its own j from the corners in LDS and ranks it by counting the smaller keys (no
 // atomics, no sort, deterministic). Compactions use a wave64 ballot, the lane prefix count and per-wave offsets in LDS.
 // Every input of a set is read before the first barrier after which outputs are written, so the compaction is in place.
-#include "hv_internal.hpp"
+#include "fresh_state.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -75,19 +75,7 @@ __device__ inline int block_prefix(bool flag, int *s_wave, int *total)
 
 __global__ __launch_bounds__(TT_MAX) void tracks_init_kernel(TableArgs a)
 {
-    const int set = blockIdx.x, i = threadIdx.x;
-    if (i < a.max_tracks) {
-        const size_t k = (size_t)set * a.max_tracks + i;
-        a.t.kf_valid[k] = 0;
-        a.t.blacklist[k] = 0;
-    }
-    if (i == 0) {
-        a.t.n_tracks[set] = 0;
-        a.t.frame_num[set] = 0;
-        a.t.mask_steps[set] = 0;
-        a.t.mask_radius[set] = a.radii[MASK_STEPS];
-        a.t.frame_flags[set] = 0;
-    }
+    tracks_fresh_set(a.t, blockIdx.x, a.max_tracks, a.radii[MASK_STEPS]);
 }
 
 __global__ __launch_bounds__(TT_MAX) void tracks_update_kernel(TableArgs a)
@@ -292,18 +280,16 @@ void fill_common(TableArgs &a, const Ctx *c, const hv_track_table_params *p, con
     a.max_track_length = p->maxTrackLength;
     a.movement_threshold = p->visualStationarityMovementThreshold;
     a.score_threshold = p->visualStationarityScoreThreshold;
-    const int min_dim = std::min(c->L.w[0], c->L.h[0]);
-    for (int s = -MASK_STEPS; s <= MASK_STEPS; ++s) {                // maskRadius (:569-576) at maskScale = s / 2
-        const double scale = std::pow(1.3, s / 2.0);
-        int r = (int)std::round(scale * min_dim * p->relativeMaskRadius);
-        if (r < 2) r = 2;
-        a.radii[s + MASK_STEPS] = r;
-    }
+    for (int s = -MASK_STEPS; s <= MASK_STEPS; ++s) a.radii[s + MASK_STEPS] = track_mask_radius(c, p, s);   // maskRadius (:569-576) at maskScale = s / 2
 }
 
 inline unsigned block_threads(int max_tracks) { return (unsigned)((max_tracks + 63) / 64 * 64); }
 
 }  // namespace
+
+// the HV_ERR_INVALID checks of the table, for session.hip (hv_internal.hpp)
+int tracks_check_table(const hv_track_table_params *p, int n_sets, const hv_track_table *t) { return check_table(p, n_sets, t); }
+
 }  // namespace hv
 
 using hv::Ctx;

@@ -18,6 +18,7 @@
 // compacted in order with a wave64 ballot, the lane prefix count and per-chunk offsets; the median of the truncated scores is a
 // rank count (no sort, no atomics); the shuffle is the one sequential chain and runs on one lane over the order in LDS; the
 // gather runs one wavefront per candidate. Arithmetic that the restatement rounds once is written with the _rn intrinsics.
+#include "fresh_state.hpp"
 #include "hv_camera.hpp"
 
 namespace hv {
@@ -67,23 +68,7 @@ __device__ inline size_t used_at(const TrailArgs &a, int set, int row, int col) 
 
 __global__ __launch_bounds__(TI_THREADS) void trail_init_kernel(TrailArgs a)
 {
-    const int set = blockIdx.x, tid = threadIdx.x;
-    for (int c = tid; c < a.M; c += TI_THREADS) {
-        a.t.col_id[(size_t)set * a.M + c] = -1;
-        a.t.col_len[(size_t)set * a.M + c] = 0;
-    }
-    if (tid < a.K) {
-        a.t.kf_row[(size_t)set * a.K + tid] = tid;
-        a.t.frame_number[(size_t)set * a.K + tid] = 0;
-        a.t.timestamp[(size_t)set * a.K + tid] = 0.0;
-    }
-    if (tid == 0) {
-        a.t.n_keyframes[set] = 1;                               // pushHeadKeyframe(0, 0) of the constructor
-        a.t.frame_counter[set] = 0;
-        a.t.n_blacklist[set] = 0;
-        a.t.n_order[set] = 0;
-        a.t.n_skipped[set] = 0;
-    }
+    trail_fresh_set(a.t, blockIdx.x, a.M, a.K);
 }
 
 __global__ __launch_bounds__(TI_THREADS) void trail_select_kernel(TrailArgs a, TrailCameras cams)

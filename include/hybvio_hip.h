@@ -170,7 +170,7 @@ int hv_klt_track_batch_ragged_dev(hv_ctx *ctx, int n_pairs, const int *prev_slot
  * State m (n = 20 + 7*cameraTrailLength + 3*hybridMapSize) and covariance P (n x n, f64,
  * column-major like Eigen) stay on the device; the scalar bookkeeping of the reference class
  * (sample clock, ZUPT rate limits, augmentTimes) lives in the host adapter (hybvio_amd/host); a batch of
- * resident sequences keeps the rate limits and flags on the device instead (hv_ekf_control, below).
+ * resident sequences keeps the rate limits and flags (hv_ekf_control) and the sample clock (hv_session) on the device instead.
  * Per-filter inputs are arrays indexed [filter][...]. Calls are asynchronous on the context
  * stream unless they return data to the host. */
 typedef struct hv_ekf hv_ekf;
@@ -194,7 +194,8 @@ int hv_ekf_state_dim(const hv_ekf *ekf);                         /* getStateDim 
 int hv_ekf_batch(const hv_ekf *ekf);
 /* setState / setStateCovariance / getState / getStateCovariance (ekf.cpp:950-979); either
  * pointer may be NULL. Synchronous. Also the route for the rare mean-side edits the adapter does
- * on the host (lockBiases, conditionOnLastPose, insertMapPoint, setInertialState, translateTo). */
+ * on the host (lockBiases, conditionOnLastPose, insertMapPoint, setInertialState, translateTo). A batch of resident sequences
+ * does not come here for initializeOrientation or for a reset: hv_session_imu_dev and hv_session_reset_dev do both in place. */
 int hv_ekf_set_state(hv_ekf *ekf, int filter, const double *m, const double *P_colmajor);
 int hv_ekf_get_state(hv_ekf *ekf, int filter, double *m, double *P_colmajor);
 int hv_ekf_get_means(hv_ekf *ekf, double *m_all /* batch * n */);
@@ -872,7 +873,7 @@ typedef struct hv_ekf_control {
 /* A fresh session: both clocks -1.0, the flag and the counter 0. */
 int hv_ekf_control_init_dev(hv_ekf *ekf, const hv_ekf_control *ctl);
 /* The control updates behind an IMU sample's predict (backend.cpp:738-749). time_dev [batch] double = the filter clock
- * t - firstSampleT (ekf.cpp:360), supplied by the caller. Per active filter, in this order:
+ * t - firstSampleT (ekf.cpp:360): the last row of hv_session_imu_dev's time_dev, or the caller's own. Per active filter, in this order:
  * - useDecayingZeroVelocityUpdate: updateZuptInitialization (ekf.cpp:594-611), skipped when was_stationary, time > 60 or
  *   time - init_zupt_time < 0.1; otherwise init_zupt_time = time and the zero-velocity update with
  *   R = initZuptR * noiseScale^2 * exp(0.5 * time);
@@ -1061,6 +1062,108 @@ int hv_flow_predict_batch_dev(hv_ekf *ekf, const hv_flow_predict_params *p, int 
                               const hv_camera_model *camera0, const hv_camera_model *camera1, float *pred_xy_dev,
                               double *distance_dev, int reuse_distance);
 
+/* ---- device session lifecycle: tracking status, reset rules, in-place re-initialisation (added within ABI 4) ------------
+ * Replaces, for the hv_ekf_batch(ekf) resident sequences of a filter batch (set s is filter s), what Session and Control do
+ * around a frame besides the filter algebra: the filter's sample clock (src/odometry/ekf.cpp:357-366) and
+ * initializeOrientation on the first IMU sample (ekf.cpp:299-317, backend.cpp:728-731), the ring of good-frame flags that
+ * decides Session::trackingStatus (backend.cpp:195-198, 807-819; CircularBuffer, odometry/util.hpp:111-149), Control's
+ * persistent status, freeze flag and reset rules (control.cpp:117-149), and the reset itself (control.cpp:49-65): a new Session --
+ * filter, tracker, trail index, control flags -- written in place for the sets that reset, with initializeAtPose
+ * (backend.cpp:224-229) for reset(true). Equal, array for array, to the literal restatement in tests/session_restatement.py.
+ * The state is device memory owned by the caller (like hv_track_table).
+ * All _dev entries: one launch, one workgroup per set, asynchronous on the filter's context stream, timed under
+ * HV_K_EKF_CONTROL, no allocation, copy-back or synchronisation inside (capturable in a HIP graph). Checks, in this order, the
+ * first two groups decided before the handle is looked at: HV_ERR_INVALID for a NULL required pointer (a member of a state
+ * struct included) or the argument ranges stated below; HV_ERR_UNSUPPORTED for a ring of more than HV_SESSION_MAX_WINDOW
+ * entries; HV_ERR_INVALID for a NULL handle; HV_ERR_UNSUPPORTED for more than 65535 sets or a state of more than 1024 entries.
+ * Masked-out sets (hv_session_imu_dev) and sets that do not reset (hv_session_reset_dev) are not touched at all.
+ * The zero-vector rule: initializeOrientation normalises the acceleration with Eigen's normalized(), which leaves a zero vector
+ * zero (Eigen >= 3.3); FromTwoVectors then sees c = 0 and a zero axis and returns q = (sqrt(2) / 2, 0, 0, 0), which is not a unit
+ * quaternion. initializeAtPose calls initializeOrientation(0), so this is the q0 of every reset(true); it is kept as it is. */
+#define HV_SESSION_MAX_WINDOW 256
+enum { HV_TRACKING_INIT = 0, HV_TRACKING_TRACKING = 1, HV_TRACKING_LOST = 2 };      /* api::TrackingStatus */
+enum { HV_RESET_NONE = 0, HV_RESET_FRESH = 1, HV_RESET_KEEP_POSE = 2 };             /* none, reset(false), reset(true) */
+typedef struct hv_session_params {
+    double targetFps;                              /* 30    codegen/parameter_definitions.c:220 */
+    int visualUpdateForEveryNFrame;                /* 1     :4   */
+    double goodFramesTimeWindowSeconds;            /* 2.0   :204 */
+    double goodFramesToTracking;                   /* 0.75  :201 */
+    double goodFramesToTrackingFailed;             /* 0.05  :202 */
+    int resetUntilInitSucceeds;                    /* 0     :193 */
+    int resetOnFailedTracking;                     /* 0     :195 */
+    double resetAfterTrackingFailsToInitialize;    /* 3.0   :197 */
+    int freezeOnFailedTracking;                    /* 0     :199 */
+} hv_session_params;
+void hv_session_default_params(hv_session_params *p);
+/* The ring holds W = (size_t)((double)targetFps / (double)visualUpdateForEveryNFrame * goodFramesTimeWindowSeconds) flags
+ * (backend.cpp:195-197; 60 with the defaults), computed on the host in every entry that takes the parameters:
+ * visualUpdateForEveryNFrame < 1 or W < 1 is HV_ERR_INVALID, W > HV_SESSION_MAX_WINDOW is HV_ERR_UNSUPPORTED. */
+typedef struct hv_session {                /* [n_sets] unless noted */
+    float   *good_ring;               /* [n_sets][W]  Session::visualUpdateCounter.mBuffer */
+    int32_t *ring_head;               /* mHead */
+    int32_t *ring_entries;            /* mEntries */
+    int32_t *tracking_status;         /* Session::trackingStatus */
+    int32_t *control_status;          /* Control::controlTrackingStatus */
+    double  *last_reset_time;         /* Control::lastResetTime */
+    uint8_t *first_sample;            /* EKF::firstSample */
+    double  *first_sample_t;          /* EKF::firstSampleT */
+    double  *prev_sample_t;           /* EKF::prevSampleT */
+    double  *time;                    /* EKF::time */
+    uint8_t *initialized_orientation; /* Session::initializedOrientation */
+} hv_session;
+/* A Control with its first Session, straight after construction: the ring empty (its W entries 0, head and entries 0), both
+ * statuses INIT, last_reset_time 0.0, first_sample 1, first_sample_t and prev_sample_t -1.0, time 0.0,
+ * initialized_orientation 0. The filter is not touched. */
+int hv_session_init_dev(hv_ekf *ekf, const hv_session_params *p, const hv_session *st);
+/* The session part of the n_samples IMU samples in front of a frame (1 <= n_samples <= HV_EKF_MAX_PREDICT_SAMPLES), in the layout
+ * of hv_ekf_predict_n_dev: t_dev [n_samples][batch] the sample times, acc_dev [n_samples][batch][3]; active_dev [batch] uint8
+ * (NULL: all). Per active filter, in sample order:
+ * - while initialized_orientation is 0: initializeOrientation(acc) as oracle/ekf_oracle.c:285-311 (its antiparallel branch
+ *   included) under the zero-vector rule above, then the flag is set. Writes m[ORI .. ORI + 3] and the 4 x 4 ORI block of P,
+ *   nothing else of the filter.
+ * - the clock: first_sample set: first_sample_t = t, the flag cleared, dt = 0; otherwise dt = t - prev_sample_t and
+ *   time = t - first_sample_t, one rounded subtraction each; then prev_sample_t = t.
+ * dt_dev [n_samples][batch] receives dt: the dt_dev of hv_ekf_predict_n_dev, whose kernels skip a sample unless dt > 0
+ * (csrc/ekf_predict.hip), as ekf.cpp:367 does. time_dev [n_samples][batch] receives the clock after the sample: row
+ * n_samples - 1 is the time_dev of hv_ekf_imu_control_dev, hv_ekf_frame_control_dev and hv_trail_select_batch_dev.
+ * A masked filter gets dt 0 and its stored time in every row. */
+int hv_session_imu_dev(hv_ekf *ekf, const hv_session *st, int n_samples, const double *t_dev, const double *acc_dev,
+                       const unsigned char *active_dev, double *dt_dev, double *time_dev);
+/* Once per processed frame, behind hv_trail_finish_batch_dev. good_frame_dev [batch] uint8 as that entry wrote it;
+ * full_update_dev [batch] uint8 (NULL: every frame is a full update). Per set:
+ * - backend.cpp:807-819: on a full update put(good ? 1.0f : 0.0f); when entries > W / 2 (integer division) the mean as
+ *   CircularBuffer::mean() forms it (a binary32 sum over mBuffer[0 .. entries) divided by the count), widened to binary64, moves
+ *   tracking_status to TRACKING above goodFramesToTracking and from TRACKING to LOST below goodFramesToTrackingFailed.
+ * - control.cpp:121-149 with t = first_sample_t + time: status_dev [batch] int32 = control_status BEFORE its update (what
+ *   output.trackingStatus carries); frozen_dev [batch] uint8 = freezeOnFailedTracking && control_status != INIT &&
+ *   tracking_status != TRACKING; then control_status takes tracking_status unless that would return it to INIT; then, with
+ *   expired = last_reset_time + resetAfterTrackingFailsToInitialize < t, the first rule that holds of
+ *     control_status == INIT && expired && resetUntilInitSucceeds         -> HV_RESET_FRESH
+ *     resetOnFailedTracking && tracking_status == LOST                    -> HV_RESET_KEEP_POSE
+ *     control_status != INIT && tracking_status == INIT && expired        -> HV_RESET_KEEP_POSE
+ *   goes to reset_kind_dev [batch] int32 (else HV_RESET_NONE).
+ * status_dev and frozen_dev may be NULL. The entry decides a reset; hv_session_reset_dev performs it. */
+int hv_session_status_dev(hv_ekf *ekf, const hv_session_params *p, const hv_session *st, const unsigned char *good_frame_dev,
+                          const unsigned char *full_update_dev, int32_t *status_dev, unsigned char *frozen_dev,
+                          int32_t *reset_kind_dev);
+/* Control::reset for the sets whose reset_kind_dev [batch] int32 is HV_RESET_FRESH or HV_RESET_KEEP_POSE, in one launch:
+ * - pos = m[POS ..] and q = m[ORI ..] are read first; last_reset_time = first_sample_t + time of the old clock.
+ * - the filter becomes what hv_ekf_create writes: m, all of P (in the covariance buffer that is current: fetch nothing again,
+ *   the ping-pong of hv_ekf_augment is not moved), the 12 x 12 Q, dydx zero.
+ * - HV_RESET_KEEP_POSE: initializeOrientation(0) under the zero-vector rule, then transformTo(pos, q) (ekf.cpp:704-758)
+ *   applied literally with that q0 = (sqrt(2) / 2, 0, 0, 0): qChange has norm sqrt(1 / 2), so the mean's orientation is q / 2
+ *   until the next predict normalises it, and the P blocks carry the factor 1 / 4 or 1 / 2 the reference's have. The fresh P
+ *   is block diagonal, so A P A' is formed block by block. initialized_orientation = 1. HV_RESET_FRESH: initialized_orientation = 0.
+ * - the set's slice of table, trail and ctl as hv_tracks_init_batch_dev, hv_trail_init_batch_dev and hv_ekf_control_init_dev
+ *   write it (the argument checks of those entries apply, their limits HV_TRACKS_MAX_TRACKS and HV_TRAIL_MAX_POSES included;
+ *   tracks_p->maxTracks must equal trail_p->maxTracks: HV_ERR_INVALID otherwise).
+ * - the session: ring empty, tracking_status INIT, first_sample 1, first_sample_t and prev_sample_t -1.0, time 0.0;
+ *   control_status is Control's and is kept.
+ * Sequence-wide random draws (sharedData->rng) survive a reset in the reference; they are the caller's (draws_dev). */
+int hv_session_reset_dev(hv_ekf *ekf, const hv_session_params *p, const hv_session *st, const hv_ekf_control *ctl,
+                         const hv_track_table_params *tracks_p, const hv_track_table *table,
+                         const hv_trail_index_params *trail_p, const hv_trail_index *trail, const int32_t *reset_kind_dev);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
@@ -1071,7 +1174,7 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3* */,
-       HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev */,
+       HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev, hv_session_*_dev */,
        HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev */,
        HV_K_COUNT = 20 };
 int hv_profile_enable(hv_ctx *ctx, int on);
