@@ -150,6 +150,25 @@ class SessionState(C.Structure):
                                           "initialized_orientation")]
 
 
+class OutputParams(C.Structure):
+    _fields_ = [("imuToCamera", C.c_double * 16), ("imuToOutput", C.c_double * 16), ("maxVisualUpdates", C.c_int),
+                ("maxSuccessfulVisualUpdates", C.c_int), ("cameraTrailLength", C.c_int), ("maxTracks", C.c_int), ("useStereo", C.c_int)]
+
+
+class OutputFrame(C.Structure):
+    """hv_output_frame: what the frame's other entries wrote (device pointers; the last five may be None)."""
+    _fields_ = [(k, C.c_void_p) for k in ("cand_id_dev", "n_candidates_dev", "status_dev", "gate_status_dev", "pf_dev",
+                                          "tracking_status_dev", "frozen_dev", "stationary_dev", "slam_to_odometry_dev",
+                                          "odometry_to_slam_dev", "ready_dev")]
+
+
+class OutputTable(C.Structure):
+    """hv_output: device pointers owned by the caller."""
+    _fields_ = [(k, C.c_void_p) for k in ("t", "tracking_status", "stationary_visual", "inertial_mean", "inertial_cov_diag",
+                                          "position_cov", "velocity_cov", "n_trail", "trail_time", "trail_pose", "api_pose",
+                                          "api_trail_pose", "n_points", "point_id", "point_status", "point_first_pixel", "point_xyz")]
+
+
 class HvError(RuntimeError):
     pass
 
@@ -299,6 +318,9 @@ PROTOTYPES = {
     "hv_session_reset_dev": (C.c_int, [C.c_void_p, C.POINTER(SessionParams), C.POINTER(SessionState), C.POINTER(EkfControlTable),
                                        C.POINTER(TrackTableParams), C.POINTER(TrackTable), C.POINTER(TrailIndexParams),
                                        C.POINTER(TrailIndexTable), C.c_void_p]),
+    "hv_output_default_params": (None, [C.POINTER(OutputParams)]),
+    "hv_output_dev": (C.c_int, [C.c_void_p, C.POINTER(OutputParams), C.POINTER(SessionState), C.POINTER(TrailIndexTable),
+                                C.POINTER(OutputFrame), C.POINTER(OutputTable)]),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -960,6 +982,42 @@ def session_state(n_sets: int, W: int, device="cuda") -> Session:
     return Session(n_sets, W, device)
 
 
+def output_default_params(imu_to_camera=None, imu_to_output=None, **over) -> OutputParams:
+    """hv_output_default_params; the two matrices row-major 4 x 4."""
+    p = OutputParams()
+    lib().hv_output_default_params(C.byref(p))
+    for T, name in ((imu_to_camera, "imuToCamera"), (imu_to_output, "imuToOutput")):
+        if T is not None:
+            getattr(p, name)[:] = list(np.asarray(T, np.float64).reshape(16))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def output_frame(**pointers) -> OutputFrame:
+    """hv_output_frame from device pointers by member name (0 / None = NULL)."""
+    f = OutputFrame()
+    for k, v in pointers.items():
+        setattr(f, k, v or None)
+    return f
+
+
+class Output:
+    """hv_output for n_sets sequences: torch tensors on the current device by member name (self.m) and the pointer table over
+    them (self.table). T = cameraTrailLength, V = maxVisualUpdates of the parameters."""
+
+    def __init__(self, n_sets: int, params: "OutputParams"):
+        S, T, V = n_sets, params.cameraTrailLength, params.maxVisualUpdates
+        i32, f64 = torch.int32, torch.float64
+        shapes = dict(t=((S,), f64), tracking_status=((S,), i32), stationary_visual=((S,), torch.uint8), inertial_mean=((S, 20), f64),
+                      inertial_cov_diag=((S, 20), f64), position_cov=((S, 3, 3), f64), velocity_cov=((S, 3, 3), f64), n_trail=((S,), i32),
+                      trail_time=((S, T), f64), trail_pose=((S, T, 7), f64), api_pose=((S, 7), f64), api_trail_pose=((S, T, 7), f64),
+                      n_points=((S,), i32), point_id=((S, V), i32), point_status=((S, V), i32),
+                      point_first_pixel=((S, V, 2), torch.float32), point_xyz=((S, V, 3), f64))
+        self.m = {k: torch.zeros(shape, dtype=dt, device="cuda") for k, (shape, dt) in shapes.items()}
+        self.table = OutputTable(*(self.m[k].data_ptr() for k, _ in OutputTable._fields_))
+
+
 def _f(a):
     return np.ascontiguousarray(a, np.float64)
 
@@ -1317,6 +1375,11 @@ class EkfBatch:
         self._chk(lib().hv_session_reset_dev(self._h, C.byref(params), C.byref(st.table), C.byref(ctl.table), C.byref(tracks_params),
                                              C.byref(table), C.byref(trail_params), C.byref(trail), C.c_void_p(reset_kind_dev)),
                   "hv_session_reset_dev")
+
+    def output_dev(self, params: "OutputParams", st: "Session", trail: "TrailIndexTable", frame: "OutputFrame", out: "Output"):
+        """hv_output_dev: the frame's output record of every set (pose, covariances, pose trail, status, point cloud)."""
+        self._chk(lib().hv_output_dev(self._h, C.byref(params), C.byref(st.table), C.byref(trail), C.byref(frame), C.byref(out.table)),
+                  "hv_output_dev")
 
     def flow_predict_batch_dev(self, params: "FlowPredictParams", kind: int, trail_params: "TrailIndexParams", trail: "TrailIndexTable",
                                table: "TrackTable", c0_dev, cam0: "CameraModel", cam1: "CameraModel", pred_xy_dev, distance_dev=0,

@@ -1,7 +1,8 @@
-// Small binary64 geometry shared by the kernels that read camera poses from the EKF mean (vu_prepare.hip, flow_predict.hip) and by the
-// RANSAC kernels (rot_ransac.hip, ransac5.hip, ransac3.hip): 3-vector and 3x3 products, odometry::util::quat2rmat / quat2rmat_d
-// (src/odometry/util.cpp:10-47) and the pseudo-inverse of a full-rank 3x2 matrix (src/odometry/triangulation.cpp:1000-1002). 3x3
-// matrices are row-major double[9] (like oracle/triangulation_oracle.c).
+// Small binary64 geometry shared by the kernels that read camera poses from the EKF mean (vu_prepare.hip, flow_predict.hip, output.hip)
+// and by the RANSAC kernels (rot_ransac.hip, ransac5.hip, ransac3.hip): 3-vector and 3x3 products, odometry::util::quat2rmat /
+// quat2rmat_d (src/odometry/util.cpp:10-47), rmat2quat, the inverse of a general 4x4 and the pseudo-inverse of a full-rank 3x2 matrix
+// (src/odometry/triangulation.cpp:1000-1002). 3x3 and 4x4 matrices are row-major double[9] / double[16] (like
+// oracle/triangulation_oracle.c).
 //
 // No include guard and no namespace of its own, on purpose: a translation unit includes it once, inside its anonymous namespace and
 // behind its own `#pragma clang fp contract(...)`, so the functions are compiled under the contraction mode of the file that uses
@@ -53,6 +54,65 @@ __device__ __forceinline__ void quat2rmat(const double *q, double *R)           
     const double d2[9] = {-c, b, a, b, c, d, -a, d, -c}, d3[9] = {-d, -a, b, a, -d, c, b, c, d};
 #pragma unroll
     for (int k = 0; k < 9; ++k) { dR[k] = d0[k]; dR[9 + k] = d1[k]; dR[18 + k] = d2[k]; dR[27 + k] = d3[k]; }
+}
+
+// odometry::util::rmat2quat = Eigen::Quaterniond(Matrix3d) (Eigen/src/Geometry/Quaternion.h, quaternionbase_assign_impl<Other, 3, 3>):
+// R row-major, q = (w, x, y, z). The sign of q is the branch's, not the filter's.
+[[maybe_unused]] __device__ void rmat2quat(const double *R, double *q)
+{
+    double t = (R[0] + R[4]) + R[8];
+    if (t > 0.0) {
+        t = sqrt(t + 1.0);
+        q[0] = 0.5 * t;
+        t = 0.5 / t;
+        q[1] = (R[7] - R[5]) * t; q[2] = (R[2] - R[6]) * t; q[3] = (R[3] - R[1]) * t;
+    } else {
+        // i = the largest diagonal entry in Eigen's order, j = (i + 1) % 3, k = (j + 1) % 3; written as selections among values
+        // read at constant indices, so that no array is indexed by i (a dynamic index puts R and q in scratch)
+        const double r00 = R[0], r01 = R[1], r02 = R[2], r10 = R[3], r11 = R[4], r12 = R[5], r20 = R[6], r21 = R[7], r22 = R[8];
+        int i = 0;
+        if (r11 > r00) i = 1;
+        if (r22 > (i ? r11 : r00)) i = 2;
+        const double mii = i == 0 ? r00 : i == 1 ? r11 : r22, mjj = i == 0 ? r11 : i == 1 ? r22 : r00, mkk = i == 0 ? r22 : i == 1 ? r00 : r11;
+        const double mkj = i == 0 ? r21 : i == 1 ? r02 : r10, mjk = i == 0 ? r12 : i == 1 ? r20 : r01;
+        const double mji = i == 0 ? r10 : i == 1 ? r21 : r02, mij = i == 0 ? r01 : i == 1 ? r12 : r20;
+        const double mki = i == 0 ? r20 : i == 1 ? r01 : r12, mik = i == 0 ? r02 : i == 1 ? r10 : r21;
+        t = sqrt(((mii - mjj) - mkk) + 1.0);
+        const double qi = 0.5 * t;
+        t = 0.5 / t;
+        const double qj = (mji + mij) * t, qk = (mki + mik) * t;
+        q[0] = (mkj - mjk) * t;
+        q[1] = i == 0 ? qi : i == 1 ? qk : qj;
+        q[2] = i == 1 ? qi : i == 2 ? qk : qj;
+        q[3] = i == 2 ? qi : i == 0 ? qk : qj;
+    }
+}
+
+// inverse of a general 4x4 (row-major) through its cofactors, grouped by the 2x2 minors of the upper and the lower row pair; the
+// determinant is inverted once (as pinv32 and the 3x3 inverses of the RANSAC kernels do)
+[[maybe_unused]] __device__ void inv4(const double *a, double *b)
+{
+    const double s0 = a[0] * a[5] - a[4] * a[1], s1 = a[0] * a[6] - a[4] * a[2], s2 = a[0] * a[7] - a[4] * a[3];
+    const double s3 = a[1] * a[6] - a[5] * a[2], s4 = a[1] * a[7] - a[5] * a[3], s5 = a[2] * a[7] - a[6] * a[3];
+    const double c5 = a[10] * a[15] - a[14] * a[11], c4 = a[9] * a[15] - a[13] * a[11], c3 = a[9] * a[14] - a[13] * a[10];
+    const double c2 = a[8] * a[15] - a[12] * a[11], c1 = a[8] * a[14] - a[12] * a[10], c0 = a[8] * a[13] - a[12] * a[9];
+    const double id = 1.0 / (s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0);
+    b[0] = (a[5] * c5 - a[6] * c4 + a[7] * c3) * id;
+    b[1] = (-a[1] * c5 + a[2] * c4 - a[3] * c3) * id;
+    b[2] = (a[13] * s5 - a[14] * s4 + a[15] * s3) * id;
+    b[3] = (-a[9] * s5 + a[10] * s4 - a[11] * s3) * id;
+    b[4] = (-a[4] * c5 + a[6] * c2 - a[7] * c1) * id;
+    b[5] = (a[0] * c5 - a[2] * c2 + a[3] * c1) * id;
+    b[6] = (-a[12] * s5 + a[14] * s2 - a[15] * s1) * id;
+    b[7] = (a[8] * s5 - a[10] * s2 + a[11] * s1) * id;
+    b[8] = (a[4] * c4 - a[5] * c2 + a[7] * c0) * id;
+    b[9] = (-a[0] * c4 + a[1] * c2 - a[3] * c0) * id;
+    b[10] = (a[12] * s4 - a[13] * s2 + a[15] * s0) * id;
+    b[11] = (-a[8] * s4 + a[9] * s2 - a[11] * s0) * id;
+    b[12] = (-a[4] * c3 + a[5] * c1 - a[6] * c0) * id;
+    b[13] = (a[0] * c3 - a[1] * c1 + a[2] * c0) * id;
+    b[14] = (-a[12] * s3 + a[13] * s1 - a[14] * s0) * id;
+    b[15] = (a[8] * s3 - a[9] * s1 + a[10] * s0) * id;
 }
 
 // pseudo-inverse of the full-rank 3x2 A (row-major): (A'A)^-1 A', the determinant inverted once

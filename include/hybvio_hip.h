@@ -1164,6 +1164,92 @@ int hv_session_reset_dev(hv_ekf *ekf, const hv_session_params *p, const hv_sessi
                          const hv_track_table_params *tracks_p, const hv_track_table *table,
                          const hv_trail_index_params *trail_p, const hv_trail_index *trail, const int32_t *reset_kind_dev);
 
+/* ---- device output stage: pose, covariances, pose trail, point cloud (added within ABI 4) ------------------------------
+ * Replaces, for the hv_ekf_batch(ekf) resident sequences of a filter batch (set s is filter s), what a session hands back at the
+ * end of a frame: src/odometry/backend.cpp:840-860 (transformInertialState :69-79, setFromEKF output.cpp:50-77, computePose
+ * :1368-1386, getPointCloud :255-280 over the point-cloud lines of the visit loop :905, 1066-1070, 1118, 1124, 1191, 1239-1251),
+ * Control's overwrite of t and trackingStatus (control.cpp:117-128) and the API's convertOutputPose (src/api/api.cpp:726-742,
+ * 759-808). One small record per set instead of a read-back of m, P and the index. Literal restatement:
+ * tests/output_restatement.py. Position in a frame: behind hv_trail_finish_batch_dev, the frame's augmentation and
+ * hv_session_status_dev, in front of hv_session_reset_dev. Per set, in binary64 and in the operation order of the restatement:
+ * - a set whose frozen_dev is 1 is not written at all (control.cpp:128);
+ * - t = first_sample_t + time, one rounded addition; tracking_status = tracking_status_dev; stationary_visual = stationary_dev;
+ * - the inertial state: (pos, ori) = toOdometryPose(toWorldToCamera(m[POS], m[ORI], imuToCamera) * slamToOdometry, imuToCamera)
+ *   (util.cpp:121-142; rmat2quat = Eigen::Quaterniond(Matrix3d), the inverse of the 4 x 4 through its cofactors with one
+ *   reciprocal of the determinant), then EKF::transformTo(pos, ori) (ekf.cpp:704-757) on m[0 .. 20) and P[0 .. 20, 0 .. 20): A is
+ *   block diagonal, so only its POS, VEL and ORI blocks of A P A' are formed. inertial_mean [20], inertial_cov_diag [20],
+ *   position_cov / velocity_cov [9] row-major. A set that is not ready, or NULL matrices, use the identity for both transforms;
+ * - the pose trail: n_trail = n_keyframes - 1 as finish left it; trail_time[i] = the timestamp of keyframe i + 1; trail_pose[i]
+ *   [7] = position, orientation (w, x, y, z) of computePose(i) from history pose i of the mean, zeros for a set that is not
+ *   ready; entries behind n_trail are not written. Deviation: with exactly one historical pose the reference leaves element 0 as
+ *   setFromEKF of its coordinate filter wrote it, a slot that filter never initialises; here it is computePose(0) like every other;
+ * - the point cloud: the candidates in visit order; visited = status[v][0] != HV_TRI_NOT_VISITED; the loop stops at the visit
+ *   that brings the successes (gate status INLIER) to maxSuccessfulVisualUpdates (<= 0: no such limit) or the attempts to
+ *   maxVisualUpdates, the rule of hv_trail_finish_batch_dev, and that candidate is NOT appended (the break at :1244 precedes the
+ *   push at :1249); every visited candidate in front of it whose triangulation status is HV_TRI_OK is appended with its ID,
+ *   point_status 4 (OUTLIER) when its prepare status is HV_PREPARE_VU_OK and its gate status is not INLIER, else 1 (POSE_TRAIL),
+ *   point_first_pixel = image_point of the candidate's column (cand_col), first camera, in keyframe 1 (the frame's keyframe,
+ *   which finish's push leaves untouched), and point_xyz = odometryToSlam applied to pf_dev. A set that is not ready has
+ *   n_points = 0; entries behind n_points are not written;
+ * - api_pose [7] and api_trail_pose[i] [7]: convertOutputPose of the transformed inertial pose and of trail_pose[i], with the
+ *   reference's inverted test: a non-identity imuToOutput passes the pose through, the identity sends it through
+ *   toWorldToCamera / toOdometryPose, so the orientation carries rmat2quat's sign, not the filter's.
+ * A non-finite mean gives whatever this arithmetic yields in its own set and touches no other. fullPointCloud, the hybrid map and
+ * the stereo-depth cloud are unsupported, like in the index; SLAM itself is the caller's (setCoordinates supplies the matrices).
+ * One launch of one wavefront per set on the filter's context stream, timed under HV_K_EKF_CONTROL, no allocation, copy-back or
+ * synchronisation inside (capturable in a HIP graph). Checks, the first two groups decided before the handle is looked at:
+ * HV_ERR_INVALID for a NULL required pointer (p, st and its first_sample_t / time, trail and every member, in and its members
+ * but frozen_dev, stationary_dev, ready_dev and the two matrices -- of which both or none are given --, out and every member),
+ * cameraTrailLength, maxTracks or maxVisualUpdates < 1; HV_ERR_UNSUPPORTED for maxVisualUpdates > HV_TRAIL_MAX_VISITS or
+ * cameraTrailLength + 1 > HV_TRAIL_MAX_POSES; HV_ERR_INVALID for a NULL handle; HV_ERR_UNSUPPORTED for more than 65535 sets, a
+ * state of more than 1024 or of fewer than 20 + 7 * cameraTrailLength entries. Counts and indices read from device memory
+ * (n_keyframes, n_candidates, kf_row, cand_col) are clamped to their capacity. */
+typedef struct hv_output_params {
+    double imuToCamera[16], imuToOutput[16];   /* row-major; identity */
+    int maxVisualUpdates;                      /* 20   V of the visit arrays */
+    int maxSuccessfulVisualUpdates;            /* 5 */
+    int cameraTrailLength;                     /* 20   K = cameraTrailLength + 1 of the index */
+    int maxTracks;                             /* 200  M of the index */
+    int useStereo;                             /* 1    C of the index */
+} hv_output_params;
+void hv_output_default_params(hv_output_params *p);
+/* What the frame's other entries wrote, device memory; V = maxVisualUpdates. */
+typedef struct hv_output_frame {
+    const int32_t *cand_id_dev;           /* [V][n_sets]      hv_trail_select_batch_dev */
+    const int32_t *n_candidates_dev;      /* [n_sets] */
+    const int32_t *status_dev;            /* [V][n_sets][2]   hv_ekf_visual_frame_ragged_dev */
+    const int32_t *gate_status_dev;       /* [V][n_sets] */
+    const double  *pf_dev;                /* [V][n_sets][3] */
+    const int32_t *tracking_status_dev;   /* [n_sets]         status_dev of hv_session_status_dev */
+    const uint8_t *frozen_dev;            /* [n_sets]         frozen_dev of hv_session_status_dev; NULL: nothing is frozen */
+    const uint8_t *stationary_dev;        /* [n_sets]         stationary_dev of hv_ekf_frame_control_dev; NULL: 0 */
+    const double  *slam_to_odometry_dev;  /* [n_sets][16]     row-major, odo.inverse() * slam (backend.cpp:61); NULL (both): identity */
+    const double  *odometry_to_slam_dev;  /* [n_sets][16]     slam.inverse() * odo (:62) */
+    const uint8_t *ready_dev;             /* [n_sets]         isReady(); NULL: ready (the reference without -useSlam) */
+} hv_output_frame;
+/* The record, device memory owned by the caller; [n_sets] unless noted, T = cameraTrailLength. */
+typedef struct hv_output {
+    double  *t;                  /* Output::t as Control leaves it */
+    int32_t *tracking_status;    /* api::TrackingStatus */
+    uint8_t *stationary_visual;
+    double  *inertial_mean;      /* [n_sets][20] */
+    double  *inertial_cov_diag;  /* [n_sets][20] */
+    double  *position_cov;       /* [n_sets][9] */
+    double  *velocity_cov;       /* [n_sets][9] */
+    int32_t *n_trail;
+    double  *trail_time;         /* [n_sets][T] */
+    double  *trail_pose;         /* [n_sets][T][7] */
+    double  *api_pose;           /* [n_sets][7] */
+    double  *api_trail_pose;     /* [n_sets][T][7] */
+    int32_t *n_points;
+    int32_t *point_id;           /* [n_sets][V] */
+    int32_t *point_status;       /* [n_sets][V]  PointFeature::Status: 1 POSE_TRAIL, 4 OUTLIER */
+    float   *point_first_pixel;  /* [n_sets][V][2] */
+    double  *point_xyz;          /* [n_sets][V][3] */
+} hv_output;
+int hv_output_dev(hv_ekf *ekf, const hv_output_params *p, const hv_session *st, const hv_trail_index *trail,
+                  const hv_output_frame *in, const hv_output *out);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
@@ -1174,7 +1260,7 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3* */,
-       HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev, hv_session_*_dev */,
+       HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev, hv_session_*_dev, hv_output_dev */,
        HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev */,
        HV_K_COUNT = 20 };
 int hv_profile_enable(hv_ctx *ctx, int on);
