@@ -169,6 +169,19 @@ class OutputTable(C.Structure):
                                           "api_trail_pose", "n_points", "point_id", "point_status", "point_first_pixel", "point_xyz")]
 
 
+class FullCloudFrame(C.Structure):
+    """hv_full_cloud_frame: what select was given and the visit loop wrote (device pointers; full_update_dev, stationary_dev,
+    odometry_to_slam_dev and ready_dev may be None)."""
+    _fields_ = [(k, C.c_void_p) for k in ("draws_dev", "full_update_dev", "cand_id_dev", "n_candidates_dev", "status_dev",
+                                          "gate_status_dev", "pf_dev", "stationary_dev", "odometry_to_slam_dev", "ready_dev")]
+
+
+class FullCloudTable(C.Structure):
+    """hv_full_cloud: device pointers owned by the caller (n_attempts and good_frame may be None)."""
+    _fields_ = [(k, C.c_void_p) for k in ("n_points", "point_id", "point_status", "point_first_pixel", "point_xyz", "n_tail", "tail_id",
+                                          "tail_status", "tail_col", "tail_pose_mask", "n_attempts", "good_frame")]
+
+
 class HvError(RuntimeError):
     pass
 
@@ -321,6 +334,8 @@ PROTOTYPES = {
     "hv_output_default_params": (None, [C.POINTER(OutputParams)]),
     "hv_output_dev": (C.c_int, [C.c_void_p, C.POINTER(OutputParams), C.POINTER(SessionState), C.POINTER(TrailIndexTable),
                                 C.POINTER(OutputFrame), C.POINTER(OutputTable)]),
+    "hv_full_point_cloud_dev": (C.c_int, [C.c_void_p, C.POINTER(TrailIndexParams), C.c_void_p, C.POINTER(TrailIndexTable),
+                                          C.POINTER(TrackTable), C.POINTER(FullCloudFrame), C.POINTER(FullCloudTable)]),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -1018,6 +1033,31 @@ class Output:
         self.table = OutputTable(*(self.m[k].data_ptr() for k, _ in OutputTable._fields_))
 
 
+def full_cloud_frame(**pointers) -> FullCloudFrame:
+    """hv_full_cloud_frame from device pointers by member name (0 / None = NULL)."""
+    f = FullCloudFrame()
+    for k, v in pointers.items():
+        setattr(f, k, v or None)
+    return f
+
+
+class FullCloud:
+    """hv_full_cloud for n_sets sequences: torch tensors on the current device by member name (self.m) and the pointer table over
+    them (self.table). M = maxTracks of the index parameters; tail_pose_mask is an int64 tensor holding the 64-bit masks.
+    counters=False leaves the optional n_attempts / good_frame NULL."""
+
+    def __init__(self, n_sets: int, params: "TrailIndexParams", counters: bool = True, fill: int = 0):
+        S, M = n_sets, params.maxTracks
+        i32 = torch.int32
+        shapes = dict(n_points=((S,), i32), point_id=((S, M), i32), point_status=((S, M), i32),
+                      point_first_pixel=((S, M, 2), torch.float32), point_xyz=((S, M, 3), torch.float64), n_tail=((S,), i32),
+                      tail_id=((S, M), i32), tail_status=((S, M), i32), tail_col=((S, M), i32), tail_pose_mask=((S, M), torch.int64),
+                      n_attempts=((S,), i32), good_frame=((S,), torch.uint8))
+        self.m = {k: torch.full(shape, fill, dtype=dt, device="cuda") for k, (shape, dt) in shapes.items()}
+        self.table = FullCloudTable(*(self.m[k].data_ptr() if counters or k not in ("n_attempts", "good_frame") else None
+                                      for k, _ in FullCloudTable._fields_))
+
+
 def _f(a):
     return np.ascontiguousarray(a, np.float64)
 
@@ -1380,6 +1420,14 @@ class EkfBatch:
         """hv_output_dev: the frame's output record of every set (pose, covariances, pose trail, status, point cloud)."""
         self._chk(lib().hv_output_dev(self._h, C.byref(params), C.byref(st.table), C.byref(trail), C.byref(frame), C.byref(out.table)),
                   "hv_output_dev")
+
+    def full_point_cloud_dev(self, trail_params: "TrailIndexParams", vu_params: "VuParams", trail: "TrailIndexTable", table: "TrackTable",
+                             frame: "FullCloudFrame", out: "FullCloud"):
+        """hv_full_point_cloud_dev (odometry.fullPointCloud): the cloud of the visited tracks with the stopping candidate, then every
+        remaining track of the shuffled order, triangulated from the mean as the frame's updates left it. Between
+        visual_frame_ragged_dev and trail_finish_batch_dev."""
+        self._chk(lib().hv_full_point_cloud_dev(self._h, C.byref(trail_params), C.byref(vu_params), C.byref(trail), C.byref(table),
+                                                C.byref(frame), C.byref(out.table)), "hv_full_point_cloud_dev")
 
     def flow_predict_batch_dev(self, params: "FlowPredictParams", kind: int, trail_params: "TrailIndexParams", trail: "TrailIndexTable",
                                table: "TrackTable", c0_dev, cam0: "CameraModel", cam1: "CameraModel", pred_xy_dev, distance_dev=0,

@@ -25,6 +25,7 @@ namespace hv {
 namespace {
 
 #include "hv_geometry.hpp"    // mm3, mmT3, mv3, mTv3, quat2rmat, quat2rmat_d, pinv32
+#include "hv_triangulation.hpp"   // camera_pose_pR, triangulate_two
 #include "hv_workgroup.hpp"   // clampi, stage_cameras
 
 constexpr int FP_THREADS = 256;
@@ -53,25 +54,6 @@ struct FlowCameras { hv_camera_model cam0, cam1; };
 __device__ inline void transform_vec3(const double *T, const double *v, double *out)
 {
     for (int i = 0; i < 3; ++i) out[i] = ((T[4 * i] * v[0] + T[4 * i + 1] * v[1]) + T[4 * i + 2] * v[2]) + T[4 * i + 3];
-}
-
-// triangulateWithTwoCameras without derivatives (triangulation.cpp:610-646), in the order of oracle/triangulation_oracle.c
-__device__ inline void triangulate_two(const double *P0, const double *P1, const double *ip0, const double *ip1, double *pf)
-{
-    const double *R0 = P0 + 3, *R1 = P1 + 3;
-    double C[9], d01[3], b[3];
-    mmT3(R0, R1, C);
-    for (int k = 0; k < 3; ++k) d01[k] = P1[k] - P0[k];
-    mv3(R0, d01, b);
-    const double v0[3] = {ip0[0], ip0[1], 1.0}, v1[3] = {ip1[0], ip1[1], 1.0};
-    const double n0 = sqrt(v0[0] * v0[0] + v0[1] * v0[1] + v0[2] * v0[2]), n1 = sqrt(v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2]);
-    const double vn0[3] = {v0[0] / n0, v0[1] / n0, v0[2] / n0}, vn1[3] = {v1[0] / n1, v1[1] / n1, v1[2] / n1};
-    double Cvn1[3], A[6], iA[6];
-    mv3(C, vn1, Cvn1);
-    for (int r = 0; r < 3; ++r) { A[2 * r] = vn0[r]; A[2 * r + 1] = -Cvn1[r]; }
-    pinv32(A, iA);
-    const double s0 = iA[0] * b[0] + iA[1] * b[1] + iA[2] * b[2];
-    for (int k = 0; k < 3; ++k) pf[k] = s0 * vn0[k];
 }
 
 __global__ __launch_bounds__(FP_THREADS) void flow_predict_kernel(FlowArgs a, FlowCameras cams)
@@ -108,16 +90,7 @@ __global__ __launch_bounds__(FP_THREADS) void flow_predict_kernel(FlowArgs a, Fl
         const int k = tid - 64;
         if (k >= 0 && k < n_kf) {                              // keyframe k is historyPosition(k - 1)
             const int ip = k == 0 ? POS : CAM + POSE_DIM * (k - 1), io = k == 0 ? ORI : CAM + POSE_DIM * (k - 1) + 3;
-            const double *T = a.tri_imu_to_cam;
-            const double Ric[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]}, base[3] = {T[3], T[7], T[11]};
-            const double q[4] = {m[io], m[io + 1], m[io + 2], m[io + 3]};
-            double Rw[9], dRw[36], R[9], t3[3];
-            quat2rmat_d(q, Rw, dRw);
-            mm3(Ric, Rw, R);
-            mTv3(R, base, t3);
-            double *o = s_pose + k * POSE_WORDS;
-            for (int j = 0; j < 3; ++j) o[j] = m[ip + j] - t3[j];
-            for (int j = 0; j < 9; ++j) o[3 + j] = R[j];
+            camera_pose_pR(m, ip, io, a.tri_imu_to_cam, s_pose + k * POSE_WORDS);
         }
         // ---- phase 2: the columns and the rows ----
         for (int c = tid; c < M; c += FP_THREADS) {

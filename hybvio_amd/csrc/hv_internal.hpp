@@ -272,6 +272,7 @@ bool vu_fused_supported(const Ctx *c, int n_state, int np, int stereo, int batch
 // trail_index.hip: the HV_ERR_INVALID checks of hv_trail_index_params / hv_trail_index, shared with flow_predict.hip
 int trail_check_params(const hv_trail_index_params *p, int n_sets);
 int trail_check_state(const hv_trail_index *t);
+int trail_check_limits(const hv_trail_index_params *p, int n_sets);   // the HV_ERR_UNSUPPORTED limits, fullPointCloud not among them (full_cloud.hip)
 // track_table.hip, ekf_control.hip: the HV_ERR_INVALID checks of hv_track_table (with its parameters) and of hv_ekf_control, shared
 // with session.hip, whose reset writes the same state
 int tracks_check_table(const hv_track_table_params *p, int n_sets, const hv_track_table *t);

@@ -29,7 +29,6 @@ constexpr int TI_MAX = HV_TRACKS_MAX_TRACKS, TI_CHUNKS = TI_MAX / 64;
 constexpr int TI_MAX_POSES = HV_TRAIL_MAX_POSES, TI_MAX_VISITS = HV_TRAIL_MAX_VISITS;
 constexpr int FAILED_UPDATES_THRESHOLD = 5;                     // backend.cpp:1272
 constexpr int GATE_INLIER = 0;                                  // VuOutlierStatus::INLIER
-constexpr int SCORE_BATCH = 4;                                  // older observations loaded together in trackScore
 static_assert(TI_MAX_POSES <= 64 && TI_MAX_VISITS <= 64, "one wavefront over the poses of a track / the candidates of a set");
 
 struct TrailArgs {
@@ -58,13 +57,14 @@ struct TrailArgs {
 struct TrailCameras { hv_camera_model cam0, cam1; };
 
 #include "hv_workgroup.hpp"   // clampi, block_compact, stage_cameras
+#include "trail_phases.hpp"   // trail_track_score, trail_order_phase, trail_filter_skips: shared with full_cloud.hip
 
 // index of the [2] record of (row, column, camera) in the observation arrays, and of the `used` byte
 __device__ inline size_t obs_at(const TrailArgs &a, int set, int row, int col, int cam)
 {
-    return ((((size_t)set * a.K + row) * a.M + col) * a.ncam + cam) * 2;
+    return trail_obs_at(a.K, a.M, a.ncam, set, row, col, cam);
 }
-__device__ inline size_t used_at(const TrailArgs &a, int set, int row, int col) { return ((size_t)set * a.K + row) * a.M + col; }
+__device__ inline size_t used_at(const TrailArgs &a, int set, int row, int col) { return trail_used_at(a.K, a.M, set, row, col); }
 
 __global__ __launch_bounds__(TI_THREADS) void trail_init_kernel(TrailArgs a)
 {
@@ -181,31 +181,8 @@ __global__ __launch_bounds__(TI_THREADS) void trail_select_kernel(TrailArgs a, T
             a.t.norm_velocity[o] = vel0[cam][0]; a.t.norm_velocity[o + 1] = vel0[cam][1];
         }
         a.t.used[used_at(a, set, row0, c)] = 0;
-        float score = 0.0f, prev_x = px[0][0], prev_y = px[0][1];
-        int n_valid = 1;                                        // the head's observation is new, hence not used
-        for (int j0 = 1; j0 < len; j0 += SCORE_BATCH) {         // the loads of a batch first: only the sum is a dependent chain
-            float2 pt[SCORE_BATCH];
-            uint8_t us[SCORE_BATCH];
-#pragma unroll
-            for (int q = 0; q < SCORE_BATCH; ++q) {
-                const int row = s_row[min(j0 + q, len - 1)];
-                pt[q] = *reinterpret_cast<const float2 *>(a.t.image_point + obs_at(a, set, row, c, 0));
-                us[q] = a.t.used[used_at(a, set, row, c)];
-            }
-#pragma unroll
-            for (int q = 0; q < SCORE_BATCH; ++q) {
-                const int j = j0 + q;
-                if (j < len) {
-                    const bool use = a.sampling == HV_TRACK_SAMPLING_ALL || us[q] == 0 || j == len - 1;
-                    if (use) {
-                        ++n_valid;
-                        const double d = __dadd_rn(fabs(__dsub_rn((double)pt[q].x, (double)prev_x)), fabs(__dsub_rn((double)pt[q].y, (double)prev_y)));
-                        score = __double2float_rn(__dadd_rn((double)score, d));
-                    }
-                    prev_x = pt[q].x; prev_y = pt[q].y;
-                }
-            }
-        }
+        int n_valid;                                            // the head's observation is new, hence not used
+        const float score = trail_track_score(a.t, K, M, ncam, a.sampling, s_row, set, c, len, px[0][0], px[0][1], n_valid);
         s_score[i] = score;
         s_old[i] = n_valid;
     }
@@ -217,44 +194,17 @@ __global__ __launch_bounds__(TI_THREADS) void trail_select_kernel(TrailArgs a, T
 
     // ---- trackOrder, the draws, minTrackScore (backend.cpp:976-992) ----
     const int n_ord = block_compact<TI_WAVES>([&](int i) { return s_old[i] >= 0; }, s_list, n, s_chunk);
-    // step k of the shuffle is i = n - 1 - k, so every draw % (i + 1) is known before the chain starts
-    for (int k = tid; k < n_ord - 1; k += TI_THREADS) s_free[k] = (int)(a.draws[(size_t)set * M + k] % (unsigned)(n_ord - k));
-    for (int p = tid; p < n_ord; p += TI_THREADS) s_state[p] = (int)s_score[s_list[p]];   // static_cast<int> (backend.cpp:988)
-    if (tid == 0) s_min = -1;
-    __syncthreads();
-    if (a.score_tracks) {
-        const int mid = n_ord / 2;
-        for (int p = tid; p < n_ord; p += TI_THREADS) {
-            const int v = s_state[p];
-            int less = 0, le = 0;
-            for (int q = 0; q < n_ord; ++q) {
-                const int w = s_state[q];
-                less += w < v; le += w <= v;
-            }
-            if (less <= mid && mid < le) s_min = v;             // every thread that gets here holds the same value
-        }
-    }
-    __syncthreads();
-    // ---- shuffleDeterministic (util.hpp:39-44): the one sequential chain ----
+    const float min_score = trail_order_phase<TI_THREADS>(a.score_tracks, a.draws + (size_t)set * M, n_ord, s_score, s_list, s_free, s_state, &s_min);
     if (tid == 0) {
-        int k = 0;
-        for (int i = n_ord - 1; i > 0; --i) {
-            const int j = s_free[k++];
-            const int tmp = s_list[i]; s_list[i] = s_list[j]; s_list[j] = tmp;
-        }
         a.draws_used[set] = max(n_ord - 1, 0);
         a.t.n_order[set] = n_ord;
     }
-    __syncthreads();
-    const float min_score = a.score_tracks ? (float)s_min : 0.0f;
 
     // ---- the filter of the visit loop (backend.cpp:1017-1046) ----
     for (int p = tid; p < n_ord; p += TI_THREADS) {
         const int slot = s_list[p];
         int st = 2;
-        if (a.score_tracks && s_score[slot] < min_score) st = 0;
-        else if (s_old[slot] < a.min_frames) st = 0;
-        else if (!full) st = 0;
+        if (trail_filter_skips(a.score_tracks, s_score[slot], min_score, s_old[slot], a.min_frames, full)) st = 0;
         else {
             const int id = s_cid[s_col[slot]];
             for (int q = 0; q < n_prev; ++q) if (s_prev[q] == id) { st = 1; break; }
@@ -458,12 +408,13 @@ int check_trail(const hv_trail_index *t)
 }
 
 // after every HV_ERR_INVALID check of the entry: a call that is both invalid and unsupported is reported as invalid
-int check_limits(const hv_trail_index_params *p, int n_sets)
+int check_limits(const hv_trail_index_params *p, int n_sets, bool full_cloud_entry = false)
 {
     if (n_sets > 65535 || p->maxTracks > TI_MAX || p->cameraTrailLength + 1 > TI_MAX_POSES) return HV_ERR_UNSUPPORTED;
     if (p->maxVisualUpdates < 1 || p->maxVisualUpdates > TI_MAX_VISITS) return HV_ERR_UNSUPPORTED;
-    if (p->trackSampling == HV_TRACK_SAMPLING_RANDOM || p->hybridMapSize > 0 || p->useIndependentStereoTriangulation || p->fullPointCloud)
-        return HV_ERR_UNSUPPORTED;
+    if (p->trackSampling == HV_TRACK_SAMPLING_RANDOM || p->hybridMapSize > 0 || p->useIndependentStereoTriangulation) return HV_ERR_UNSUPPORTED;
+    // the three entries of this file state the loop that breaks at its stop; the tail behind it is hv_full_point_cloud_dev's
+    if (p->fullPointCloud && !full_cloud_entry) return HV_ERR_UNSUPPORTED;
     return HV_OK;
 }
 
@@ -479,9 +430,12 @@ void fill_common(TrailArgs &a, const hv_trail_index_params *p, int n_sets, const
 
 }  // namespace
 
-// the HV_ERR_INVALID checks of the parameters and of the state, for flow_predict.hip, which reads the same state (hv_internal.hpp)
+// the HV_ERR_INVALID checks of the parameters and of the state, for flow_predict.hip, output.hip and full_cloud.hip, which read the
+// same state (hv_internal.hpp)
 int trail_check_params(const hv_trail_index_params *p, int n_sets) { return check_params(p, n_sets); }
 int trail_check_state(const hv_trail_index *t) { return check_trail(t); }
+// the HV_ERR_UNSUPPORTED limits of the index for full_cloud.hip, which does not read fullPointCloud: calling it is the switch
+int trail_check_limits(const hv_trail_index_params *p, int n_sets) { return check_limits(p, n_sets, true); }
 
 }  // namespace hv
 

@@ -41,19 +41,7 @@ constexpr int POSE_WORDS = 51;          // p[3] R[9] dR[4][9] baseline[3]
 constexpr int ITER_WORDS = 26;          // C[9] t[3] h[3] E[6] err[2] d[3]
 
 #include "hv_geometry.hpp"   // mm3, mmT3, mv3, mTv3, quat2rmat_d, pinv32: compiled here under this file's contraction mode
-
-__device__ __forceinline__ void pos_ori(int i, int &pos, int &ori)                   // triangulation.cpp:989-998
-{
-    pos = i == 0 ? 0 : 20 + 7 * (i - 1);
-    ori = i == 0 ? 6 : 20 + 7 * (i - 1) + 3;
-}
-
-__device__ __forceinline__ void inverse_depth(const double *p, double *ip, double *dip)   // :1004-1012
-{
-    const double iz = 1 / p[2];
-    ip[0] = p[0] * iz; ip[1] = p[1] * iz; ip[2] = iz;
-    dip[0] = iz; dip[1] = 0; dip[2] = -ip[0] * iz; dip[3] = 0; dip[4] = iz; dip[5] = -ip[1] * iz; dip[6] = 0; dip[7] = 0; dip[8] = -ip[2] * iz;
-}
+#include "hv_triangulation.hpp"   // pos_ori, inverse_depth, inv3sym, norm1_3, gn_observation: shared with full_cloud.hip, likewise
 
 // derivative of the pseudo-inverse of the full-rank 3x2 A (Golub & Pereyra 4.12, triangulation.cpp:31-52)
 __device__ void dpinv(const double *A, const double *iA, const double *dA, double *out)
@@ -78,23 +66,6 @@ __device__ void dpinv(const double *A, const double *iA, const double *dA, doubl
         for (int k = 0; k < 3; ++k) s += t23[3 * r + k] * ((k == c ? 1.0 : 0.0) - AiA[3 * k + c]) + t23b[3 * r + k] * iATiA[3 * k + c];
         out[3 * r + c] += s;
     }
-}
-
-__device__ __forceinline__ double inv3sym(const double *M, double *inv)
-{
-    const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
-    const double det = M[0] * c00 + M[1] * c01 + M[2] * c02, id = 1.0 / det;
-    inv[0] = c00 * id; inv[1] = (M[2] * M[7] - M[1] * M[8]) * id; inv[2] = (M[1] * M[5] - M[2] * M[4]) * id;
-    inv[3] = c01 * id; inv[4] = (M[0] * M[8] - M[2] * M[6]) * id; inv[5] = (M[2] * M[3] - M[0] * M[5]) * id;
-    inv[6] = c02 * id; inv[7] = (M[1] * M[6] - M[0] * M[7]) * id; inv[8] = (M[0] * M[4] - M[1] * M[3]) * id;
-    return det;
-}
-__device__ __forceinline__ double norm1_3(const double *M)
-{
-    double best = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) best = fmax(best, fabs(M[c]) + fabs(M[3 + c]) + fabs(M[6 + c]));
-    return best;
 }
 
 // One (pose, column) pair of the derivative sums (triangulation.cpp:264-311): given dh (the change of h), dC and dt
@@ -634,22 +605,11 @@ __device__ __forceinline__ void vu_prepare_body(const VuPrepareArgs &a, const in
 #pragma unroll
                     for (int k = 0; k < 3; ++k) d[k] = p0[k] - cur[k];
                     mv3(cur + 3, d, t);
-                    const double pfiab[3] = {pfi[0], pfi[1], 1.0};
-                    mv3(C, pfiab, h);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) h[k] += pfi[2] * t[k];
-                    const double ih2 = 1.0 / h[2], ih2sq = ih2 * ih2;
+                    gn_observation(C, t, pfi, s_feat + 4 * tid, h, o + 15, o + 21);
 #pragma unroll
                     for (int k = 0; k < 9; ++k) o[k] = C[k];
 #pragma unroll
                     for (int k = 0; k < 3; ++k) { o[9 + k] = t[k]; o[12 + k] = h[k]; o[23 + k] = d[k]; }
-#pragma unroll
-                    for (int r = 0; r < 2; ++r) {
-#pragma unroll
-                        for (int c = 0; c < 2; ++c) o[15 + 3 * r + c] = -ih2 * C[3 * r + c] + h[r] * ih2sq * C[6 + c];
-                        o[15 + 3 * r + 2] = -t[r] * ih2 + h[r] * ih2sq * t[2];
-                        o[21 + r] = s_feat[4 * tid + r] - h[r] * ih2;
-                    }
                 }
                 __syncthreads();
                 if (it < 6) VU_STAMP(4 + 4 * it);
@@ -1282,23 +1242,11 @@ __device__ __forceinline__ void vu_tri_body(const VuPrepareArgs &a, const int b)
 #pragma unroll
             for (int k = 0; k < 3; ++k) d[k] = p0[k] - cur[k];
             mv3(cur + 3, d, t);
-            const double pfiab[3] = {pfi[0], pfi[1], 1.0};
-            mv3(C, pfiab, h);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) h[k] += pfi[2] * t[k];
-            const double ih2 = 1.0 / h[2], ih2sq = ih2 * ih2;
+            o[26] = gn_observation(C, t, pfi, s_feat + 4 * tid, h, o + 15, o + 21);
 #pragma unroll
             for (int k = 0; k < 9; ++k) o[k] = C[k];
 #pragma unroll
             for (int k = 0; k < 3; ++k) { o[9 + k] = t[k]; o[12 + k] = h[k]; o[23 + k] = d[k]; }
-            o[26] = ih2;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-#pragma unroll
-                for (int c = 0; c < 2; ++c) o[15 + 3 * r + c] = -ih2 * C[3 * r + c] + h[r] * ih2sq * C[6 + c];
-                o[15 + 3 * r + 2] = -t[r] * ih2 + h[r] * ih2sq * t[2];
-                o[21 + r] = s_feat[4 * tid + r] - h[r] * ih2;
-            }
         }
         sync();
         TRI_IT_STAMP(1);

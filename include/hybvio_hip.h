@@ -915,7 +915,9 @@ int hv_ekf_frame_control_dev(hv_ekf *ekf, const hv_ekf_control_params *p, const 
  * constructor asserts), a strided stride < 1 with a strided part, a trackSampling that is no TrackSampling; then
  * HV_ERR_UNSUPPORTED for n_sets > 65535, maxTracks > HV_TRACKS_MAX_TRACKS, maxSize > HV_TRAIL_MAX_POSES, maxVisualUpdates
  * outside 1 .. HV_TRAIL_MAX_VISITS, TrackSampling::RANDOM (its draws depend on the visit outcomes), hybridMapSize > 0,
- * useIndependentStereoTriangulation and fullPointCloud. Counts read from device memory are clamped to their capacity. */
+ * useIndependentStereoTriangulation and fullPointCloud = 1: these entries state the loop that breaks at its stop; the tracks
+ * behind the stop are hv_full_point_cloud_dev's (below), which a caller runs between the visit loop and finish, with
+ * fullPointCloud left 0 here. Counts read from device memory are clamped to their capacity. */
 #define HV_TRAIL_MAX_POSES 64
 #define HV_TRAIL_MAX_VISITS 64
 enum { HV_TRACK_SAMPLING_GAP = 0, HV_TRACK_SAMPLING_ALL = 1, HV_TRACK_SAMPLING_RANDOM = 2 };
@@ -936,7 +938,7 @@ typedef struct hv_trail_index_params {
     int maxTracks;                          /* 200 */
     int hybridMapSize;                      /* 0; > 0 unsupported */
     int useIndependentStereoTriangulation;  /* 0; unsupported */
-    int fullPointCloud;                     /* 0; unsupported */
+    int fullPointCloud;                     /* 0; 1 is refused here: call hv_full_point_cloud_dev */
 } hv_trail_index_params;
 void hv_trail_index_default_params(hv_trail_index_params *p);
 /* K = maxSize, M = maxTracks, C = useStereo ? 2 : 1, V = maxVisualUpdates; set s at s * (the size of one set) of every array. */
@@ -1194,8 +1196,9 @@ int hv_session_reset_dev(hv_ekf *ekf, const hv_session_params *p, const hv_sessi
  * - api_pose [7] and api_trail_pose[i] [7]: convertOutputPose of the transformed inertial pose and of trail_pose[i], with the
  *   reference's inverted test: a non-identity imuToOutput passes the pose through, the identity sends it through
  *   toWorldToCamera / toOdometryPose, so the orientation carries rmat2quat's sign, not the filter's.
- * A non-finite mean gives whatever this arithmetic yields in its own set and touches no other. fullPointCloud, the hybrid map and
- * the stereo-depth cloud are unsupported, like in the index; SLAM itself is the caller's (setCoordinates supplies the matrices).
+ * A non-finite mean gives whatever this arithmetic yields in its own set and touches no other. The cloud of fullPointCloud -- this
+ * one, the stopping candidate and every remaining track -- is hv_full_point_cloud_dev's (below); the hybrid map and the stereo-depth
+ * cloud are unsupported, like in the index; SLAM itself is the caller's (setCoordinates supplies the matrices).
  * One launch of one wavefront per set on the filter's context stream, timed under HV_K_EKF_CONTROL, no allocation, copy-back or
  * synchronisation inside (capturable in a HIP graph). Checks, the first two groups decided before the handle is looked at:
  * HV_ERR_INVALID for a NULL required pointer (p, st and its first_sample_t / time, trail and every member, in and its members
@@ -1250,10 +1253,84 @@ typedef struct hv_output {
 int hv_output_dev(hv_ekf *ekf, const hv_output_params *p, const hv_session *st, const hv_trail_index *trail,
                   const hv_output_frame *in, const hv_output *out);
 
+/* ---- device full point cloud: triangulate every remaining track of a frame (added within ABI 4) ----
+ * odometry.fullPointCloud ("triangulate all tracks on each frame to get the full point cloud", codegen/parameter_definitions.c:
+ * 54-56) for the hv_ekf_batch(ekf) resident sequences of a filter batch (set s is filter s). With it the visit loop of
+ * Session::trackerVisualUpdate (backend.cpp:1012-1252) does not break where its limits set needMoreVisualUpdates = false
+ * (:1242-1247). Calling this entry is the switch: the fullPointCloud field of tp is not read, and hv_trail_*_batch_dev and
+ * hv_output_dev keep stating the loop that breaks. Literal restatement: tests/full_cloud_restatement.py.
+ * Position in a frame: behind hv_ekf_visual_frame_ragged_dev, in front of hv_trail_finish_batch_dev and the augmentation: the
+ * index is as select left it (the head is keyframe 0 and holds this frame's corners, the `used` marks and the previous blacklist
+ * are last frame's, the pose indices match the mean). The entry only reads the filter, the index and the table. Per set:
+ * - the prefix: the candidates in visit order under the stop rule of hv_trail_finish_batch_dev / hv_output_dev; every visited
+ *   candidate up to AND INCLUDING the stopping one (its push at :1249-1251 is no longer behind a break) whose triangulation status
+ *   is HV_TRI_OK is appended with its ID, point_status 4 (OUTLIER) when its prepare status is HV_PREPARE_VU_OK and its gate status
+ *   is not INLIER, else 1 (POSE_TRAIL), point_first_pixel = image_point of its column, first camera, keyframe 0, and point_xyz =
+ *   odometryToSlam applied to pf_dev;
+ * - the tail: every track behind the stop in the shuffled trackOrder -- derived again from the table, the index and draws_dev by
+ *   the rules of select -- that passes the filter of :1017-1038: skipped when scoreVisualUpdateTracks and score < minTrackScore,
+ *   then when nValid < trackMinFrames, then on a frame that is not a full update. The previous-blacklist test (:1039-1046) is
+ *   conditioned on needMoreVisualUpdates: a track blacklisted in the previous frame is triangulated and not blacklisted again
+ *   (hv_trail_finish_batch_dev agrees: a skipped track enters the new blacklist only when its position precedes the stop);
+ * - each tail track: createTrackIndex (GAP or ALL) as tail_pose_mask, buildTrackVectors read in place from norm_point,
+ *   extractCameraPoseTrail (triangulation.cpp:65-103) from the current mean through imuToCamera / secondImuToCamera of vp,
+ *   Triangulator::triangulate (:120-407), the iterative method without derivatives -- triangulateWithTwoCameras between pose 0
+ *   and the last pose of the first camera, inverseDepth, Gauss-Newton with the 3 x 3 solve and its rcond, the convergence test,
+ *   the way back, pf == p0, isBehind -- then the depth window of backend.cpp:1096-1099 from vp; tail_status is the
+ *   TriangulatorStatus after that window (the reference's triangulationForPointCloud statistics); an OK track is appended behind
+ *   the prefix in tail order with status POSE_TRAIL (:1126-1132). pf and the status do not depend on calculateDerivatives;
+ * - n_attempts = the visits the loop counted + n_tail (:1121) and good_frame = (stationary || stopped) && !(n_attempts -
+ *   successes > 5) (:1272-1274), the reference's values WITH fullPointCloud: the tail's attempts make tooManyFailures true on
+ *   almost every frame with more than a handful of tail tracks. hv_trail_finish_batch_dev reports the values without the tail;
+ *   the caller decides which one feeds hv_session_status_dev;
+ * - a loop that never stopped has no tail: the cloud is the one hv_output_dev reports; a set that is not ready has n_points = 0
+ *   (getPointCloud, :255-280), its tail and counters are still reported. Entries behind n_points / n_tail are not written.
+ * Nothing is gated, applied, marked used, blacklisted or deleted; mean, covariance, index and table are not written.
+ * Two launches, one workgroup per set each, on the filter's context stream: the index kernel, timed under HV_K_TRAIL_INDEX, and
+ * the triangulation kernel, one lane per tail track, timed under HV_K_VU_TRI; no allocation, copy-back or synchronisation inside
+ * (capturable in a HIP graph). Checks, in this order: HV_ERR_INVALID for the parameter errors of hv_trail_*_batch_dev, a NULL
+ * required pointer (tp, vp, trail and every member, table and its n_tracks / ids, in and its members but full_update_dev,
+ * stationary_dev, odometry_to_slam_dev and ready_dev, out and every member but n_attempts and good_frame) or a useStereo that
+ * differs between tp and vp; HV_ERR_UNSUPPORTED for the index's limits (maxTracks > HV_TRACKS_MAX_TRACKS, maxSize >
+ * HV_TRAIL_MAX_POSES, maxVisualUpdates outside 1 .. HV_TRAIL_MAX_VISITS, TrackSampling::RANDOM, hybridMapSize > 0,
+ * useIndependentStereoTriangulation) and for useLinearTriangulation (the tail states the iterative method only: the closed form
+ * has no Gauss-Newton loop to share with it, and the visit loop's own linear front carries derivatives the cloud never reads);
+ * HV_ERR_INVALID for a NULL handle; HV_ERR_UNSUPPORTED for more than 65535 sets or a state shorter than 20 + 7 *
+ * cameraTrailLength. Counts and indices read from device memory (n_tracks, n_keyframes, n_candidates, kf_row, col_len, cand_col,
+ * cand_pos, and the entry's own n_tail / tail_col between its two kernels) are clamped to their capacity. */
+typedef struct hv_full_cloud_frame {      /* device memory; V = maxVisualUpdates, M = maxTracks */
+    const uint32_t *draws_dev;            /* [n_sets][M]      as given to hv_trail_select_batch_dev */
+    const uint8_t  *full_update_dev;      /* [n_sets]         as given to select; NULL: every frame is full */
+    const int32_t  *cand_id_dev;          /* [V][n_sets]      hv_trail_select_batch_dev */
+    const int32_t  *n_candidates_dev;     /* [n_sets] */
+    const int32_t  *status_dev;           /* [V][n_sets][2]   hv_ekf_visual_frame_ragged_dev */
+    const int32_t  *gate_status_dev;      /* [V][n_sets] */
+    const double   *pf_dev;               /* [V][n_sets][3] */
+    const uint8_t  *stationary_dev;       /* [n_sets]         stationary_dev of hv_ekf_frame_control_dev; NULL: 0 */
+    const double   *odometry_to_slam_dev; /* [n_sets][16]     row-major, slam.inverse() * odo (backend.cpp:62); NULL: identity */
+    const uint8_t  *ready_dev;            /* [n_sets]         isReady(); NULL: ready */
+} hv_full_cloud_frame;
+typedef struct hv_full_cloud {            /* device memory owned by the caller; [n_sets] unless noted */
+    int32_t  *n_points;
+    int32_t  *point_id;           /* [n_sets][M]     the visited prefix with the stopping candidate, then the tail's OK tracks */
+    int32_t  *point_status;       /* [n_sets][M]     PointFeature::Status: 1 POSE_TRAIL, 4 OUTLIER */
+    float    *point_first_pixel;  /* [n_sets][M][2] */
+    double   *point_xyz;          /* [n_sets][M][3] */
+    int32_t  *n_tail;
+    int32_t  *tail_id;            /* [n_sets][M]     the tail in trackOrder order */
+    int32_t  *tail_status;        /* [n_sets][M]     TriangulatorStatus after the depth window */
+    int32_t  *tail_col;           /* [n_sets][M]     the track's column of the index */
+    uint64_t *tail_pose_mask;     /* [n_sets][M]     bit k = keyframe k is in poseTrailIndex */
+    int32_t  *n_attempts;         /* optional: updateAttemptCount with the tail */
+    uint8_t  *good_frame;         /* optional: goodFrame with the tail */
+} hv_full_cloud;
+int hv_full_point_cloud_dev(hv_ekf *ekf, const hv_trail_index_params *tp, const hv_vu_params *vp, const hv_trail_index *trail,
+                            const hv_track_table *table, const hv_full_cloud_frame *in, const hv_full_cloud *out);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
-       HV_K_VU_TRI = 11 /* r06: the triangulation front of the split form (vu_tri_kernel); HV_K_VU_PREPARE then times the record-fed gates */,
+       HV_K_VU_TRI = 11 /* r06: the triangulation front of the split form (vu_tri_kernel); HV_K_VU_PREPARE then times the record-fed gates; also the tail kernel of hv_full_point_cloud_dev */,
        HV_K_SUBPIX = 12 /* added within ABI 4: hv_corner_subpix* */,
        HV_K_RANSAC5 = 13 /* added within ABI 4: hv_ransac5*, hv_hybrid_ransac_lk_batch_dev */,
        HV_K_STEREO_GATE = 14 /* added within ABI 4: hv_flow_status_batch_dev, hv_track_gate*, hv_detection_filter* */,
@@ -1261,7 +1338,7 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3* */,
        HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev, hv_session_*_dev, hv_output_dev */,
-       HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev */,
+       HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev, the index kernel of hv_full_point_cloud_dev */,
        HV_K_COUNT = 20 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
