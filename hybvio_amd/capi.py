@@ -33,8 +33,11 @@ HV_MAX_LEVELS = 6
  K_SUBPIX, K_RANSAC5, K_STEREO_GATE, K_DETECT_TAIL, K_TRACK_TABLE, K_RANSAC3, K_EKF_CONTROL, K_TRAIL_INDEX) = range(20)
 RANSAC5_MAX_ITERS = 75
 RANSAC3_MAX_ITERS = 500
+UPRIGHT2P_MAX_ITERS = 500
 # RansacResult::Type as reported by hv_ransac3_lk_batch_dev
 R3_TYPE_SKIPPED, R3_TYPE_R3 = 0, 2
+# RansacResult::Type as reported by hv_upright2p_lk_batch_dev
+U2_TYPE_SKIPPED, U2_TYPE_UPRIGHT_2P = 0, 4
 # RansacResult::Type as reported by hv_hybrid_ransac_lk_batch_dev
 R5_TYPE_SKIPPED, R5_TYPE_R2, R5_TYPE_R5 = 0, 1, 3
 SUBPIX_MAX_WIN = 16
@@ -84,6 +87,12 @@ class Ransac5Params(C.Structure):
 class Ransac3Params(C.Structure):
     _fields_ = [("ransac3ErrorThresh", C.c_double), ("ransac3FailureProbability", C.c_double), ("ransac3MaxIterations", C.c_int),
                 ("ransac3MinIterations", C.c_int), ("ransac3UseMle", C.c_int), ("ransacMinInlierFraction", C.c_double)]
+
+
+class Upright2pParams(C.Structure):
+    _fields_ = [("ransacStereoUpright2pErrorThresh", C.c_double), ("ransacStereoUpright2pFailureProbability", C.c_double),
+                ("ransacStereoUpright2pMaxIterations", C.c_int), ("ransacStereoUpright2pMinIterations", C.c_int),
+                ("ransacStereoUpright2pUseMle", C.c_int), ("ransacMinInlierFraction", C.c_double)]
 
 
 class StereoGateParams(C.Structure):
@@ -321,6 +330,10 @@ PROTOTYPES = {
                                             C.POINTER(TrackTable), C.c_void_p, C.c_void_p] + [C.c_void_p] * 13),
     "hv_trail_finish_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(TrailIndexParams), C.c_int, C.POINTER(TrailIndexTable)]
                                   + [C.c_void_p] * 11),
+    "hv_upright2p_default_params": (None, [C.POINTER(Upright2pParams)]),
+    "hv_upright2p": (C.c_int, [C.c_void_p, C.POINTER(Upright2pParams), C.c_int] + [C.c_void_p] * 11),
+    "hv_upright2p_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Upright2pParams), C.c_int, C.c_int] + [C.c_void_p] * 12),
+    "hv_upright2p_lk_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(Upright2pParams), C.POINTER(FlowPredictParams), C.c_int] + [C.c_void_p] * 14),
     "hv_flow_predict_default_params": (None, [C.POINTER(FlowPredictParams)]),
     "hv_flow_predict_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(FlowPredictParams), C.c_int, C.POINTER(TrailIndexParams),
                                             C.POINTER(TrailIndexTable), C.POINTER(TrackTable)] + [C.c_void_p] * 5 + [C.c_int]),
@@ -553,6 +566,36 @@ class Context:
                                                 C.byref(cam0), C.byref(cam1), T.ctypes.data_as(C.c_void_p), p(draws_dev),
                                                 p(result_dev), p(score_dev), p(pose_dev), p(summary_dev)),
                   "hv_ransac3_lk_batch_dev")
+
+    # ---- stereo upright 2-point RANSAC (rotation about gravity + translation) ----
+    def upright2p(self, status, prev_left, prev_right, cur_left, cam0: "CameraModel", cam1: "CameraModel", second_to_first, poses,
+                  draws, params: "Upright2pParams" = None):
+        """hv_upright2p (StereoUpright2p::compute): poses = the two camera-to-world 4x4 of the previous and the current frame;
+        returns (new status [n], model [12] = R row-major + t, summary [inliers, best iteration, iterations run,
+        correspondences]); draws = 2 * ransacStereoUpright2pMaxIterations raw std::mt19937 outputs."""
+        rp = params if params is not None else upright2p_default_params()
+        a, b, c = (np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in (prev_left, prev_right, cur_left))
+        st = np.ascontiguousarray(status, np.int32).copy()
+        T = np.ascontiguousarray(second_to_first, np.float64).reshape(16)
+        P = np.ascontiguousarray(poses, np.float64).reshape(32)
+        dr = np.ascontiguousarray(draws, np.uint32).reshape(-1)
+        assert len(a) == len(b) == len(c) == len(st) and len(dr) >= 2 * rp.ransacStereoUpright2pMaxIterations
+        model, sm = np.zeros(12), np.zeros(4, np.int32)
+        vp = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(lib().hv_upright2p(self._h, C.byref(rp), len(a), vp(a), vp(b), vp(c), C.byref(cam0), C.byref(cam1), vp(T), vp(P), vp(dr),
+                                     vp(st), vp(model), vp(sm)), "hv_upright2p")
+        return st, model, sm
+
+    def upright2p_batch_dev(self, n_sets, max_points, n_points_dev, prev_left_dev, prev_right_dev, cur_left_dev, cam0, cam1,
+                            second_to_first, poses_dev, draws_dev, status_dev, model_dev=0, summary_dev=0,
+                            params: "Upright2pParams" = None):
+        rp = params if params is not None else upright2p_default_params()
+        T = np.ascontiguousarray(second_to_first, np.float64).reshape(16)          # (copied by the call: a kernel argument)
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_upright2p_batch_dev(self._h, C.byref(rp), n_sets, max_points, p(n_points_dev), p(prev_left_dev),
+                                               p(prev_right_dev), p(cur_left_dev), C.byref(cam0), C.byref(cam1),
+                                               T.ctypes.data_as(C.c_void_p), p(poses_dev), p(draws_dev), p(status_dev), p(model_dev),
+                                               p(summary_dev)), "hv_upright2p_batch_dev")
 
     # ---- stereo track gate: flow status, epipolar check, crop, blacklist and the detection filter ----
     def flow_status_batch_dev(self, n_sets, max_points, n_points_dev, xy_dev, lk_status_dev, status_dev):
@@ -839,6 +882,14 @@ def gftt_default_params(**over) -> GfttParams:
 def ransac5_default_params(**over) -> Ransac5Params:
     p = Ransac5Params()
     lib().hv_ransac5_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def upright2p_default_params(**over) -> Upright2pParams:
+    p = Upright2pParams()
+    lib().hv_upright2p_default_params(C.byref(p))
     for k, v in over.items():
         setattr(p, k, v)
     return p
@@ -1438,6 +1489,20 @@ class EkfBatch:
                                                   C.c_void_p(c0_dev), C.addressof(cam0), C.addressof(cam1) if cam1 is not None else None,
                                                   C.c_void_p(pred_xy_dev), C.c_void_p(distance_dev), int(bool(reuse_distance))),
                   "hv_flow_predict_batch_dev")
+
+    def upright2p_lk_batch_dev(self, cam_params: "FlowPredictParams", max_points, n_points_dev, prev_left_dev, prev_right_dev,
+                               cur_left_dev, track_status_dev, r2_summary_dev, cam0: "CameraModel", cam1: "CameraModel", second_to_first,
+                               draws_dev, result_dev, score_dev, model_dev=0, summary_dev=0, params: "Upright2pParams" = None):
+        """hv_upright2p_lk_batch_dev: the upright 2-point filter of every filter's sequence (set s is filter s) with the two poses
+        formed on the device from the mean (history pose 0 and the current pose through cam_params.cameraToImu)."""
+        rp = params if params is not None else upright2p_default_params()
+        T = np.ascontiguousarray(second_to_first, np.float64).reshape(16)
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_upright2p_lk_batch_dev(self._h, C.byref(rp), C.byref(cam_params), max_points, p(n_points_dev), p(prev_left_dev),
+                                                  p(prev_right_dev), p(cur_left_dev), p(track_status_dev), p(r2_summary_dev),
+                                                  C.addressof(cam0), C.addressof(cam1), T.ctypes.data_as(C.c_void_p), p(draws_dev),
+                                                  p(result_dev), p(score_dev), p(model_dev), p(summary_dev)),
+                  "hv_upright2p_lk_batch_dev")
 
     def symmetrize(self):
         self._chk(lib().hv_ekf_symmetrize(self._h), "hv_ekf_symmetrize")

@@ -311,6 +311,7 @@ static int init_ctx(Ctx *c, int high_priority)
     if (rc == HV_OK) rc = hv::pyramid_init(c);
     if (rc == HV_OK) rc = hv::ransac5_init(c);
     if (rc == HV_OK) rc = hv::ransac3_init(c);
+    if (rc == HV_OK) rc = hv::upright2p_init(c);
     if (rc == HV_OK) rc = hv::detect_tail_init(c);
     if (rc == HV_OK) rc = hv::ekf_kernels_init(c);
     if (rc == HV_OK) rc = hv::vu_prepare_init(c);

@@ -24,7 +24,7 @@
 namespace hv {
 namespace {
 
-#include "hv_geometry.hpp"    // mm3, mmT3, mv3, mTv3, quat2rmat, quat2rmat_d, pinv32
+#include "hv_geometry.hpp"    // mm3, mmT3, mv3, mTv3, quat2rmat, quat2rmat_d, pinv32, imu_to_world, mm4_entry
 #include "hv_triangulation.hpp"   // camera_pose_pR, triangulate_two
 #include "hv_workgroup.hpp"   // clampi, stage_cameras
 
@@ -77,9 +77,7 @@ __global__ __launch_bounds__(FP_THREADS) void flow_predict_kernel(FlowArgs a, Fl
     if (tid == 0) {
         const int ip = a.pose0_history ? CAM : POS, io = a.pose0_history ? CAM + 3 : ORI;
         double R[9], t[3];
-        quat2rmat(m + io, R);                                  // toCameraToWorld: imuToWorld = [rot' | position]
-        const double i2w[16] = {R[0], R[3], R[6], m[ip], R[1], R[4], R[7], m[ip + 1], R[2], R[5], R[8], m[ip + 2], 0.0, 0.0, 0.0, 1.0};
-        for (int j = 0; j < 16; ++j) s_mat[0][j] = i2w[j];
+        imu_to_world(m, ip, io, s_mat[0]);                     // toCameraToWorld: imuToWorld = [rot' | position]
         quat2rmat(m + ORI, R);                                 // toWorldToCamera: worldToImu = [rot | -rot * position]
         for (int r = 0; r < 3; ++r) t[r] = ((-R[3 * r]) * m[POS] + (-R[3 * r + 1]) * m[POS + 1]) + (-R[3 * r + 2]) * m[POS + 2];
         const double w2i[16] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2], 0.0, 0.0, 0.0, 1.0};
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(FP_THREADS) void flow_predict_kernel(FlowArgs a, Fl
     if (tid < 32) {                                            // camToWorld0 = imuToWorld * cameraToImu, worldToCam1 = imuToCamera * worldToImu
         const int w = tid >> 4, r = (tid >> 2) & 3, c = tid & 3;
         const double *A = s_mat[2 * w], *B = s_mat[2 * w + 1];
-        (w ? s_w2c : s_c2w)[4 * r + c] = ((A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c]) + A[4 * r + 3] * B[12 + c];
+        (w ? s_w2c : s_c2w)[4 * r + c] = mm4_entry(A, B, r, c);
     }
     __syncthreads();
 

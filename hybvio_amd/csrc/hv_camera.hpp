@@ -1,5 +1,5 @@
-// Device camera models shared by the tracker-side kernels (rot_ransac.hip, ransac5.hip, ransac3.hip, stereo_gate.hip, trail_index.hip,
-// flow_predict.hip): tracker::Camera's pixelToRay / rayToPixel (src/tracker/camera.cpp:93-221 pinhole, :264-398 fisheye) and
+// Device camera models shared by the tracker-side kernels (rot_ransac.hip, ransac5.hip, ransac3.hip, upright2p.hip, stereo_gate.hip,
+// trail_index.hip, flow_predict.hip): tracker::Camera's pixelToRay / rayToPixel (src/tracker/camera.cpp:93-221 pinhole, :264-398 fisheye) and
 // normalizePixel (:471-476) in double precision, in the oracle's operation order.
 #pragma once
 

@@ -1,5 +1,5 @@
-// Small binary64 geometry shared by the kernels that read camera poses from the EKF mean (vu_prepare.hip, flow_predict.hip, output.hip)
-// and by the RANSAC kernels (rot_ransac.hip, ransac5.hip, ransac3.hip): 3-vector and 3x3 products, odometry::util::quat2rmat /
+// Small binary64 geometry shared by the kernels that read camera poses from the EKF mean (vu_prepare.hip, flow_predict.hip, output.hip,
+// upright2p.hip) and by the RANSAC kernels (rot_ransac.hip, ransac5.hip, ransac3.hip, upright2p.hip): 3-vector and 3x3 products, odometry::util::quat2rmat /
 // quat2rmat_d (src/odometry/util.cpp:10-47), rmat2quat, the inverse of a general 4x4 and the pseudo-inverse of a full-rank 3x2 matrix
 // (src/odometry/triangulation.cpp:1000-1002). 3x3 and 4x4 matrices are row-major double[9] / double[16] (like
 // oracle/triangulation_oracle.c).
@@ -45,6 +45,20 @@ __device__ __forceinline__ void quat2rmat(const double *q, double *R)           
     R[0] = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3]; R[1] = 2 * q[1] * q[2] - 2 * q[0] * q[3]; R[2] = 2 * q[1] * q[3] + 2 * q[0] * q[2];
     R[3] = 2 * q[1] * q[2] + 2 * q[0] * q[3]; R[4] = q[0] * q[0] - q[1] * q[1] + q[2] * q[2] - q[3] * q[3]; R[5] = 2 * q[2] * q[3] - 2 * q[0] * q[1];
     R[6] = 2 * q[1] * q[3] - 2 * q[0] * q[2]; R[7] = 2 * q[2] * q[3] + 2 * q[0] * q[1]; R[8] = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
+}
+// odometry::util::toCameraToWorld (util.cpp:144-158) in its two factors, shared by flow_predict.hip and upright2p.hip: imuToWorld =
+// [rot' | position] of the pose at m[ip], m[io] (row-major 4x4), and one entry of the product imuToWorld * cameraToImu with the four
+// terms added left to right (the caller supplies cameraToImu: Eigen's inverse is not restated)
+[[maybe_unused]] __device__ inline void imu_to_world(const double *m, int ip, int io, double *out)
+{
+    double R[9];
+    quat2rmat(m + io, R);
+    const double i2w[16] = {R[0], R[3], R[6], m[ip], R[1], R[4], R[7], m[ip + 1], R[2], R[5], R[8], m[ip + 2], 0.0, 0.0, 0.0, 1.0};
+    for (int j = 0; j < 16; ++j) out[j] = i2w[j];
+}
+[[maybe_unused]] __device__ __forceinline__ double mm4_entry(const double *A, const double *B, int r, int c)
+{
+    return ((A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c]) + A[4 * r + 3] * B[12 + c];
 }
 [[maybe_unused]] __device__ void quat2rmat_d(const double *q, double *R, double *dR /* [4][9] */)    // util.cpp:10-47: R as above
 {

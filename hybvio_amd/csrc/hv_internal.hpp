@@ -251,6 +251,7 @@ template <class K> inline hipError_t set_lds_limit(K kernel, size_t bytes)      
 }
 int ransac5_init(Ctx *c);              // ransac5.hip: the kernel's dynamic-LDS limit, set once per context
 int ransac3_init(Ctx *c);              // ransac3.hip: likewise
+int upright2p_init(Ctx *c);            // upright2p.hip: likewise
 int detect_tail_init(Ctx *c);         // detect_tail.hip: likewise
 int pyramid_init(Ctx *c);             // pyramid.hip: likewise
 int ekf_kernels_init(Ctx *c);         // ekf.hip: likewise, every EKF kernel that carves dynamic LDS (lds_layout.hpp), through ...

@@ -1,4 +1,4 @@
-// Dynamic-LDS layouts of the two tracker-side RANSAC kernels (ransac5.hip, ransac3.hip), written once in the idiom of lds_layout.hpp:
+// Dynamic-LDS layouts of the tracker-side RANSAC kernels (ransac5.hip, ransac3.hip, upright2p.hip), written once in the idiom of lds_layout.hpp:
 // the launcher and the *_init function take the byte count, and the kernel carves its pointers, from the same description. Offsets are
 // in BYTES from the base of the dynamic region, doubles first, then ints. Plain C++, no HIP header (tests/cpp/test_lds_layout.cpp).
 #pragma once
@@ -45,6 +45,25 @@ HV_HD constexpr Ransac3Lds ransac3_lds(int max_points)
     return Ransac3Lds{c.doubles(mp), c.doubles(mp), c.doubles(mp), c.doubles(mp), c.doubles(mp), c.doubles(R3_THREADS * 12),
                       c.doubles(R3_THREADS), c.doubles(12), c.ints(mp), c.ints(mp), c.ints(mp), c.ints(mp), c.ints((mp + 63) / 64 + 1),
                       c.ints(3 * R3_CHUNK), c.ints(3 * R3_CHUNK), c.ints(R3_THREADS), c.ints(16), c.at};
+}
+
+// ---- upright2p_kernel ----
+constexpr int U2_THREADS = 256, U2_WAVES = U2_THREADS / 64;
+constexpr int U2_CHUNK = 128;                      // iterations per round; U2_CHUNK * 2 roots = one lane each (solver and cost phase)
+static_assert(U2_CHUNK * 2 == U2_THREADS, "one lane per (hypothesis, root)");
+constexpr int U2_MODEL = 5;                        // a model: c, s of the rotation about z, then t
+// mx .. mz, rx .. rz, nu, nv [max_points]: rotated model points, rotated rays, normalised rays; mod [U2_THREADS][U2_MODEL];
+// cost [U2_THREADS]; best [U2_MODEL]; rot [2][9]: R0, R1; map: tracked k -> feature; vmap: valid j -> tracked k; st, idx [max_points];
+// chunk: block_compact's scratch; pair [U2_CHUNK][2]; draw [U2_CHUNK][2] (unsigned); cnt [U2_THREADS]: inlier count, -1 = no model; ctl [16]
+struct Upright2pLds { size_t mx, my, mz, rx, ry, rz, nu, nv, mod, cost, best, rot, map, vmap, st, idx, chunk, pair, draw, cnt, ctl, end; };
+HV_HD constexpr Upright2pLds upright2p_lds(int max_points)
+{
+    const size_t mp = (size_t)max_points;
+    LdsCursor c;
+    return Upright2pLds{c.doubles(mp), c.doubles(mp), c.doubles(mp), c.doubles(mp), c.doubles(mp), c.doubles(mp), c.doubles(mp),
+                        c.doubles(mp), c.doubles(U2_THREADS * U2_MODEL), c.doubles(U2_THREADS), c.doubles(U2_MODEL), c.doubles(18),
+                        c.ints(mp), c.ints(mp), c.ints(mp), c.ints(mp), c.ints((mp + 63) / 64 + 1), c.ints(2 * U2_CHUNK),
+                        c.ints(2 * U2_CHUNK), c.ints(U2_THREADS), c.ints(16), c.at};
 }
 
 }  // namespace hv

@@ -257,12 +257,14 @@ std::unique_ptr<rot_ransac::RotRansac> rot_ransac::RotRansac::buildHip(Session &
 }
 
 namespace {
-// Counterpart of RansacPipelineImplementation (src/tracker/ransac_pipeline.cpp:43-151) on its RANSAC2, hybrid and RANSAC3 paths.
+// Counterpart of RansacPipelineImplementation (src/tracker/ransac_pipeline.cpp:43-151) on its RANSAC2, hybrid, RANSAC3 and upright 2-point paths.
 class HipRansacPipeline : public RansacPipeline {
     Session &session;
     const RansacPipelineParameters parameters;
-    std::mt19937 rng, rng3;                                                  // :66, :78
+    std::mt19937 rng, rng3, rngUpright;                                      // :66, :78, stereo_upright_2p.cpp:101
     const bool stereo;                                                       // built with secondToFirstCamera
+    const bool upright;                                                      // built by buildHipUpright2p
+    hv_upright2p_params upright2p{};
     std::array<double, 16> secondToFirstCamera{};
     std::unique_ptr<rot_ransac::RotRansac> rotRansac;
     RansacResult ransacResult, ransac2Result, ransac5Result;
@@ -345,6 +347,33 @@ class HipRansacPipeline : public RansacPipeline {
         return true;
     }
 
+    bool doUpright2p(const std::vector<std::array<const hv_camera_model *, 2>> &cameras,
+                     const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners, const double *poses,
+                     std::vector<Feature::Status> &trackStatus) {          // stereo_upright_2p.cpp:110-183
+        const std::size_t n = corners[0][0]->size();
+        assert(corners[1][0]->size() == n && corners[0][1]->size() == n && trackStatus.size() == n);
+        initialize(ransacResult, n);
+        status3.resize(n);
+        for (std::size_t i = 0; i < n; ++i) status3[i] = static_cast<int>(trackStatus[i]);
+        // the next 2 * maxIterations raw outputs of a COPY of the generator; the real one advances by what the loop consumed
+        std::mt19937 ahead = rngUpright;
+        draws3.resize(2 * static_cast<std::size_t>(upright2p.ransacStereoUpright2pMaxIterations));
+        for (auto &d : draws3) d = static_cast<std::uint32_t>(ahead());
+        int summary[4];
+        static_assert(sizeof(Feature::Point) == 2 * sizeof(float), "Point must be two packed floats");
+        auto xy = [](const std::vector<Feature::Point> *v) { return reinterpret_cast<const float *>(v->data()); };
+        session.check(hv_upright2p(session.ctx(), &upright2p, static_cast<int>(n), xy(corners[0][0]), xy(corners[1][0]),
+                                   xy(corners[0][1]), cameras[0][0], cameras[1][0], secondToFirstCamera.data(), poses, draws3.data(),
+                                   status3.data(), nullptr, summary),
+                      "hv_upright2p");
+        rngUpright.discard(2ull * static_cast<unsigned long long>(summary[2]));
+        for (std::size_t i = 0; i < n; ++i) trackStatus[i] = static_cast<Feature::Status>(status3[i]);
+        if (summary[3] < 2 || summary[1] < 0) return false;                  // :161-163, 172-174
+        ransacResult.inlierCount = static_cast<std::size_t>(summary[0]);
+        ransacResult.type = RansacResult::Type::UPRIGHT_2P;
+        return true;
+    }
+
     void computeHybridRansac(const hv_camera_model &camera1, const hv_camera_model &camera2, bool ransac2Done) {   // :158-195
         const auto &p = parameters.ransac5;
         const std::size_t n = c1.size();
@@ -363,16 +392,18 @@ class HipRansacPipeline : public RansacPipeline {
     }
 
 public:
-    HipRansacPipeline(Session &s, int width, int height, const RansacPipelineParameters &p, const std::array<double, 16> *secondToFirst)
-        : session(s), parameters(p), rng(p.ransacRngSeed), rng3(p.ransacRngSeed), stereo(secondToFirst != nullptr),
-          rotRansac(rot_ransac::RotRansac::buildHip(s)) {
+    HipRansacPipeline(Session &s, int width, int height, const RansacPipelineParameters &p, const std::array<double, 16> *secondToFirst,
+                      const hv_upright2p_params *up = nullptr)
+        : session(s), parameters(p), rng(p.ransacRngSeed), rng3(p.ransacRngSeed), rngUpright(p.ransacRngSeed),
+          stereo(secondToFirst != nullptr), upright(up != nullptr), rotRansac(rot_ransac::RotRansac::buildHip(s)) {
         if (secondToFirst) secondToFirstCamera = *secondToFirst;
+        if (up) upright2p = *up;
         const double su = std::min(height, width) / 720.0;                   // :91-93
         rotRansac->threshold_pow2 = static_cast<float>(std::pow(p.ransac2Threshold * su, 2));
     }
 
     double compute(const std::vector<std::array<const hv_camera_model *, 2>> &cameras,
-                   const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners, const void *,
+                   const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners, const void *poses,
                    std::vector<Feature::Status> &trackStatus) final {
         assert(!cameras.empty() && !corners.empty());
         c1.clear();
@@ -386,6 +417,8 @@ public:
         const bool ransac2Done = doRansac2(*cameras[0][0], *cameras[0][1]);
         if (stereo && parameters.useRansac3 && cameras.size() >= 2 && corners.size() >= 2) {   // :121-123
             doRansac3(cameras, corners, trackStatus);
+        } else if (upright && parameters.useStereoUpright2p && cameras.size() >= 2 && corners.size() >= 2 && poses) {   // :124-127
+            doUpright2p(cameras, corners, static_cast<const double *>(poses), trackStatus);
         } else if (parameters.useHybridRansac) {
             computeHybridRansac(*cameras[0][0], *cameras[0][1], ransac2Done);
             if (ransacResult.type != RansacResult::Type::SKIPPED) updateTrackStatus(ransacResult, trackStatus);
@@ -408,7 +441,7 @@ std::unique_ptr<RansacPipeline> RansacPipeline::buildHip(Session &s, int width, 
         throw std::invalid_argument("RansacPipeline::buildHip: tracker.useRansac3 needs the stereo transform: call the overload that "
                                     "takes secondToFirstCamera, or set useRansac3 false to use the hybrid RANSAC2 / RANSAC5 path");
     if (p.useStereoUpright2p)
-        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useStereoUpright2p is not implemented on the device");
+        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useStereoUpright2p needs the stereo transform and the upright parameters: call buildHipUpright2p");
     return std::unique_ptr<RansacPipeline>(new HipRansacPipeline(s, width, height, p, nullptr));
 }
 
@@ -416,8 +449,15 @@ std::unique_ptr<RansacPipeline> RansacPipeline::buildHip(Session &s, int width, 
                                                          const std::array<double, 16> &secondToFirstCamera)
 {
     if (p.useStereoUpright2p)
-        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useStereoUpright2p is not implemented on the device");
+        throw std::invalid_argument("RansacPipeline::buildHip: tracker.useStereoUpright2p needs the upright parameters: call buildHipUpright2p");
     return std::unique_ptr<RansacPipeline>(new HipRansacPipeline(s, width, height, p, &secondToFirstCamera));
+}
+
+std::unique_ptr<RansacPipeline> RansacPipeline::buildHipUpright2p(Session &s, int width, int height, const RansacPipelineParameters &p,
+                                                                  const std::array<double, 16> &secondToFirstCamera,
+                                                                  const hv_upright2p_params &upright2p)
+{
+    return std::unique_ptr<RansacPipeline>(new HipRansacPipeline(s, width, height, p, &secondToFirstCamera, &upright2p));
 }
 
 namespace {

@@ -244,7 +244,7 @@ struct RansacResult {
 struct RansacPipelineParameters {
     bool useHybridRansac = true;
     bool useRansac3 = true;                  // the reference's default; needs the buildHip overload with the stereo transform
-    bool useStereoUpright2p = false;         // refused by both overloads
+    bool useStereoUpright2p = false;         // refused by the two buildHip overloads; served by buildHipUpright2p
     double ransac2Threshold = 4.0;
     unsigned ransacRngSeed = 4649;
     hv_ransac5_params ransac5{0.999, 2.0, 75, 0.9, 0.3, 0.9};
@@ -265,6 +265,13 @@ struct RansacPipelineParameters {
 // current-left corner is normalised with cameras[0][0] where the reference uses cameras[0][1] (:248): the same model in both
 // frames, as the tracker always passes it. RANSAC3 draws from its own std::mt19937(ransacRngSeed)
 // (:78), advanced by three draws per iteration run. It still refuses useStereoUpright2p.
+// buildHipUpright2p takes the stereo transform and the parameters of the upright 2-point filter (hv_upright2p_params,
+// codegen/parameter_definitions.c:299-303) and accepts useStereoUpright2p. compute() then follows :121-128: RANSAC3 first if
+// useRansac3; else the upright branch (StereoUpright2p::compute, src/tracker/stereo_upright_2p.cpp:110-183, through hv_upright2p)
+// when cameras.size() >= 2 && corners.size() >= 2 && poses; else hybrid. poses points at two row-major 4x4 doubles, the
+// camera-to-world matrices of the previous and the current frame (backend.cpp:667-679); null falls through to the hybrid
+// branch. The filter draws from its own std::mt19937(ransacRngSeed) (stereo_upright_2p.cpp:101), advanced by two draws per
+// iteration run; lastResult().type is UPRIGHT_2P. With useStereoUpright2p false it behaves like the overload above.
 class RansacPipeline {
 public:
     static std::unique_ptr<RansacPipeline> buildHip(Session &session, int imageWidth, int imageHeight,
@@ -272,6 +279,10 @@ public:
     static std::unique_ptr<RansacPipeline> buildHip(Session &session, int imageWidth, int imageHeight,
                                                     const RansacPipelineParameters &parameters,
                                                     const std::array<double, 16> &secondToFirstCamera);
+    static std::unique_ptr<RansacPipeline> buildHipUpright2p(Session &session, int imageWidth, int imageHeight,
+                                                             const RansacPipelineParameters &parameters,
+                                                             const std::array<double, 16> &secondToFirstCamera,
+                                                             const hv_upright2p_params &upright2p);
     virtual ~RansacPipeline();
     virtual double compute(
         const std::vector<std::array<const hv_camera_model *, 2>> &cameras,

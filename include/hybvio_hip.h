@@ -1064,6 +1064,65 @@ int hv_flow_predict_batch_dev(hv_ekf *ekf, const hv_flow_predict_params *p, int 
                               const hv_camera_model *camera0, const hv_camera_model *camera1, float *pred_xy_dev,
                               double *distance_dev, int reuse_distance);
 
+/* ---- stereo upright 2-point RANSAC: gravity-aware track filter (added within ABI 4) -----------------------------------
+ * Replaces StereoUpright2p::compute (src/tracker/stereo_upright_2p.cpp:110-183, the error :72-81) and the UPRIGHT_2P
+ * branch of RansacPipeline::compute (src/tracker/ransac_pipeline.cpp:124-127, 137-149) without Theia. poses = the
+ * camera-to-world matrices of the previous and the current frame (two row-major 4x4, src/odometry/backend.cpp:667-679); the
+ * filter reads their rotations R0, R1. Per feature with status TRACKED (0), in feature order: the status becomes
+ * RANSAC_OUTLIER (3); Camera::normalizePixel of the previous-left (camera0) and previous-right (camera1) corner;
+ * triangulateStereoFeatureIdp of the pair with second_to_first (as hv_ransac3); Camera::pixelToRay of the current-left
+ * corner (camera0); the correspondence is modelPoint = R0 X, ray = R1 ray_cam, rayNormalized = ray_cam.xy / ray_cam.z. A
+ * feature failing any step takes no part. With at least 2 correspondences a 2-point RANSAC estimates the rotation about
+ * the world's z axis (gravity) and the translation between the two frames, and its inliers go back to TRACKED.
+ * The sample-consensus loop, the sampler and the minimal solver are the ones stated in tests/upright2p_restatement.py
+ * (Theia is not in the reference tree; DESIGN.md 3.21 lists what follows a recollection of it and what departs from it).
+ * draws = the next 2 * ransacStereoUpright2pMaxIterations raw outputs of the caller's std::mt19937; afterwards the caller
+ * keeps 2 * iterations-run of them consumed. Field names are the reference's parameters
+ * (codegen/parameter_definitions.c:282, 299-303).
+ * HV_ERR_UNSUPPORTED: ransacStereoUpright2pMaxIterations > HV_UPRIGHT2P_MAX_ITERS, more than 1024 points or more than 65535
+ * sets; HV_ERR_INVALID: ...FailureProbability outside (0, 1), ...ErrorThresh <= 0, ...MaxIterations < 1, ...MinIterations >
+ * ...MaxIterations, ransacMinInlierFraction outside [0, 1] or a NULL required pointer. The parameter and size checks come
+ * before the context is looked at. The launches are timed under HV_K_RANSAC3. */
+#define HV_UPRIGHT2P_MAX_ITERS 500
+typedef struct hv_upright2p_params {
+    double ransacStereoUpright2pErrorThresh; double ransacStereoUpright2pFailureProbability;
+    int ransacStereoUpright2pMaxIterations; int ransacStereoUpright2pMinIterations; int ransacStereoUpright2pUseMle;
+    double ransacMinInlierFraction;
+} hv_upright2p_params;
+void hv_upright2p_default_params(hv_upright2p_params *p);   /* 1e-4, 1e-4, 500, 50, 1, 0.3 */
+/* StereoUpright2p::compute on one set of n features: poses[32], status[n] int32 Feature::Status in/out (entries other than
+ * TRACKED stay), model[12] (NULL ok) = R row-major then t, world1 = R world0 + t, zeros without a model; summary[4]
+ * (NULL ok) = {inlier count, iteration of the best model (-1: none), iterations run, correspondences m}. Fewer than 2
+ * correspondences: not run, {0, -1, 0, m}. Synchronous; host pointers, staged through the context's arena. */
+int hv_upright2p(hv_ctx *ctx, const hv_upright2p_params *p, int n, const float *prev_left_xy, const float *prev_right_xy,
+                 const float *cur_left_xy, const hv_camera_model *camera0, const hv_camera_model *camera1,
+                 const double *second_to_first, const double *poses, const uint32_t *draws, int *status, double *model,
+                 int *summary);
+/* n_sets sets in device memory, laid out as for hv_ransac3_batch_dev; poses_dev [n_sets][2][16], draws_dev
+ * [n_sets][2 * ransacStereoUpright2pMaxIterations], model_dev [n_sets][12] and summary_dev [n_sets][4] (NULL ok).
+ * Asynchronous on the context stream, no allocation or synchronisation inside (capturable in a HIP graph). */
+int hv_upright2p_batch_dev(hv_ctx *ctx, const hv_upright2p_params *p, int n_sets, int max_points, const int *n_points_dev,
+                           const float *prev_left_dev, const float *prev_right_dev, const float *cur_left_dev,
+                           const hv_camera_model *camera0, const hv_camera_model *camera1, const double *second_to_first,
+                           const double *poses_dev, const uint32_t *draws_dev, int *status_dev, double *model_dev,
+                           int *summary_dev);
+/* The stereo device chain step after hv_rot_ransac_lk_batch_dev for the hv_ekf_batch(ekf) resident sequences of a filter
+ * batch (set s is filter s), on the filter's context stream: RansacPipeline::compute on the UPRIGHT_2P branch with the poses
+ * of backend.cpp:667-679 formed on the device from the mean, poses[0] = toCameraToWorld(historyPosition(0),
+ * historyOrientation(0)) and poses[1] = toCameraToWorld(position(), orientation()) (src/odometry/util.cpp:144-158) with
+ * cam_params->cameraToImu, the caller's inverse of imuToCamera (as hv_flow_predict_batch_dev; the other members are not
+ * read). It belongs where Session::applyTracker runs: after the frame's IMU predicts and before the visual update.
+ * track_status_dev, r2_summary_dev, score_dev and the corner arguments are those of hv_ransac3_lk_batch_dev; result_dev
+ * [n_sets][2] = {type 0 SKIPPED / 4 UPRIGHT_2P, inlierCount}. A set whose mean is non-finite ends SKIPPED and touches no
+ * other set. After the checks above: HV_ERR_INVALID for a NULL handle, HV_ERR_UNSUPPORTED for a state of fewer than 27
+ * entries. Asynchronous, capturable. */
+int hv_upright2p_lk_batch_dev(hv_ekf *ekf, const hv_upright2p_params *p, const hv_flow_predict_params *cam_params,
+                              int max_points, const int *n_points_dev, const float *prev_left_dev,
+                              const float *prev_right_dev, const float *cur_left_dev, int *track_status_dev,
+                              const int *r2_summary_dev, const hv_camera_model *camera0, const hv_camera_model *camera1,
+                              const double *second_to_first, const uint32_t *draws_dev, int *result_dev, double *score_dev,
+                              double *model_dev, int *summary_dev);
+
 /* ---- device session lifecycle: tracking status, reset rules, in-place re-initialisation (added within ABI 4) ------------
  * Replaces, for the hv_ekf_batch(ekf) resident sequences of a filter batch (set s is filter s), what Session and Control do
  * around a frame besides the filter algebra: the filter's sample clock (src/odometry/ekf.cpp:357-366) and
@@ -1336,7 +1395,7 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_STEREO_GATE = 14 /* added within ABI 4: hv_flow_status_batch_dev, hv_track_gate*, hv_detection_filter* */,
        HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
-       HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3* */,
+       HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3*, hv_upright2p* */,
        HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev, hv_session_*_dev, hv_output_dev */,
        HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev, the index kernel of hv_full_point_cloud_dev */,
        HV_K_COUNT = 20 };
