@@ -191,6 +191,11 @@ class FullCloudTable(C.Structure):
                                           "tail_status", "tail_col", "tail_pose_mask", "n_attempts", "good_frame")]
 
 
+class RngState(C.Structure):
+    """hv_rng: device pointers owned by the caller."""
+    _fields_ = [("mt", C.c_void_p), ("pos", C.c_void_p)]
+
+
 class HvError(RuntimeError):
     pass
 
@@ -349,6 +354,9 @@ PROTOTYPES = {
                                 C.POINTER(OutputFrame), C.POINTER(OutputTable)]),
     "hv_full_point_cloud_dev": (C.c_int, [C.c_void_p, C.POINTER(TrailIndexParams), C.c_void_p, C.POINTER(TrailIndexTable),
                                           C.POINTER(TrackTable), C.POINTER(FullCloudFrame), C.POINTER(FullCloudTable)]),
+    "hv_rng_seed_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RngState), C.c_uint32, C.c_void_p, C.c_void_p]),
+    "hv_rng_draw_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RngState), C.c_int, C.c_void_p]),
+    "hv_rng_advance_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RngState), C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -715,6 +723,26 @@ class Context:
                                                   p(discarded_dev)),
                   "hv_trail_finish_batch_dev")
 
+    # ---- device std::mt19937 streams: the draws of the RANSAC filters and of the shuffle ----
+    def rng_seed_batch_dev(self, n_sets, rng: "RngState", seed: int = 0, seed_dev=0, reset_kind_dev=0):
+        """hv_rng_seed_batch_dev: std::mt19937(seed) per set (seed_dev [n_sets] uint32 overrides `seed`); with reset_kind_dev only the
+        sets that reset are written."""
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_rng_seed_batch_dev(self._h, n_sets, C.byref(rng), int(seed) & 0xffffffff, p(seed_dev), p(reset_kind_dev)),
+                  "hv_rng_seed_batch_dev")
+
+    def rng_draw_batch_dev(self, n_sets, rng: "RngState", n_draws, draws_dev):
+        """hv_rng_draw_batch_dev: draws_dev [n_sets][n_draws] = the next raw outputs of each set; the state is not changed."""
+        self._chk(lib().hv_rng_draw_batch_dev(self._h, n_sets, C.byref(rng), int(n_draws), C.c_void_p(draws_dev or None)),
+                  "hv_rng_draw_batch_dev")
+
+    def rng_advance_batch_dev(self, n_sets, rng: "RngState", count_dev, count_stride, multiplier, max_draws):
+        """hv_rng_advance_batch_dev: every set moves on by min(multiplier * clamp(count_dev[s * count_stride], 0, max_draws), max_draws)
+        outputs. count_dev is an address: summary.data_ptr() + 4 for the RANSAC2 summary (stride 2, multiplier 2), + 8 for the RANSAC3
+        and upright summaries (stride 4, multiplier 3 or 2), draws_used (stride 1, multiplier 1)."""
+        self._chk(lib().hv_rng_advance_batch_dev(self._h, n_sets, C.byref(rng), C.c_void_p(count_dev or None), int(count_stride),
+                                                 int(multiplier), int(max_draws)), "hv_rng_advance_batch_dev")
+
     # ---- image ingest (f2): colour -> gray and the undistort / rectify remap in front of the pyramid ----
     def ingest_set_undistort_map(self, camera: int, pix_orig=None, valid=None):
         """pix_orig (h, w, 2) f64 = original-image position of every rectified pixel (None removes the table)."""
@@ -969,6 +997,26 @@ class TrailIndex:
                       skipped_id=((S, M), i32), cand_pos=((S, V), i32), cand_col=((S, V), i32))
         self.m = {k: torch.zeros(shape, dtype=dt, device="cuda") for k, (shape, dt) in shapes.items()}
         self.table = TrailIndexTable(*(self.m[k].data_ptr() for k, _ in TrailIndexTable._fields_))
+
+
+RNG_STATE_WORDS = 624
+RNG_MAX_DRAWS = 2048
+
+
+class Rng:
+    """hv_rng for n_sets sequences: mt [n_sets][624] (int32 tensor holding the uint32 words) and pos [n_sets] int32 on `device`, and
+    the pointer table over them (self.table). Uninitialised until rng_seed_batch_dev."""
+
+    def __init__(self, n_sets: int, device="cuda"):
+        self.n_sets = n_sets
+        self.mt = torch.zeros((n_sets, RNG_STATE_WORDS), dtype=torch.int32, device=device)
+        self.pos = torch.zeros((n_sets,), dtype=torch.int32, device=device)
+        self.table = RngState(self.mt.data_ptr(), self.pos.data_ptr())
+
+
+def rng_state(n_sets: int, device="cuda") -> Rng:
+    """Allocates an hv_rng (the allocator beside session_state and TrailIndex)."""
+    return Rng(n_sets, device)
 
 
 def subpix_default_params(**over) -> SubpixParams:

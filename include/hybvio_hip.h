@@ -1386,6 +1386,56 @@ typedef struct hv_full_cloud {            /* device memory owned by the caller; 
 int hv_full_point_cloud_dev(hv_ekf *ekf, const hv_trail_index_params *tp, const hv_vu_params *vp, const hv_trail_index *trail,
                             const hv_track_table *table, const hv_full_cloud_frame *in, const hv_full_cloud *out);
 
+/* ---- device std::mt19937 streams: the draws of the RANSAC filters and of the shuffle (added within ABI 4) --------------
+ * Replaces, for n_sets resident sequences, the host generators whose raw outputs the entries above take as draws_dev and
+ * the step "read the consumed count back, advance the generator" behind them: a std::mt19937 per sequence and per generator
+ * in device memory owned by the caller (like hv_trail_index), one hv_rng each for
+ * - the pipeline's generator (src/tracker/ransac_pipeline.cpp:46,66), read by RotRansac::fit (src/tracker/rot_ransac.cpp:74-96),
+ *   two outputs per hypothesis visited: draw 200, hv_rot_ransac_lk_batch_dev, advance(summary_dev + 1, 2, 2, 200);
+ * - RANSAC3's own (ransac_pipeline.cpp:78), three outputs per iteration run: draw 3 * ransac3MaxIterations, hv_ransac3*_batch_dev,
+ *   advance(summary_dev + 2, 4, 3, 3 * ransac3MaxIterations);
+ * - the upright 2-point filter's own (src/tracker/stereo_upright_2p.cpp:101), two per iteration: draw 2 *
+ *   ransacStereoUpright2pMaxIterations, hv_upright2p*_batch_dev, advance(summary_dev + 2, 4, 2, 2 * ...MaxIterations);
+ * - the odometry generator (src/odometry/backend.cpp:107,117,193), read by shuffleDeterministic (src/util/util.hpp:39-44,
+ *   backend.cpp:964): draw maxTracks, hv_trail_select_batch_dev, the visit loop, hv_full_point_cloud_dev on the same buffer,
+ *   advance(draws_used_dev, 1, 1, maxTracks).
+ * Control::reset (src/odometry/control.cpp:49-65) builds a new Session and with it a new tracker, whose three generators start again
+ * from ransacRngSeed; the odometry generator belongs to the shared data and survives (backend.cpp:107-117,193). So a caller
+ * runs hv_rng_seed_batch_dev(..., reset_kind_dev) on the three tracker generators behind hv_session_reset_dev, never on the
+ * odometry one.
+ * The stored state is the engine's own, lazy as in libstdc++ (bits/random.tcc): mt is the array of the last twist and pos the
+ * number of its words already handed out; a twist happens only when an output needs it, so pos is 624 after seeding and
+ * 1 .. 624 after any output, and mt / pos compare bit for bit with tests/rng_restatement.py and with the state of numpy's
+ * legacy-seeded MT19937.
+ * All entries: one launch of one wavefront per set on the context stream, timed under HV_K_TRAIL_INDEX, no allocation or
+ * synchronisation inside (capturable in a HIP graph). Checks made before the context is looked at: HV_ERR_INVALID for a NULL
+ * required pointer (a state member included), a negative size, n_draws < 1, multiplier < 1, count_stride < 1; then
+ * HV_ERR_UNSUPPORTED for n_sets > 65535, n_draws or max_draws above HV_RNG_MAX_DRAWS. n_sets = 0 returns HV_OK without a
+ * launch. Values read from device memory are clamped: pos to 0 .. 624, counts as stated at hv_rng_advance_batch_dev. */
+#define HV_RNG_STATE_WORDS 624
+#define HV_RNG_MAX_DRAWS   2048          /* >= 3 * HV_RANSAC3_MAX_ITERS */
+typedef struct hv_rng {                  /* device memory owned by the caller */
+    uint32_t *mt;                        /* [n_sets][624] */
+    int32_t  *pos;                       /* [n_sets]  words of mt already handed out: 1 .. 624, 624 = twist before the next output */
+} hv_rng;
+/* std::mt19937(seed) (the constructors of ransac_pipeline.cpp:66,78, stereo_upright_2p.cpp:101 and backend.cpp:117):
+ * mt[0] = seed, mt[i] = 1812433253 * (mt[i-1] ^ (mt[i-1] >> 30)) + i, pos = 624. seed_dev [n_sets] or NULL (every set takes
+ * `seed`). reset_kind_dev [n_sets] int32 or NULL (every set): only sets whose entry is HV_RESET_FRESH or HV_RESET_KEEP_POSE are
+ * written, the others keep mt and pos bit for bit. */
+int hv_rng_seed_batch_dev(hv_ctx *ctx, int n_sets, const hv_rng *rng, uint32_t seed, const uint32_t *seed_dev,
+                          const int32_t *reset_kind_dev);
+/* draws_dev [n_sets][n_draws] = what the next n_draws calls of rng() would return (the rng() of rot_ransac.cpp:75-76 and of
+ * util.hpp:39-44); the state is NOT changed: the consumer decides how many of them count, and hv_full_point_cloud_dev reads
+ * the same draws as hv_trail_select_batch_dev did. 1 <= n_draws <= HV_RNG_MAX_DRAWS. */
+int hv_rng_draw_batch_dev(hv_ctx *ctx, int n_sets, const hv_rng *rng, int n_draws, uint32_t *draws_dev);
+/* The state after c further calls of rng(), c = min(multiplier * clamp(count_dev[s * count_stride], 0, max_draws), max_draws),
+ * 0 <= max_draws <= HV_RNG_MAX_DRAWS: what the loop of rot_ransac.cpp:74-96 leaves behind when it ends at the first all-inlier
+ * hypothesis, and the samplers of the two own generators and the shuffle likewise. count_dev = summary_dev + 1, stride 2,
+ * multiplier 2 for RANSAC2; summary_dev + 2, stride 4, multiplier 3 (RANSAC3) or 2 (upright 2-point); draws_used_dev, stride 1,
+ * multiplier 1. A set with c = 0 is not written at all; after c > 0, pos is in 1 .. 624. */
+int hv_rng_advance_batch_dev(hv_ctx *ctx, int n_sets, const hv_rng *rng, const int32_t *count_dev, int count_stride,
+                             int multiplier, int max_draws);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
@@ -1397,7 +1447,7 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3*, hv_upright2p* */,
        HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev, hv_session_*_dev, hv_output_dev */,
-       HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev, the index kernel of hv_full_point_cloud_dev */,
+       HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev, the index kernel of hv_full_point_cloud_dev, hv_rng_*_batch_dev */,
        HV_K_COUNT = 20 };
 int hv_profile_enable(hv_ctx *ctx, int on);
 int hv_profile_reset(hv_ctx *ctx);
