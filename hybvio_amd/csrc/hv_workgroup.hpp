@@ -1,5 +1,5 @@
-// Small workgroup-level tools shared by the tracker-side kernels (rot_ransac.hip, ransac5.hip, ransac3.hip, upright2p.hip,
-// trail_index.hip, flow_predict.hip, track_table.hip): the ordered ballot compaction, the gather that follows it in the RANSAC kernels, the staging of
+// Small workgroup-level tools shared by the tracker-side kernels (rot_ransac.hip, ransac5.hip, ransac3.hip and upright2p.hip -- there
+// mostly through hv_sample_consensus.hpp --, trail_index.hip, flow_predict.hip, track_table.hip): the ordered ballot compaction, the gather that follows it in the RANSAC kernels, the staging of
 // two camera models into LDS, and clampi. Device-only; wave64, one-dimensional workgroups.
 //
 // No include guard and no namespace of its own, like hv_geometry.hpp: a translation unit includes it once, inside its anonymous

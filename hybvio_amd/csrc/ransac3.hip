@@ -16,6 +16,8 @@
 //   e. lane 0 replays the loop's rule over the stored costs: strict `<`, adaptive limit
 //   f. every lane classifies its correspondences with the best model; statuses, pose, summary, the tail of compute
 // Arithmetic is binary64 in the operation order of the restatement (the library is built without FMA contraction).
+// The round loop, b, d, e, f and the compaction of a are hv_sample_consensus.hpp's, shared with upright2p.hip; this file holds the
+// problem (R3Problem): the per-lane loop of a, c with the quartic and the P3P, the residual and the entry points.
 #include "hv_camera.hpp"
 #include "hv_internal.hpp"
 #include "ransac_lds.hpp"
@@ -31,53 +33,17 @@ namespace {
 #include "hv_stereo_idp.hpp"  // triangulate_world: shared with upright2p.hip
 #include "hv_workgroup.hpp"  // block_compact, block_gather_front, stage_cameras
 
-constexpr int R3_MAX_PTS = 1024;
-// R3_THREADS, R3_WAVES, R3_CHUNK (iterations per round): ransac_lds.hpp
+// R3_THREADS, R3_CHUNK (iterations per round): ransac_lds.hpp
+#include "hv_sample_consensus.hpp"  // ScArgs, ScView and the phases a (tail), b, d, e, f, the round loop, the host side
 
-struct R3Args {
-    int max_points, max_iters, min_iters, use_mle, cap, tail;
-    const int *n_points;
-    const float *pl, *pr, *cl;            // previous-left, previous-right, current-left corners [sets][max_points][2]
-    const uint32_t *draws;                // [sets][3 * max_iters] raw std::mt19937 outputs
-    int *status;                          // [sets][max_points] Feature::Status in/out (TRACKED selects)
-    const int *r2_summary;                // tail: RANSAC2's {bestInlierCount, visited}
-    int *result;                          // tail: [sets][2] {type, inlierCount}
-    double *score;                        // tail: [sets]
-    double *pose;                         // [sets][12] or NULL
-    int *summary;                         // [sets][4] or NULL
-    double thr, logp;
-    double T[16];                         // secondToFirstCamera, row-major
-    hv_camera_model cam0, cam1;
-};
+struct R3Args : ScArgs {};                // model: the pose, R row-major and c (a type of its own: the kernel's name carries it)
 
-// a workgroup's LDS: the sections of Ransac3Lds as pointers, the staged cameras and secondToFirstCamera
-struct R3View {
-    double *wx, *wy, *wz, *fu, *fv, *mod, *cost, *best;
-    int *map, *vmap, *st, *idx, *chunk, *tri;
-    unsigned *draw;
-    int *cnt, *ctl;
-    const hv_camera_model *cam;
-    const double *T;
-};
+// a workgroup's LDS: the sections of Ransac3Lds as pointers
+struct R3View : ScView { double *wx, *wy, *wz, *fu, *fv; };
 __device__ __forceinline__ R3View r3_view(unsigned char *base, const Ransac3Lds &L, const hv_camera_model *cam, const double *T)
 {
     auto d = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
-    auto i = [&](size_t off) { return reinterpret_cast<int *>(base + off); };
-    return R3View{d(L.wx), d(L.wy), d(L.wz), d(L.fu), d(L.fv), d(L.mod), d(L.cost), d(L.best),
-                  i(L.map), i(L.vmap), i(L.st), i(L.idx), i(L.chunk), i(L.tri), reinterpret_cast<unsigned *>(base + L.draw),
-                  i(L.cnt), i(L.ctl), cam, T};
-}
-
-// ComputeMaxIterations for a sample of 3 (restatement: compute_max_iterations)
-__host__ __device__ inline int max_iterations_for(double ratio, double logp, int min_it, int max_it)
-{
-    if (ratio <= 0.0) return max_it;
-    if (ratio == 1.0) return min_it;
-    const double lp = log(1.0 - (ratio * ratio) * ratio) - DBL_EPSILON;
-    double v = ceil(logp / lp);
-    v = v < (double)min_it ? (double)min_it : v;
-    v = v > (double)max_it ? (double)max_it : v;
-    return (int)v;
+    return R3View{sc_view(base, L, L.tri, cam, T), d(L.wx), d(L.wy), d(L.wz), d(L.fu), d(L.fv)};
 }
 
 // real roots of A4 x^4 + ... + A0 (restatement: quartic_real_roots) -> x[4] and ok[4] in LDS
@@ -214,76 +180,6 @@ __device__ void p3p_lane(const double (*Pw)[3], const double (*F)[2], double *ro
     }
 }
 
-// |(R (X - c)).hnormalized() - feature|^2 (restatement: residuals)
-__device__ __forceinline__ double residual(const double *M, double X0, double X1, double X2, double fu, double fv)
-{
-    const double d0 = X0 - M[9], d1 = X1 - M[10], d2 = X2 - M[11];
-    const double p0 = (M[0] * d0 + M[1] * d1) + M[2] * d2, p1 = (M[3] * d0 + M[4] * d1) + M[5] * d2,
-                 p2 = (M[6] * d0 + M[7] * d1) + M[8] * d2;
-    const double e0 = p0 / p2 - fu, e1 = p1 / p2 - fv;
-    return e0 * e0 + e1 * e1;
-}
-
-// ---- the phases of ransac3_kernel (a .. f of the file header). Every thread of the workgroup calls every phase; each header says which
-// barriers the phase holds and what they publish ----
-
-// a. The correspondences of the n tracked features (ransac_pipeline.cpp:231-251): three normalizePixel calls and the triangulation per
-// lane, the m survivors compacted to the front (order kept), every status preset to RANSAC_OUTLIER (:235), the sampler's index vector and
-// the loop's control words {iteration, limit, best iteration, inliers} initialised. Returns m. Begins without a barrier (s_map, s_cam and
-// s_T are published by the caller). Barriers: one after the triangulation (publishes s_st and the points), block_compact's three,
-// block_gather_front's one; ends with one, which publishes the gathered points, s_st, s_idx and s_ctl.
-__device__ __forceinline__ int correspondences(const R3View &v, const float *pl, const float *pr, const float *cl, int n, int cap, int tid)
-{
-    for (int k = tid; k < n; k += R3_THREADS) {
-        const int src = v.map[k];
-        double h0[2], h1[2], h2[2], X[3];
-        bool ok = normalize_pixel_positive(v.cam[0], pl[2 * src], pl[2 * src + 1], h0);
-        ok = ok && normalize_pixel_positive(v.cam[1], pr[2 * src], pr[2 * src + 1], h1);
-        ok = ok && normalize_pixel_positive(v.cam[0], cl[2 * src], cl[2 * src + 1], h2);
-        ok = ok && triangulate_world(v.T, h0[0], h0[1], h1[0], h1[1], X);
-        v.st[k] = ok ? 1 : 0;
-        if (ok) { v.wx[k] = X[0]; v.wy[k] = X[1]; v.wz[k] = X[2]; v.fu[k] = h2[0]; v.fv[k] = h2[1]; }
-    }
-    __syncthreads();
-    const int m = block_compact<R3_WAVES>([&](int k) { return v.st[k] != 0; }, v.vmap, n, v.chunk);
-    static_assert(R3_MAX_PTS <= 4 * R3_THREADS, "four points per thread");
-    double *const pts[5] = {v.wx, v.wy, v.wz, v.fu, v.fv};
-    block_gather_front<R3_THREADS>(pts, v.vmap, m);
-    for (int k = tid; k < n; k += R3_THREADS) v.st[k] = 3;
-    for (int j = tid; j < m; j += R3_THREADS) v.idx[j] = j;
-    if (tid == 0) { v.ctl[0] = 0; v.ctl[1] = cap; v.ctl[2] = -1; v.ctl[3] = 0; }
-    __syncthreads();
-    return m;
-}
-
-// positions 0..2 of the sampler's index vector, kept in registers by lane 0 (the rest is s_idx)
-struct R3Head { int i0, i1, i2; };
-
-// b. The sampler for the h iterations from it0: the raw draws go to LDS, a barrier publishes them, then lane 0 replays the partial
-// shuffle idx[i] <-> idx[i + raw % (m - i)], i = 0, 1, 2, and hands each sample over in ascending index order. Ends with a barrier,
-// which publishes s_tri.
-__device__ __forceinline__ void sampler(const R3View &v, const uint32_t *draws, int it0, int h, int m, R3Head &hd, int tid)
-{
-    if (tid < 3 * h) v.draw[tid] = draws[3 * it0 + tid];
-    __syncthreads();
-    if (tid == 0) {
-        int &i0 = hd.i0, &i1 = hd.i1, &i2 = hd.i2;
-        for (int k = 0; k < h; ++k) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int j = i + (int)(v.draw[3 * k + i] % (unsigned)(m - i));
-                int &mine = i == 0 ? i0 : i == 1 ? i1 : i2;
-                if (j >= 3) { const int o = v.idx[j]; v.idx[j] = mine; mine = o; }
-                else { int &other = j == 0 ? i0 : j == 1 ? i1 : i2; const int o = other; other = mine; mine = o; }
-            }
-            // the solver's canonical order: ascending indices (a repeated triple repeats its models bit for bit)
-            const int lo = min(i0, min(i1, i2)), hi = max(i0, max(i1, i2));
-            v.tri[3 * k] = lo; v.tri[3 * k + 1] = i0 + i1 + i2 - lo - hi; v.tri[3 * k + 2] = hi;
-        }
-    }
-    __syncthreads();
-}
-
 // c. One P3P per lane, lanes 0 .. h - 1: up to four (R, c) into s_mod, their flags into s_cnt (s_cost holds the quartic's roots). Ends
 // with a barrier, which publishes the models and the flags.
 __device__ __forceinline__ void p3p_round(const R3View &v, int h, int tid)
@@ -292,7 +188,7 @@ __device__ __forceinline__ void p3p_round(const R3View &v, int h, int tid)
         double Pw[3][3], F[3][2];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const int s = v.tri[3 * tid + q];
+            const int s = v.sample[3 * tid + q];
             Pw[q][0] = v.wx[s]; Pw[q][1] = v.wy[s]; Pw[q][2] = v.wz[s]; F[q][0] = v.fu[s]; F[q][1] = v.fv[s];
         }
         p3p_lane(Pw, F, v.cost + 4 * tid, v.cnt + 4 * tid, v.mod + 48 * tid);
@@ -300,166 +196,88 @@ __device__ __forceinline__ void p3p_round(const R3View &v, int h, int tid)
     __syncthreads();
 }
 
-// d. Cost and inlier count of (hypothesis, solution) = lane over all m correspondences, added in order, into s_cost and s_cnt (-1: no
-// model) over the lane's own flag and root. Ends with a barrier, which publishes both.
-__device__ __forceinline__ void cost_and_count(const R3View &v, int h, int m, double thr, int use_mle, int tid)
-{
-    const bool have = (tid >> 2) < h && v.cnt[tid] != 0;
-    double cost = 0.0;
-    int cnt = -1;
-    if (have) {
-        double M[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) M[i] = v.mod[12 * tid + i];
-        cnt = 0;
-        for (int j = 0; j < m; ++j) {
-            const double r = residual(M, v.wx[j], v.wy[j], v.wz[j], v.fu[j], v.fv[j]);
-            const bool in = r < thr;
-            cnt += in ? 1 : 0;
-            cost = cost + (in ? r : thr);
-        }
-        if (!use_mle) cost = (double)(m - cnt);
-    }
-    v.cnt[tid] = cnt; v.cost[tid] = cost;
-    __syncthreads();
-}
+// the problem of hv_sample_consensus.hpp: its phases a (the per-lane loop) and c, the residual and the output model
+struct R3Problem {
+    static constexpr int SAMPLE = 3, SOLUTIONS = 4, MODEL = 12, THREADS = R3_THREADS, CHUNK = R3_CHUNK, TYPE = 2;   // RansacResult::Type::R3
+    using View = R3View;
 
-// e. The loop's rule, replayed by lane 0 over the stored costs of the round: strict `<`, adaptive limit; the best model goes to s_best,
-// the control words are brought up to date. Ends with a barrier, which publishes s_ctl (the loop's condition reads it) and s_best.
-__device__ __forceinline__ void loop_rule(const R3View &v, const R3Args &a, int it0, int limit, int h, int m, double &best_cost, int tid)
-{
-    if (tid == 0) {
-        int it = it0, lim = limit;
-        for (int k = 0; k < h && it < lim; ++k, ++it)
-            for (int s = 0; s < 4; ++s) {
-                const int w = 4 * k + s, cnt = v.cnt[w];
-                if (cnt >= 0 && v.cost[w] < best_cost) {
-                    best_cost = v.cost[w];
-                    for (int i = 0; i < 12; ++i) v.best[i] = v.mod[12 * w + i];
-                    v.ctl[2] = it; v.ctl[3] = cnt;
-                    const double ratio = (double)cnt / (double)m;
-                    if (!(ratio < 3.0 / (double)m)) lim = min(max_iterations_for(ratio, a.logp, a.min_iters, a.max_iters), lim);
-                }
-            }
-        v.ctl[0] = it; v.ctl[1] = lim;
-    }
-    __syncthreads();
-}
-
-// f. The best model's inliers go back to TRACKED (:265-268); statuses, pose, summary and the tail of compute (:139-144). Two barriers:
-// one publishes the zeroed counter s_ctl[4], one the inlier count and s_st. Begins and ends without one.
-__device__ __forceinline__ void inliers_and_outputs(const R3View &v, const R3Args &a, int set, int *ts, int n_all, int n, int m, bool run,
-                                                    int tid)
-{
-    const int iters = v.ctl[0], best_it = v.ctl[2];
-    const bool success = run && best_it >= 0;
-    if (tid == 0) v.ctl[4] = 0;
-    __syncthreads();
-    if (success) {
-        double M[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) M[i] = v.best[i];
-        int cnt = 0;
-        for (int j = tid; j < m; j += R3_THREADS)
-            if (residual(M, v.wx[j], v.wy[j], v.wz[j], v.fu[j], v.fv[j]) < a.thr) { v.st[v.vmap[j]] = 0; ++cnt; }
-        if (cnt) atomicAdd(&v.ctl[4], cnt);
-    }
-    __syncthreads();
-    const int count = v.ctl[4];
-    if (tid == 0) {
-        if (a.pose)
-            for (int i = 0; i < 12; ++i) a.pose[12 * (size_t)set + i] = success ? v.best[i] : 0.0;
-        if (a.summary) {
-            int *sm = a.summary + 4 * (size_t)set;
-            sm[0] = count; sm[1] = success ? best_it : -1; sm[2] = run ? iters : 0; sm[3] = m;
+    // a. The correspondences of the n tracked features (ransac_pipeline.cpp:231-251): three normalizePixel calls and the triangulation
+    // per lane, then compact_and_init (every status preset to RANSAC_OUTLIER: :235). Begins without a barrier (s_map, s_cam and s_T are
+    // published by the caller).
+    static __device__ __forceinline__ int correspondences(const R3View &v, const float *pl, const float *pr, const float *cl, int n, int cap, int tid)
+    {
+        for (int k = tid; k < n; k += R3_THREADS) {
+            const int src = v.map[k];
+            double h0[2], h1[2], h2[2], X[3];
+            bool ok = normalize_pixel_positive(v.cam[0], pl[2 * src], pl[2 * src + 1], h0);
+            ok = ok && normalize_pixel_positive(v.cam[1], pr[2 * src], pr[2 * src + 1], h1);
+            ok = ok && normalize_pixel_positive(v.cam[0], cl[2 * src], cl[2 * src + 1], h2);
+            ok = ok && triangulate_world(v.T, h0[0], h0[1], h1[0], h1[1], X);
+            v.st[k] = ok ? 1 : 0;
+            if (ok) { v.wx[k] = X[0]; v.wy[k] = X[1]; v.wz[k] = X[2]; v.fu[k] = h2[0]; v.fv[k] = h2[1]; }
         }
+        double *const pts[5] = {v.wx, v.wy, v.wz, v.fu, v.fv};
+        return compact_and_init<R3Problem>(v, pts, n, cap, tid);
     }
-    if (a.tail && !success) {                                                // SKIPPED: every track is cleared (:139-144)
-        for (int i = tid; i < n_all; i += R3_THREADS) ts[i] = 3;
-    } else {
-        for (int k = tid; k < n; k += R3_THREADS) ts[v.map[k]] = v.st[k];
+
+    // c. p3p_round with its barrier, then the model of (hypothesis, solution) = lane from s_mod into M. Returns whether the lane has one.
+    static __device__ __forceinline__ bool models(const R3View &v, int h, int tid, double *M)
+    {
+        p3p_round(v, h, tid);
+        const bool have = (tid >> 2) < h && v.cnt[tid] != 0;
+        if (have) {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) M[i] = v.mod[12 * tid + i];
+        }
+        return have;
     }
-    if (a.tail && tid == 0) {
-        a.result[2 * (size_t)set] = success ? 2 : 0;
-        a.result[2 * (size_t)set + 1] = count;
-        const int r2count = n >= 2 ? a.r2_summary[2 * set] : 0;              // doRansac2 does not run below two tracks (:210)
-        a.score[set] = n ? (double)r2count / (double)n : 0.0;
+
+    // |(R (X - c)).hnormalized() - feature|^2 of correspondence j (restatement: residuals)
+    static __device__ __forceinline__ double residual(const double *M, const R3View &v, int j)
+    {
+        const double d0 = v.wx[j] - M[9], d1 = v.wy[j] - M[10], d2 = v.wz[j] - M[11];
+        const double p0 = (M[0] * d0 + M[1] * d1) + M[2] * d2, p1 = (M[3] * d0 + M[4] * d1) + M[5] * d2,
+                     p2 = (M[6] * d0 + M[7] * d1) + M[8] * d2;
+        const double e0 = p0 / p2 - v.fu[j], e1 = p1 / p2 - v.fv[j];
+        return e0 * e0 + e1 * e1;
     }
-}
+
+    static __device__ __forceinline__ void write_model(double *o, const double *best, bool success)
+    {
+        for (int i = 0; i < 12; ++i) o[i] = success ? best[i] : 0.0;
+    }
+};
 
 __global__ __launch_bounds__(R3_THREADS) void ransac3_kernel(R3Args a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char r3_lds[];
     __shared__ hv_camera_model s_cam[2];
     __shared__ double s_T[16];
-    const int set = blockIdx.x, tid = threadIdx.x;
-    const int MP = a.max_points;
-    const R3View v = r3_view(r3_lds, ransac3_lds(MP), s_cam, s_T);
+    const int tid = threadIdx.x;
     stage_cameras<R3_THREADS>(s_cam, a.cam0, a.cam1);
     if (tid < 16) s_T[tid] = a.T[tid];
-    __syncthreads();                                            // publishes s_cam and s_T
-    const int n_all = min(max(a.n_points[set], 0), MP);
-    const float *pl = a.pl + (size_t)set * MP * 2, *pr = a.pr + (size_t)set * MP * 2, *cl = a.cl + (size_t)set * MP * 2;
-    int *ts = a.status + (size_t)set * MP;
-
-    // the set: TRACKED features in feature order
-    const int n = block_compact<R3_WAVES>([&](int i) { return ts[i] == 0; }, v.map, n_all, v.chunk);
-    const int m = correspondences(v, pl, pr, cl, n, a.cap, tid);            // a
-    // m, and the control words that the loop reads behind a barrier, are the same in every thread: the conditions below are uniform
-    // over the workgroup, so the barriers inside the phases are met by every thread or by none
-    const bool run = m >= 3;
-    if (run) {
-        R3Head head{0, 1, 2};                                               // lane 0
-        double best_cost = DBL_MAX;                                         // lane 0
-        const uint32_t *draws = a.draws + (size_t)set * 3 * a.max_iters;
-        for (;;) {                                                          // rounds of up to R3_CHUNK iterations
-            const int it0 = v.ctl[0], limit = v.ctl[1];
-            if (it0 >= limit) break;
-            const int h = min(R3_CHUNK, a.cap - it0);
-            sampler(v, draws, it0, h, m, head, tid);                        // b
-            p3p_round(v, h, tid);                                           // c
-            cost_and_count(v, h, m, a.thr, a.use_mle, tid);                 // d
-            loop_rule(v, a, it0, limit, h, m, best_cost, tid);              // e
-        }
-    }
-    inliers_and_outputs(v, a, set, ts, n_all, n, m, run, tid);              // f
+    sample_consensus<R3Problem>(r3_view(r3_lds, ransac3_lds(a.max_points), s_cam, s_T), a);   // begins with the barrier for s_cam and s_T
 }
 
-
-// the host-side checks, made before the context is looked at
-int check_params(const hv_ransac3_params *p, int max_points, int n_sets)
+ScParams six(const hv_ransac3_params *p)
 {
-    if (!p || !(p->ransac3FailureProbability > 0 && p->ransac3FailureProbability < 1) || !(p->ransac3ErrorThresh > 0) ||
-        p->ransac3MaxIterations < 1 || p->ransac3MinIterations > p->ransac3MaxIterations ||
-        !(p->ransacMinInlierFraction >= 0 && p->ransacMinInlierFraction <= 1) || max_points < 1 || n_sets < 0)
-        return HV_ERR_INVALID;
-    if (max_points > R3_MAX_PTS || p->ransac3MaxIterations > HV_RANSAC3_MAX_ITERS || n_sets > 65535) return HV_ERR_UNSUPPORTED;
-    return HV_OK;
+    if (!p) return ScParams{};
+    return ScParams{p->ransac3ErrorThresh, p->ransac3FailureProbability, p->ransac3MaxIterations, p->ransac3MinIterations, p->ransac3UseMle,
+                    p->ransacMinInlierFraction};
 }
 
-void fill_common(R3Args &a, const hv_ransac3_params *p, int max_points, const hv_camera_model *cam0, const hv_camera_model *cam1,
-                 const double *second_to_first)
-{
-    a.max_points = max_points; a.max_iters = p->ransac3MaxIterations; a.min_iters = p->ransac3MinIterations;
-    a.use_mle = p->ransac3UseMle ? 1 : 0;
-    a.thr = p->ransac3ErrorThresh; a.logp = std::log(p->ransac3FailureProbability);
-    a.cap = std::min(a.max_iters, max_iterations_for(p->ransacMinInlierFraction, a.logp, a.min_iters, a.max_iters));
-    for (int i = 0; i < 16; ++i) a.T[i] = second_to_first[i];
-    a.cam0 = *cam0; a.cam1 = *cam1;
-}
+int check_params(const hv_ransac3_params *p, int max_points, int n_sets) { return check(six(p), max_points, n_sets, HV_RANSAC3_MAX_ITERS); }
 
 int launch(Ctx *c, int n_sets, const R3Args &a)
 {
-    hipLaunchKernelGGL(ransac3_kernel, dim3((unsigned)n_sets), dim3(R3_THREADS), ransac3_lds(a.max_points).end, c->stream, a);
-    HV_HIP(c, hipGetLastError());
-    return HV_OK;
+    return launch(c, ransac3_kernel, R3_THREADS, ransac3_lds(a.max_points).end, n_sets, a);
 }
 
 }  // namespace
 
 int ransac3_init(Ctx *c)
 {
-    HV_HIP(c, set_lds_limit(ransac3_kernel, ransac3_lds(R3_MAX_PTS).end));
+    HV_HIP(c, set_lds_limit(ransac3_kernel, ransac3_lds(SC_MAX_PTS).end));
     return HV_OK;
 }
 
@@ -491,9 +309,9 @@ int hv_ransac3_batch_dev(hv_ctx *h, const hv_ransac3_params *p, int n_sets, int 
     if (n_sets > 0 && (!n_points_dev || !prev_left_dev || !prev_right_dev || !cur_left_dev || !draws_dev || !status_dev)) return HV_ERR_INVALID;
     if (n_sets == 0) return HV_OK;
     hv::R3Args a{};
-    hv::fill_common(a, p, max_points, camera0, camera1, second_to_first);
+    hv::fill_common<3>(a, hv::six(p), max_points, camera0, camera1, second_to_first);
     a.n_points = n_points_dev; a.pl = prev_left_dev; a.pr = prev_right_dev; a.cl = cur_left_dev; a.draws = draws_dev;
-    a.status = status_dev; a.pose = pose_dev; a.summary = summary_dev;
+    a.status = status_dev; a.model = pose_dev; a.summary = summary_dev;
     hv::ScopedKernelTime tm(c, HV_K_RANSAC3);
     return hv::launch(c, n_sets, a);
 }
@@ -512,10 +330,10 @@ int hv_ransac3_lk_batch_dev(hv_ctx *h, const hv_ransac3_params *p, int n_sets, i
         return HV_ERR_INVALID;
     if (n_sets == 0) return HV_OK;
     hv::R3Args a{};
-    hv::fill_common(a, p, max_points, camera0, camera1, second_to_first);
+    hv::fill_common<3>(a, hv::six(p), max_points, camera0, camera1, second_to_first);
     a.n_points = n_points_dev; a.pl = prev_left_dev; a.pr = prev_right_dev; a.cl = cur_left_dev; a.draws = draws_dev;
     a.status = track_status_dev; a.r2_summary = r2_summary_dev; a.result = result_dev; a.score = score_dev; a.tail = 1;
-    a.pose = pose_dev; a.summary = summary_dev;
+    a.model = pose_dev; a.summary = summary_dev;
     hv::ScopedKernelTime tm(c, HV_K_RANSAC3);
     return hv::launch(c, n_sets, a);
 }
@@ -524,43 +342,10 @@ int hv_ransac3(hv_ctx *h, const hv_ransac3_params *p, int n, const float *prev_l
                const float *cur_left_xy, const hv_camera_model *camera0, const hv_camera_model *camera1,
                const double *second_to_first, const uint32_t *draws, int *status, double *pose, int *summary)
 {
-    if (n < 0) return HV_ERR_INVALID;
-    if (const int rc = hv::check_params(p, std::max(n, 1), 1)) return rc;
-    Ctx *c = hv::ctx_of(h);
-    if (!c || (n > 0 && (!prev_left_xy || !prev_right_xy || !cur_left_xy || !status)) || !camera0 || !camera1 || !second_to_first || !draws)
-        return HV_ERR_INVALID;
-    const int mp = std::max(n, 1);
-    const size_t nd = 3 * (size_t)p->ransac3MaxIterations;
-    hv::Stage s(c);
-    const auto o_pl = s.take<float>(2 * (size_t)mp), o_pr = s.take<float>(2 * (size_t)mp), o_cl = s.take<float>(2 * (size_t)mp);
-    const auto o_n = s.take<int>(1), o_st = s.take<int>(mp), o_sum = s.take<int>(4);
-    const auto o_dr = s.take<uint32_t>(nd);
-    const auto o_pose = s.take<double>(12);
-    int rc = s.reserve();
-    if (rc != HV_OK) return rc;
-    float *d_pl = s.at(o_pl), *d_pr = s.at(o_pr), *d_cl = s.at(o_cl);
-    int *d_n = s.at(o_n), *d_st = s.at(o_st), *d_sum = s.at(o_sum);
-    uint32_t *d_dr = s.at(o_dr);
-    double *d_pose = s.at(o_pose);
-    if (n > 0) {
-        HV_HIP(c, hipMemcpyAsync(d_pl, prev_left_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d_pr, prev_right_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d_cl, cur_left_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d_st, status, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    }
-    HV_HIP(c, hipMemcpyAsync(d_dr, draws, sizeof(uint32_t) * nd, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    rc = hv_ransac3_batch_dev(h, p, 1, mp, d_n, d_pl, d_pr, d_cl, camera0, camera1, second_to_first, d_dr, d_st, d_pose, d_sum);
-    if (rc != HV_OK) return rc;
-    int sm[4];
-    double ps[12];
-    if (n > 0) HV_HIP(c, hipMemcpyAsync(status, d_st, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(ps, d_pose, sizeof(ps), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(sm, d_sum, sizeof(sm), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    if (pose) for (int i = 0; i < 12; ++i) pose[i] = ps[i];
-    if (summary) for (int i = 0; i < 4; ++i) summary[i] = sm[i];
-    return HV_OK;
+    return hv::staged_entry<3>(h, hv::six(p), HV_RANSAC3_MAX_ITERS, n, prev_left_xy, prev_right_xy, cur_left_xy,
+                               camera0 && camera1 && second_to_first, nullptr, 0, draws, status, pose, summary, [&](const hv::StagedSet &d) {
+        return hv_ransac3_batch_dev(h, p, 1, d.max_points, d.n, d.pl, d.pr, d.cl, camera0, camera1, second_to_first, d.draws, d.status, d.model, d.summary);
+    });
 }
 
 }  // extern "C"

@@ -320,58 +320,51 @@ class HipRansacPipeline : public RansacPipeline {
         return true;
     }
 
-    bool doRansac3(const std::vector<std::array<const hv_camera_model *, 2>> &cameras,
-                   const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners,
-                   std::vector<Feature::Status> &trackStatus) {            // :218-272
+    // The body of doRansac3 (:218-272) and of StereoUpright2p::compute (stereo_upright_2p.cpp:110-183): a filter with samples of
+    // `sample` features, drawn from gen; call(n, previous-left, previous-right, current-left, draws, status, summary) is the library call.
+    template <class Call>
+    bool doStereoFilter(std::mt19937 &gen, unsigned sample, int maxIterations, RansacResult::Type type,
+                        const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners,
+                        std::vector<Feature::Status> &trackStatus, Call call) {
         const std::size_t n = corners[0][0]->size();
         assert(corners[1][0]->size() == n && corners[0][1]->size() == n && trackStatus.size() == n);
         initialize(ransacResult, n);
         status3.resize(n);
         for (std::size_t i = 0; i < n; ++i) status3[i] = static_cast<int>(trackStatus[i]);
-        // the next 3 * maxIterations raw outputs of a COPY of the generator; the real one advances by what the loop consumed
-        std::mt19937 ahead = rng3;
-        draws3.resize(3 * static_cast<std::size_t>(parameters.ransac3.ransac3MaxIterations));
+        // the next sample * maxIterations raw outputs of a COPY of the generator; the real one advances by what the loop consumed
+        std::mt19937 ahead = gen;
+        draws3.resize(sample * static_cast<std::size_t>(maxIterations));
         for (auto &d : draws3) d = static_cast<std::uint32_t>(ahead());
         int summary[4];
         static_assert(sizeof(Feature::Point) == 2 * sizeof(float), "Point must be two packed floats");
         auto xy = [](const std::vector<Feature::Point> *v) { return reinterpret_cast<const float *>(v->data()); };
-        session.check(hv_ransac3(session.ctx(), &parameters.ransac3, static_cast<int>(n), xy(corners[0][0]), xy(corners[1][0]),
-                                 xy(corners[0][1]), cameras[0][0], cameras[1][0], secondToFirstCamera.data(), draws3.data(),
-                                 status3.data(), nullptr, summary),
-                      "hv_ransac3");
-        rng3.discard(3ull * static_cast<unsigned long long>(summary[2]));
+        call(static_cast<int>(n), xy(corners[0][0]), xy(corners[1][0]), xy(corners[0][1]), draws3.data(), status3.data(), summary);
+        gen.discard(static_cast<unsigned long long>(sample) * static_cast<unsigned long long>(summary[2]));
         for (std::size_t i = 0; i < n; ++i) trackStatus[i] = static_cast<Feature::Status>(status3[i]);
-        if (summary[3] < 3 || summary[1] < 0) return false;                  // :253-255, 261-263
+        if (summary[3] < static_cast<int>(sample) || summary[1] < 0) return false;   // :253-255, 261-263; stereo_upright_2p.cpp:161-163, 172-174
         ransacResult.inlierCount = static_cast<std::size_t>(summary[0]);
-        ransacResult.type = RansacResult::Type::R3;
+        ransacResult.type = type;
         return true;
+    }
+
+    bool doRansac3(const std::vector<std::array<const hv_camera_model *, 2>> &cameras,
+                   const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners,
+                   std::vector<Feature::Status> &trackStatus) {
+        return doStereoFilter(rng3, 3, parameters.ransac3.ransac3MaxIterations, RansacResult::Type::R3, corners, trackStatus,
+            [&](int n, const float *pl, const float *pr, const float *cl, const std::uint32_t *draws, int *status, int *summary) {
+                session.check(hv_ransac3(session.ctx(), &parameters.ransac3, n, pl, pr, cl, cameras[0][0], cameras[1][0],
+                                         secondToFirstCamera.data(), draws, status, nullptr, summary), "hv_ransac3");
+            });
     }
 
     bool doUpright2p(const std::vector<std::array<const hv_camera_model *, 2>> &cameras,
                      const std::vector<std::array<const std::vector<Feature::Point> *, 2>> &corners, const double *poses,
-                     std::vector<Feature::Status> &trackStatus) {          // stereo_upright_2p.cpp:110-183
-        const std::size_t n = corners[0][0]->size();
-        assert(corners[1][0]->size() == n && corners[0][1]->size() == n && trackStatus.size() == n);
-        initialize(ransacResult, n);
-        status3.resize(n);
-        for (std::size_t i = 0; i < n; ++i) status3[i] = static_cast<int>(trackStatus[i]);
-        // the next 2 * maxIterations raw outputs of a COPY of the generator; the real one advances by what the loop consumed
-        std::mt19937 ahead = rngUpright;
-        draws3.resize(2 * static_cast<std::size_t>(upright2p.ransacStereoUpright2pMaxIterations));
-        for (auto &d : draws3) d = static_cast<std::uint32_t>(ahead());
-        int summary[4];
-        static_assert(sizeof(Feature::Point) == 2 * sizeof(float), "Point must be two packed floats");
-        auto xy = [](const std::vector<Feature::Point> *v) { return reinterpret_cast<const float *>(v->data()); };
-        session.check(hv_upright2p(session.ctx(), &upright2p, static_cast<int>(n), xy(corners[0][0]), xy(corners[1][0]),
-                                   xy(corners[0][1]), cameras[0][0], cameras[1][0], secondToFirstCamera.data(), poses, draws3.data(),
-                                   status3.data(), nullptr, summary),
-                      "hv_upright2p");
-        rngUpright.discard(2ull * static_cast<unsigned long long>(summary[2]));
-        for (std::size_t i = 0; i < n; ++i) trackStatus[i] = static_cast<Feature::Status>(status3[i]);
-        if (summary[3] < 2 || summary[1] < 0) return false;                  // :161-163, 172-174
-        ransacResult.inlierCount = static_cast<std::size_t>(summary[0]);
-        ransacResult.type = RansacResult::Type::UPRIGHT_2P;
-        return true;
+                     std::vector<Feature::Status> &trackStatus) {
+        return doStereoFilter(rngUpright, 2, upright2p.ransacStereoUpright2pMaxIterations, RansacResult::Type::UPRIGHT_2P, corners, trackStatus,
+            [&](int n, const float *pl, const float *pr, const float *cl, const std::uint32_t *draws, int *status, int *summary) {
+                session.check(hv_upright2p(session.ctx(), &upright2p, n, pl, pr, cl, cameras[0][0], cameras[1][0],
+                                           secondToFirstCamera.data(), poses, draws, status, nullptr, summary), "hv_upright2p");
+            });
     }
 
     void computeHybridRansac(const hv_camera_model &camera1, const hv_camera_model &camera2, bool ransac2Done) {   // :158-195

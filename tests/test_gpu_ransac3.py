@@ -204,10 +204,14 @@ def test_use_mle_off_and_other_parameters_follow_the_restatement(oracle):
     rng = np.random.default_rng(21)
     sets = [_make(rng, oracle, ocam, "pinhole", n, 0.3, 0.25, 900 + n) for n in (20, 65, 200)]
     with capi.Context(width=752, height=480) as ctx:
-        for kw in (dict(ransac3UseMle=0), dict(ransac3MinIterations=10, ransac3MaxIterations=100), dict(ransac3ErrorThresh=2.5e-5)):
+        for kw in (dict(ransac3UseMle=0), dict(ransac3MinIterations=10, ransac3MaxIterations=100),
+                   dict(ransac3MinIterations=100, ransac3MaxIterations=200),                               # more than one 64-iteration round
+                   dict(ransac3ErrorThresh=2.5e-5)):
             st, pose, sm = _run_batch(ctx, sets, gcam, params=capi.ransac3_default_params(**kw))
             for s, d in enumerate(sets):
                 ts, pr, mr = _reference(d, ocam, R.Params(**kw))
+                if kw.get("ransac3MinIterations") == 100:
+                    assert mr[3] < 3 or mr[2] > 64, (d["n"], mr)               # (by the restatement: the case spans rounds)
                 assert np.array_equal(st[s, :d["n"]], ts) and sm[s].tolist() == list(mr), (kw, d["n"], sm[s], mr)
                 assert np.abs(pose[s] - pr).max() <= 1e-9
 

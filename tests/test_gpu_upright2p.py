@@ -242,6 +242,51 @@ def test_use_mle_off_and_other_parameters_follow_the_restatement(oracle):
                 assert np.abs(model[s] - pr).max() <= 1e-9
 
 
+EDGE_COUNTS = [0, 1, 2, 3, 63, 64, 65, 128, 129, 769, 1023, 1024]
+
+
+def build_edge_sets(oracle):
+    """The sets of test_compaction_and_gather_at_the_chunk_edges, every one with its restatement result `ref`."""
+    ocam, _ = _cams(oracle, "pinhole_radial")
+    rng = np.random.default_rng(79)
+    sets = []
+    for k, n in enumerate(EDGE_COUNTS):
+        extra = 6 if n >= 63 else 0
+        base = U.make_set(rng, ocam, n - extra, 0.2, 0.0, n_diverging=extra, kind=U.ATTITUDES[k % 4], psi=rng.uniform(-math.pi, math.pi))
+        i = np.arange(n)
+        for j, mask in enumerate([np.ones(n, bool), i % 2 == 0, (i % 64 == 63) | (i == 0)]):
+            d = dict(base, n=n, status=np.where(mask, 0, 2).astype(np.int32), draws=oracle.mt19937_draws(7000 + 3 * k + j, 2 * U.MAX_ITERS))
+            d["ref"] = _reference(d, ocam)
+            sets.append(d)
+    return sets
+
+
+def edge_conditions(sets):
+    """By the restatement alone: both outcomes (run, not run) are reached, and sets where correspondences < TRACKED features."""
+    ran = {d["ref"][2][3] >= 2 for d in sets}
+    moved = sum(2 <= d["ref"][2][3] < int((d["status"] == 0).sum()) for d in sets)
+    assert ran == {True, False} and moved >= 10, (ran, moved)
+
+
+def test_compaction_and_gather_at_the_chunk_edges(oracle):
+    """The ordered compaction (TRACKED features, then correspondences) and the gather behind it at their edges: one launch of
+    hv_upright2p_batch_dev with max_points = 1024, point counts around the 64-feature chunks and the 256-thread strides, and
+    per count three masks: all TRACKED, every second feature, feature 0 and the last feature of every 64-feature chunk.
+    Noise-free sets with 20 % outliers; counts from 63 up carry six features whose triangulation is rejected, so the gather
+    moves the correspondences behind them. Every set must equal the restatement's do_upright2p, none exempted."""
+    _, gcam = _cams(oracle, "pinhole_radial")
+    sets = build_edge_sets(oracle)
+    edge_conditions(sets)
+    with capi.Context(width=752, height=480) as ctx:
+        st, model, sm = _run_batch(ctx, sets, gcam, 1024)
+    for s, d in enumerate(sets):
+        n, (ts, pr, mr) = d["n"], d["ref"]
+        print("set", s, "n", n, "tracked", int((d["status"] == 0).sum()), "summary", list(mr), "gpu", sm[s])
+        assert np.array_equal(st[s, :n], ts) and (st[s, n:] == -9).all(), (s, n)
+        assert sm[s].tolist() == list(mr), (s, n, sm[s], mr)
+        assert np.abs(model[s] - pr).max() <= 1e-9, (s, n)
+
+
 def _chain_case(oracle):
     """12 filters with distinct states and a trail of 3 poses, one 60-feature set each (sets 3 and 7: one and no TRACKED feature)."""
     import flow_predict_restatement as F
