@@ -196,6 +196,21 @@ class RngState(C.Structure):
     _fields_ = [("mt", C.c_void_p), ("pos", C.c_void_p)]
 
 
+class IntensityParams(C.Structure):
+    _fields_ = [("matchSuccessiveIntensities", C.c_double), ("matchStereoIntensities", C.c_int)]
+
+
+class IntensityState(C.Structure):
+    """hv_intensity_state: device pointers owned by the caller."""
+    _fields_ = [(k, C.c_void_p) for k in ("prev_sum", "prev_sqsum", "has_prev", "hist")]
+
+
+class IntensityRecord(C.Structure):
+    """hv_intensity_record (index 0 = left, 1 = right)."""
+    _fields_ = [(k, C.c_uint64 * 2) for k in ("in_sum", "in_sqsum", "out_sum", "out_sqsum")] + [
+        (k, C.c_double * 2) for k in ("k", "mean0", "mean")] + [("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class HvError(RuntimeError):
     pass
 
@@ -357,6 +372,12 @@ PROTOTYPES = {
     "hv_rng_seed_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RngState), C.c_uint32, C.c_void_p, C.c_void_p]),
     "hv_rng_draw_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RngState), C.c_int, C.c_void_p]),
     "hv_rng_advance_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RngState), C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "hv_intensity_default_params": (None, [C.POINTER(IntensityParams)]),
+    "hv_intensity_init_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(IntensityState)]),
+    "hv_match_intensities_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(IntensityParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.POINTER(IntensityState),
+                                                 C.c_void_p, C.c_void_p]),
+    "hv_match_intensities": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double]),
     "hv_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hv_profile_reset": (C.c_int, [C.c_void_p]),
     "hv_profile_read": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_longlong)]),
@@ -723,6 +744,31 @@ class Context:
                                                   p(discarded_dev)),
                   "hv_trail_finish_batch_dev")
 
+    # ---- intensity matching: stereo and successive-frame equalisation ----
+    def intensity_init_batch_dev(self, n_sets, state: "IntensityState"):
+        """hv_intensity_init_batch_dev: no previous frame, cleared workspace."""
+        self._chk(lib().hv_intensity_init_batch_dev(self._h, n_sets, C.byref(state)), "hv_intensity_init_batch_dev")
+
+    def match_intensities_batch_dev(self, params: "IntensityParams", n_sets, width, height, left_dev, left_image_stride, right_dev,
+                                    right_image_stride, row_stride, state: "IntensityState", active_dev=0, record_dev=0):
+        """hv_match_intensities_batch_dev: one frame of n_sets sequences, in place in the caller's gray buffers (addresses;
+        right_dev 0 = mono, active_dev [n_sets] bytes or 0, record_dev [n_sets] hv_intensity_record or 0)."""
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_match_intensities_batch_dev(self._h, C.byref(params), n_sets, width, height, p(left_dev),
+                                                       int(left_image_stride), p(right_dev), int(right_image_stride),
+                                                       int(row_stride), C.byref(state), p(active_dev), p(record_dev)),
+                  "hv_match_intensities_batch_dev")
+
+    def match_intensities(self, l: np.ndarray, r: np.ndarray, weight: float = 1.0) -> np.ndarray:
+        """hv_match_intensities: matchIntensities(l, r, weight) on one pair of host images; returns the new r (rows may be strided)."""
+        assert l.dtype == np.uint8 and r.dtype == np.uint8 and l.shape == r.shape and l.ndim == 2
+        assert l.strides[1] == 1 and r.strides[1] == 1
+        out = np.array(r, copy=True, order="C")
+        vp = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(lib().hv_match_intensities(self._h, l.shape[1], l.shape[0], vp(l), l.strides[0], vp(out), out.strides[0],
+                                             float(weight)), "hv_match_intensities")
+        return out
+
     # ---- device std::mt19937 streams: the draws of the RANSAC filters and of the shuffle ----
     def rng_seed_batch_dev(self, n_sets, rng: "RngState", seed: int = 0, seed_dev=0, reset_kind_dev=0):
         """hv_rng_seed_batch_dev: std::mt19937(seed) per set (seed_dev [n_sets] uint32 overrides `seed`); with reset_kind_dev only the
@@ -1017,6 +1063,40 @@ class Rng:
 def rng_state(n_sets: int, device="cuda") -> Rng:
     """Allocates an hv_rng (the allocator beside session_state and TrailIndex)."""
     return Rng(n_sets, device)
+
+
+class Intensity:
+    """hv_intensity_state for n_sets sequences on `device` (prev_sum / prev_sqsum int64 tensors holding the uint64 sums, has_prev
+    int32, hist [n_sets][2][256] int32 holding the uint32 counts), one hv_intensity_record per set (self.record, bytes; records()
+    decodes a download) and the pointer table (self.table). Zeroed; hv_intensity_init_batch_dev does the same on the stream."""
+
+    def __init__(self, n_sets: int, device="cuda"):
+        self.n_sets = n_sets
+        self.prev_sum = torch.zeros((n_sets,), dtype=torch.int64, device=device)
+        self.prev_sqsum = torch.zeros((n_sets,), dtype=torch.int64, device=device)
+        self.has_prev = torch.zeros((n_sets,), dtype=torch.int32, device=device)
+        self.hist = torch.zeros((n_sets, 2, 256), dtype=torch.int32, device=device)
+        self.record = torch.zeros((n_sets, C.sizeof(IntensityRecord)), dtype=torch.uint8, device=device)
+        self.table = IntensityState(self.prev_sum.data_ptr(), self.prev_sqsum.data_ptr(), self.has_prev.data_ptr(), self.hist.data_ptr())
+
+    def records(self):
+        """The records as a list of IntensityRecord (synchronising download)."""
+        raw = self.record.cpu().numpy().tobytes()
+        n = C.sizeof(IntensityRecord)
+        return [IntensityRecord.from_buffer_copy(raw[i * n:(i + 1) * n]) for i in range(self.n_sets)]
+
+
+def intensity_state(n_sets: int, device="cuda") -> Intensity:
+    """Allocates an hv_intensity_state and its records (the allocator beside rng_state)."""
+    return Intensity(n_sets, device)
+
+
+def intensity_default_params(**over) -> IntensityParams:
+    p = IntensityParams()
+    lib().hv_intensity_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
 
 
 def subpix_default_params(**over) -> SubpixParams:

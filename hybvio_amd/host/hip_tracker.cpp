@@ -556,5 +556,15 @@ std::unique_ptr<OpticalFlow> OpticalFlow::buildHip(Session &s)
     return std::unique_ptr<OpticalFlow>(new HipOpticalFlow(s));
 }
 
+namespace util {
+void matchIntensities(Session &s, const GrayImage &l, GrayImage &r, double weight)
+{
+    assert(l.data && r.data && l.width == r.width && l.height == r.height);   // util.cpp:174-175, :25
+    assert(weight >= 0.0 && weight <= 1.0);                                   // util.cpp:26
+    s.check(hv_match_intensities(s.ctx(), l.width, l.height, l.data, l.strideBytes, const_cast<std::uint8_t *>(r.data), r.strideBytes,
+                                 weight), "hv_match_intensities");
+}
+}  // namespace util
+
 }  // namespace tracker
 }  // namespace hybvio

@@ -6,6 +6,7 @@
 //   tracker::Feature::{Point,Status}                src/tracker/track.hpp:8-32
 //   tracker::SubPixelAdjuster                       src/tracker/subpixel_adjuster.hpp:10-15
 //   tracker::RansacPipeline / RansacResult          src/tracker/ransac_pipeline.hpp:15-45, ransac_result.hpp:9-33
+//   tracker::util::matchIntensities                 src/tracker/util.cpp:173-179
 //   tracker::StereoGate (no reference class)         the status rules of src/tracker/tracker.cpp:266-311, 441-478
 //   odometry::EKF                                   src/odometry/ekf.hpp:62-174
 //
@@ -324,6 +325,15 @@ public:
                                   const std::vector<Feature::Status> *detectionStatus, const hv_camera_model &camera0,
                                   const hv_camera_model &camera1) = 0;
 };
+
+// tracker::util::matchIntensities (src/tracker/util.hpp, util.cpp:173-179), the call of main.cpp:767,776: the mean and standard
+// deviation of r's intensities are moved towards l's (weight 1: onto them). l is read, r's pixels are rewritten in place -- r.data
+// must point at writable memory although GrayImage carries a pointer to const -- and a constant r stays as it is (the reference
+// asserts). One synchronous hv_match_intensities on two host images of any size; a caller with resident batches uses
+// hv_match_intensities_batch_dev, which also keeps main.cpp's prevGrayFrame on the device.
+namespace util {
+void matchIntensities(Session &session, const GrayImage &l, GrayImage &r, double weight = 1.0);
+}  // namespace util
 
 }  // namespace tracker
 

@@ -1436,6 +1436,72 @@ int hv_rng_draw_batch_dev(hv_ctx *ctx, int n_sets, const hv_rng *rng, int n_draw
 int hv_rng_advance_batch_dev(hv_ctx *ctx, int n_sets, const hv_rng *rng, const int32_t *count_dev, int count_stride,
                              int multiplier, int max_draws);
 
+/* ---- intensity matching: stereo and successive-frame equalisation -----------------------------
+ * tracker::util::matchIntensities (src/tracker/util.cpp:173-179: cv::meanStdDev of l, then setIntensities(r, r, mean, stddev,
+ * weight), util.cpp:16-52) as the command line runs it in front of everything else on every frame (src/commandline/main.cpp:763-777;
+ * options tracker.matchStereoIntensities / matchSuccessiveIntensities, codegen/parameter_definitions.c:533-534), for a batch of
+ * resident sequences. Per set:
+ * - matchSuccessiveIntensities = w > 0 (main.cpp:763-769): the left frame is matched against prevGrayFrame with weight w;
+ *   prevGrayFrame is the frame itself on the first frame (:766), and the MATCHED frame becomes the next prevGrayFrame (:768);
+ * - right_dev != NULL and matchStereoIntensities (main.cpp:770-777, useStereo && matchStereoIntensities): the right frame is
+ *   matched against the left one -- the already matched one if the first step ran -- with weight 1.
+ * setIntensities, all in binary64: stddev0 = meanStdDev(in).stddev; stddev = stddev0 + weight (stddev - stddev0); k = stddev /
+ * stddev0; mean0 = double(sum in) k / (rows cols); mean = mean0 + weight (mean - mean0); every pixel x becomes
+ * clamp((int)round(double(x) k + mean - mean0), 0, 255), round() rounding halves away from zero. cv::meanStdDev of an 8-bit
+ * image: exact integer sums, scale = 1 / N, mean = sum scale, stddev = sqrt(max(sqsum scale - mean^2, 0)) (the reference pins no
+ * OpenCV version; every 4.x source computes this). A matched pixel depends on the input byte alone, so the kernels work on
+ * 256-bin histograms and 256-entry tables, and prevGrayFrame is kept as the two exact sums of the matched frame
+ * (hv_intensity_state): tests/intensity_match_restatement.py, DESIGN.md 3.23. prevGrayFrame is a local of run_algorithm and
+ * survives Control::reset, so nothing here is tied to hv_session_reset_dev.
+ * Two cases the reference leaves open:
+ * - a constant image (stddev0 == 0): the reference asserts (util.cpp:33; Debug is its default build) and divides by zero without
+ *   asserts. Here the image is left bit for bit as it is, HV_INTENSITY_CONSTANT_* is set in the set's record, and -- for the left
+ *   frame -- its statistics still become the prev statistics;
+ * - colour frames: the command line converts them with cv::cvtColor (main.cpp:765,774-775); these entries take 8-bit gray
+ *   frames only, the conversion stays with the caller (hv_ingest_build* converts for the pyramid, not in the caller's buffer).
+ * rows * cols is an int in the reference (util.cpp:41); here the pixel count is exact for every supported size. */
+typedef struct hv_intensity_params {
+    double matchSuccessiveIntensities;   /* weight of the successive step, 0 = off (default 0.0) */
+    int matchStereoIntensities;          /* (default 0) */
+} hv_intensity_params;
+void hv_intensity_default_params(hv_intensity_params *p);   /* 0.0, 0 (parameter_definitions.c:533-534) */
+typedef struct hv_intensity_state {      /* device memory owned by the caller */
+    uint64_t *prev_sum, *prev_sqsum;     /* [n_sets] sum and squared sum of the previous matched left frame (prevGrayFrame) */
+    int32_t  *has_prev;                  /* [n_sets] 0 until the first successive step of the set */
+    uint32_t *hist;                      /* [n_sets][2][256] workspace: all zero between calls */
+} hv_intensity_state;
+enum { HV_INTENSITY_CONSTANT_LEFT = 1, HV_INTENSITY_CONSTANT_RIGHT = 2,     /* stddev0 == 0: the frame was left as it is */
+       HV_INTENSITY_MATCHED_LEFT = 4, HV_INTENSITY_MATCHED_RIGHT = 8 };     /* the frame was rewritten */
+typedef struct hv_intensity_record {     /* index 0 = left, 1 = right */
+    uint64_t in_sum[2], in_sqsum[2];     /* of the frame as given; 0 for a frame the call does not look at */
+    uint64_t out_sum[2], out_sqsum[2];   /* of the frame as left behind (= in_* unless HV_INTENSITY_MATCHED_*) */
+    double k[2], mean0[2], mean[2];      /* devDivDev0, mean0 and the blended mean of setIntensities; 1, 0, 0 unless MATCHED */
+    int32_t flags;                       /* HV_INTENSITY_* */
+    int32_t reserved;                    /* 0 */
+} hv_intensity_record;
+/* has_prev, the prev sums and the workspace := 0. Every state member must be given. */
+int hv_intensity_init_batch_dev(hv_ctx *ctx, int n_sets, const hv_intensity_state *state);
+/* One frame of n_sets sequences. The frames are the caller's gray buffers (set s at left_dev + s * left_image_stride_bytes, rows
+ * row_stride_bytes apart, likewise right_dev) and are modified in place; bytes between width and the row stride are neither read
+ * nor written. Any alignment is served; 16-byte aligned bases and strides take 16-byte loads throughout. The call runs in front
+ * of hv_pyramid_build_batch_dev or hv_ingest_build_batch_dev(channels = 1) on the same buffers and, as in the reference, before
+ * any rectifying remap. right_dev NULL = mono. active_dev [n_sets] bytes or NULL (every set): an inactive set keeps its pixels,
+ * state and record bit for bit. record_dev [n_sets] or NULL.
+ * Three launches on the context stream (histograms; tables + rewrite; state, record and the cleared workspace), timed under
+ * HV_K_INGEST, no allocation or synchronisation inside (capturable in a HIP graph); the result does not depend on scheduling.
+ * Checks made before the context is looked at: HV_ERR_INVALID for a NULL params, left_dev, state or state->hist -- and, when the
+ * successive step is on, a NULL prev_sum, prev_sqsum or has_prev --, a weight outside [0, 1], n_sets < 0, width or height < 1,
+ * row_stride_bytes < width; then HV_ERR_UNSUPPORTED for width or height above 65535 or n_sets above 65535 (a grid dimension).
+ * n_sets = 0, or neither step on (matchStereoIntensities with right_dev NULL included), returns HV_OK without a launch. */
+int hv_match_intensities_batch_dev(hv_ctx *ctx, const hv_intensity_params *params, int n_sets, int width, int height,
+                                   uint8_t *left_dev, long long left_image_stride_bytes, uint8_t *right_dev,
+                                   long long right_image_stride_bytes, int row_stride_bytes, const hv_intensity_state *state,
+                                   const unsigned char *active_dev, hv_intensity_record *record_dev);
+/* matchIntensities(l, r, weight) (util.cpp:173-179) on one pair of host images: l is read, r is rewritten in place (a constant r
+ * stays as it is). Synchronous; staged through the context's arena. weight in [0, 1] (util.cpp:26). */
+int hv_match_intensities(hv_ctx *ctx, int width, int height, const uint8_t *l_host, int l_stride_bytes, uint8_t *r_host,
+                         int r_stride_bytes, double weight);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
