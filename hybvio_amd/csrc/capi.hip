@@ -65,6 +65,21 @@ int hip_fail(Ctx *c, hipError_t e, const char *what)
     return HV_ERR_HIP;
 }
 
+// what the staging arena needs from the runtime (hv_stage.hpp): every copy of a host-pointer entry on the context's stream
+DevBuf<unsigned char> &stage_arena(Ctx *c) { return c->d_stage; }
+int stage_drain(Ctx *c) { HV_HIP(c, hipStreamSynchronize(c->stream)); return HV_OK; }
+int stage_to_device(Ctx *c, void *dst_dev, const void *src_host, size_t bytes)
+{
+    HV_HIP(c, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, c->stream));
+    return HV_OK;
+}
+int stage_to_host(Ctx *c, void *dst_host, const void *src_dev, size_t bytes)
+{
+    HV_HIP(c, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    return HV_OK;
+}
+int stage_sync(Ctx *c) { HV_HIP(c, hipStreamSynchronize(c->stream)); return HV_OK; }
+
 ScopedKernelTime::ScopedKernelTime(Ctx *c_, int id_, hipStream_t stream) : c(c_), id(id_), s(stream ? stream : c_->stream)
 {
     if (!c->profiling) return;
@@ -139,14 +154,13 @@ int compute_layout(const hv_params &p, PyrLayout &L)
     return HV_OK;
 }
 
-// staging sections of hv_klt_track for n points; hv_create reserves them for max_tracks points, so that the first frame of a
-// session allocates nothing
-struct KltStage {
-    Stage s;
+// staging sections of hv_klt_track for n points; hv_create reserves them for max_tracks points (null host arrays: carved only), so
+// that the first frame of a session allocates nothing
+struct KltStage : Stage {
     StageSection<float> prev, next, err;
     StageSection<uint8_t> status;
-    KltStage(Ctx *c, int n)
-        : s(c), prev(s.take<float>(2 * (size_t)n)), next(s.take<float>(2 * (size_t)n)), err(s.take<float>(n)), status(s.take<uint8_t>(n)) {}
+    KltStage(Ctx *c, size_t n, const float *prev_xy, float *next_xy, bool next_in, uint8_t *st, float *e)
+        : Stage(c), prev(in(prev_xy, 2 * n)), next(next_in ? inout(next_xy, 2 * n) : out(next_xy, 2 * n)), err(out(e, n)), status(out(st, n)) {}
 };
 
 bool slot_ok(Ctx *c, int s) { return s >= 0 && s < c->p.pool_size && c->slot_used[s]; }
@@ -305,7 +319,7 @@ static int init_ctx(Ctx *c, int high_priority)
     if (hipStreamSynchronize(c->stream) != hipSuccess) return HV_ERR_HIP;      // the context stream has run its first command
     c->slot_used.assign(p.pool_size, 0);
     for (int s = p.pool_size - 1; s >= 0; --s) c->free_slots.push_back(s);
-    rc = hv::KltStage(c, p.max_tracks).s.reserve();
+    rc = hv::KltStage(c, p.max_tracks, nullptr, nullptr, false, nullptr, nullptr).reserve();
     if (rc == HV_OK) rc = hv::fill_gradient_borders(c, 0, p.pool_size);
     if (rc == HV_OK) rc = hv::rot_ransac_alloc_split(c);     // (r05 advisor: once, here -- never inside a launch that may be under capture)
     if (rc == HV_OK) rc = hv::pyramid_init(c);
@@ -521,25 +535,16 @@ int hv_klt_track(hv_ctx *h, int prev_slot, int next_slot, int n, const float *pr
     if (!prev_xy || !next_xy || !status) return HV_ERR_INVALID;
     Ctx *c = &h->c;
     if (!hv::slot_ok(c, prev_slot) || !hv::slot_ok(c, next_slot)) return HV_ERR_POOL;
-    hv::KltStage ks(c, n);
-    int rc = ks.s.reserve();
+    hv::KltStage ks(c, n, prev_xy, next_xy, use_initial_flow != 0, status, err);
+    int rc = ks.upload();
     if (rc != HV_OK) return rc;
-    float *d_prev = ks.s.at(ks.prev), *d_next = ks.s.at(ks.next), *d_err = ks.s.at(ks.err);
-    uint8_t *d_status = ks.s.at(ks.status);
-    HV_HIP(c, hipMemcpyAsync(d_prev, prev_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    if (use_initial_flow)
-        HV_HIP(c, hipMemcpyAsync(d_next, next_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
     hv::IntPack pk{{prev_slot, next_slot, 0, 0}};
     hipLaunchKernelGGL(hv::set_ints_kernel, dim3(1), dim3(64), 0, c->stream, c->d_slots + 2, pk, 2);
     HV_HIP(c, hipGetLastError());
     const int iters = max_iter_override > 0 ? max_iter_override : c->p.max_iter;
-    rc = hv::launch_klt(c, 1, c->d_slots + 2, c->d_slots + 3, n, n, d_prev, d_next, d_status, err ? d_err : nullptr, use_initial_flow, iters);
-    if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(next_xy, d_next, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c->stream));
-    if (err) HV_HIP(c, hipMemcpyAsync(err, d_err, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    return HV_OK;
+    rc = hv::launch_klt(c, 1, c->d_slots + 2, c->d_slots + 3, n, n, ks.at(ks.prev), ks.at(ks.next), ks.at(ks.status), ks.at_or_null(ks.err),
+                        use_initial_flow, iters);
+    return rc != HV_OK ? rc : ks.download();
 }
 
 int hv_optical_flow_compute(hv_ctx *h, int prev_slot, int cur_slot, int n, const float *prev_corners,

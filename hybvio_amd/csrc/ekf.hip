@@ -79,6 +79,13 @@ int hv_ekf_create(hv_ctx *ctx, const hv_ekf_params *par, int batch, hv_ekf **out
     e->max_rows = n;
     const size_t nn = (size_t)n * n;
     bool ok = e->fixed.ensure(*e) == HV_OK;
+    // the context's staging arena is made to hold every SMALL section of this batch's host-pointer entries at once -- residuals
+    // [n x batch], IMU samples, the [batch] vectors -- so that only a Jacobian upload (up to n x n x batch) can still grow it
+    hv::Stage small(c);
+    const size_t B = batch;
+    small.take<double>(n * B); small.take<double>(7 * HV_EKF_MAX_PREDICT_SAMPLES * B);
+    small.take<double>(B); small.take<double>(B); small.take<int>(B); small.take<int>(B); small.take<unsigned char>(B);
+    ok = ok && small.reserve() == HV_OK;
     if (ok && hipMemset(e->fixed.err_dev, 0, sizeof(int)) != hipSuccess) ok = false;
     if (!ok) { hv_ekf_destroy(h); return HV_ERR_NOMEM; }
 
@@ -214,17 +221,15 @@ int hv_ekf_device_pointers(hv_ekf *h, double **m_dev, double **P_dev)
     return HV_OK;
 }
 
-static int stage_update_inputs(Ekf *e, int nr, int l, const double *H, const double *v, const double *rdiag,
-                               const unsigned char *active)
-{
-    Ctx *c = e->c; const size_t B = e->batch;
-    if ((size_t)nr * l * B > e->fixed.sH_cap) return HV_ERR_INVALID;
-    HV_HIP(c, hipMemcpyAsync(e->fixed.sH, H, sizeof(double) * nr * l * B, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(e->fixed.sv, v, sizeof(double) * nr * B, hipMemcpyHostToDevice, c->stream));
-    if (rdiag) HV_HIP(c, hipMemcpyAsync(e->fixed.sr, rdiag, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
-    if (active) HV_HIP(c, hipMemcpyAsync(e->fixed.sactive, active, B, hipMemcpyHostToDevice, c->stream));
-    return HV_OK;
-}
+// the staged inputs of an update launch: H [batch][nr x l], v [batch][nr], and where given R's diagonal [batch] and the flags [batch]
+namespace {
+struct UpdateStage : hv::Stage {
+    hv::StageSection<double> H, v, r;
+    hv::StageSection<unsigned char> active;
+    UpdateStage(Ekf *e, size_t nr, size_t l, const double *h_H, const double *h_v, const double *rdiag, const unsigned char *h_active)
+        : hv::Stage(e->c), H(in(h_H, nr * l * e->batch)), v(in(h_v, nr * e->batch)), r(in(rdiag, (size_t)e->batch)), active(in(h_active, (size_t)e->batch)) {}
+};
+}  // namespace
 
 int hv_ekf_update(hv_ekf *h, int nr, int l, const double *H, const double *y, const double *r_diag,
                   const unsigned char *active, int normalize_all)
@@ -232,27 +237,27 @@ int hv_ekf_update(hv_ekf *h, int nr, int l, const double *H, const double *y, co
     if (!h || !H || !y || !r_diag) return HV_ERR_INVALID;
     Ekf *e = &h->e;
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
-    int rc = stage_update_inputs(e, nr, l, H, y, r_diag, active);
+    UpdateStage u(e, nr, l, H, y, r_diag, active);
+    int rc = u.upload();
     if (rc != HV_OK) return rc;
     hv::UpdateRequest rq;
-    rq.nr = nr; rq.l = l; rq.H_dev = e->fixed.sH; rq.v_dev = e->fixed.sv; rq.rdiag_dev = e->fixed.sr; rq.mode = 1; rq.generic = 1; rq.normalize_all = normalize_all;
-    if (active) rq.active_dev = e->fixed.sactive;
+    rq.nr = nr; rq.l = l; rq.H_dev = u.at(u.H); rq.v_dev = u.at(u.v); rq.rdiag_dev = u.at(u.r); rq.mode = 1; rq.generic = 1; rq.normalize_all = normalize_all;
+    rq.active_dev = u.at_or_null(u.active);
     return hv::ekf_launch_update(e, rq);
 }
 
 int hv_ekf_visual_gate(hv_ekf *h, int nr, int l, const double *H, const double *v, double r, double *chi2, int *status)
 {
     if (!h || !H || !v) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
+    Ekf *e = &h->e;
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
-    int rc = stage_update_inputs(e, nr, l, H, v, nullptr, nullptr);
+    UpdateStage u(e, nr, l, H, v, nullptr, nullptr);
+    const auto o_chi2 = u.out(chi2, (size_t)e->batch);
+    const auto o_status = u.out(status, (size_t)e->batch);
+    int rc = u.upload();
     if (rc != HV_OK) return rc;
-    rc = hv::ekf_launch_update(e, hv::gate_request(nr, l, e->fixed.sH, e->fixed.sv, r * r * e->noise_scale, e->fixed.schi2, e->fixed.sstatus));
-    if (rc != HV_OK) return rc;
-    if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, e->fixed.schi2, sizeof(double) * e->batch, hipMemcpyDeviceToHost, c->stream));
-    if (status) HV_HIP(c, hipMemcpyAsync(status, e->fixed.sstatus, sizeof(int) * e->batch, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    return HV_OK;
+    rc = hv::ekf_launch_update(e, hv::gate_request(nr, l, u.at(u.H), u.at(u.v), r * r * e->noise_scale, u.at(o_chi2), u.at(o_status)));
+    return rc != HV_OK ? rc : u.download();
 }
 
 int hv_ekf_visual_update(hv_ekf *h, int nr, int l, const double *H, const double *v, double r, const unsigned char *active)
@@ -260,9 +265,10 @@ int hv_ekf_visual_update(hv_ekf *h, int nr, int l, const double *H, const double
     if (!h || !H || !v) return HV_ERR_INVALID;
     Ekf *e = &h->e;
     if (nr < 1 || nr > e->max_rows || l < 1 || l > e->n) return HV_ERR_INVALID;
-    int rc = stage_update_inputs(e, nr, l, H, v, nullptr, active);
+    UpdateStage u(e, nr, l, H, v, nullptr, active);
+    int rc = u.upload();
     if (rc != HV_OK) return rc;
-    return hv::ekf_launch_update(e, hv::inlier_update_request(nr, l, e->fixed.sH, e->fixed.sv, r * r * e->noise_scale, active ? e->fixed.sactive : nullptr));
+    return hv::ekf_launch_update(e, hv::inlier_update_request(nr, l, u.at(u.H), u.at(u.v), r * r * e->noise_scale, u.at_or_null(u.active)));
 }
 
 int hv_ekf_visual_dev(hv_ekf *h, int nr, int l, const double *H_dev, const double *v_dev, double r, int mode,

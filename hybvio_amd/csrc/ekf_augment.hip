@@ -425,11 +425,12 @@ int hv_ekf_augment(hv_ekf *h, const int *discarded, const unsigned char *active)
     Ekf *e = &h->e; Ctx *c = e->c;
     hv::AugmentArgs a;
     const size_t shmem = augment_fill(e, a);
-    if (discarded) {
-        if (e->batch == 1) a.dropped0 = discarded[0];
-        else { HV_HIP(c, hipMemcpyAsync(e->fixed.sdrop, discarded, sizeof(int) * e->batch, hipMemcpyHostToDevice, c->stream)); a.dropped = e->fixed.sdrop; }
-    }
-    if (active) { HV_HIP(c, hipMemcpyAsync(e->fixed.sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); a.active = e->fixed.sactive; }
+    if (discarded && e->batch == 1) { a.dropped0 = discarded[0]; discarded = nullptr; }      // an immediate, no copy
+    hv::Stage s(c);
+    const auto o_drop = s.in(discarded, (size_t)e->batch);
+    const auto o_act = s.in(active, (size_t)e->batch);
+    if (const int rc = s.upload()) return rc;
+    a.dropped = s.at_or_null(o_drop); a.active = s.at_or_null(o_act);
     if (shmem > hv::LDS_AUGMENT_LIMIT) return HV_ERR_UNSUPPORTED;      // (state vectors with map points, n > ~190, need more than the default limit)
     hv::ScopedKernelTime tm(c, HV_K_EKF_AUGMENT);
     hipLaunchKernelGGL(hv::ekf_augment_kernel<false>, dim3(e->batch), dim3(hv::AUG_THREADS), shmem, c->stream, a);
@@ -458,11 +459,12 @@ static int augment_dev_impl(hv_ekf *h, const int *discarded_dev, const unsigned 
 int hv_ekf_symmetrize_augment(hv_ekf *h, const int *discarded, const unsigned char *active)
 {
     if (!h) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
-    const int *d_drop = nullptr; const unsigned char *d_act = nullptr;
-    if (discarded) { HV_HIP(c, hipMemcpyAsync(e->fixed.sdrop, discarded, sizeof(int) * e->batch, hipMemcpyHostToDevice, c->stream)); d_drop = e->fixed.sdrop; }
-    if (active) { HV_HIP(c, hipMemcpyAsync(e->fixed.sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); d_act = e->fixed.sactive; }
-    const int rc = augment_dev_impl(h, d_drop, d_act, true);
+    Ekf *e = &h->e;
+    hv::Stage s(e->c);
+    const auto o_drop = s.in(discarded, (size_t)e->batch);
+    const auto o_act = s.in(active, (size_t)e->batch);
+    if (const int rc = s.upload()) return rc;
+    const int rc = augment_dev_impl(h, s.at_or_null(o_drop), s.at_or_null(o_act), true);
     if (rc != HV_ERR_UNSUPPORTED) return rc;
     // (map-point states: the folded kernel's LDS limit; the two calls it stands for)
     const int rc2 = hv_ekf_symmetrize(h);
@@ -476,8 +478,10 @@ int hv_ekf_undo_augment(hv_ekf *h, const unsigned char *active)
 {
     if (!h) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
-    hv::ShiftArgs a{e->n, e->map_dim, e->fixed.m, e->fixed.P, e->fixed.P1, e->fixed.m1, nullptr};
-    if (active) { HV_HIP(c, hipMemcpyAsync(e->fixed.sactive, active, e->batch, hipMemcpyHostToDevice, c->stream)); a.active = e->fixed.sactive; }
+    hv::Stage s(c);
+    const auto o_act = s.in(active, (size_t)e->batch);
+    if (const int rc = s.upload()) return rc;
+    hv::ShiftArgs a{e->n, e->map_dim, e->fixed.m, e->fixed.P, e->fixed.P1, e->fixed.m1, s.at_or_null(o_act)};
     hv::ScopedKernelTime tm(c, HV_K_EKF_AUGMENT);
     hipLaunchKernelGGL(hv::ekf_unaugment_kernel, dim3(e->batch), dim3(1024), 0, c->stream, a);
     HV_HIP(c, hipGetLastError());

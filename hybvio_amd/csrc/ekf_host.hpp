@@ -1,6 +1,7 @@
 // Host side of the EKF shared by the kernel families (ekf_predict.hip, ekf_update.hip, ekf_gate.hip, ekf_augment.hip: kernels, their
-// launchers, the one-launch entries), ekf.hip (create / destroy, accessors) and ekf_visit.hip (track visits, frame loops, host-pointer
-// staging): the filter object, the launch requests. Plain C++ and HIP host types, no kernel.
+// launchers, the one-launch entries), ekf.hip (create / destroy, accessors) and ekf_visit.hip (track visits, frame loops): the filter
+// object, the launch requests. Plain C++ and HIP host types, no kernel. The filter owns no staging: its host-pointer entries stage
+// through hv::Stage in the arena of its context (hv_stage.hpp), as every other host-pointer entry of the library does.
 #pragma once
 #include "hv_internal.hpp"
 
@@ -18,10 +19,6 @@ struct Ekf {
     // allocated by hv_ekf_create, never regrown
     struct Fixed {
         DevBuf<double> m, P, P1, m1, Q, dydx, ws;             // state
-        DevBuf<double> sH, sv, sr, schi2, simu;               // staging for host-pointer calls
-        DevBuf<int> sstatus, sdrop;
-        DevBuf<unsigned char> sactive;
-        size_t sH_cap = 0;
         DevBuf<int> err_dev;                                  // device error word (UpdateArgs::err)
         DevBuf<int> visit_counts, visit_lists;                // compaction lists of a visit: counts {inliers short, long records, inliers long}, lists 3 x [batch]
         DevBuf<int> visit_order;                              // [VISIT_SLOTS][batch] launch_visit_order of the running frame loop, valid while visit_order_ok
@@ -29,10 +26,8 @@ struct Ekf {
         int ensure(const Ekf &e)
         {
             const size_t n = e.n, B = e.batch, nn = n * n;
-            sH_cap = nn * B;
             if (m.alloc(n * B) || P.alloc(nn * B) || P1.alloc(nn * B) || m1.alloc(n * B) || Q.alloc(144 * B) || dydx.alloc(400 * B) ||
-                ws.alloc((2 * n + 1) * n * B) || sH.alloc(sH_cap) || sv.alloc(n * B) || sr.alloc(B) || schi2.alloc(B) ||
-                simu.alloc(7 * HV_EKF_MAX_PREDICT_SAMPLES * B) || sstatus.alloc(B) || sdrop.alloc(B) || sactive.alloc(B) || err_dev.alloc(1) ||
+                ws.alloc((2 * n + 1) * n * B) || err_dev.alloc(1) ||
                 visit_counts.alloc(4 * (VISIT_SLOTS + 1)) || visit_order.alloc(VISIT_SLOTS * B) || visit_long.alloc(VISIT_SLOTS * B) ||
                 visit_long_count.alloc(VISIT_SLOTS) || visit_lists.alloc(3 * B)) return HV_ERR_NOMEM;
             return HV_OK;
@@ -40,17 +35,19 @@ struct Ekf {
     } fixed;
 
     // one track visit (hv_ekf_visual_track_dev, row f3): dense or compact Jacobians and residuals of `cap_rows` rows per filter, regrown
-    // when a longer track arrives; once: point, active flags, the compact Jacobians' column lists, per-filter rows of a ragged visit
+    // when a longer track arrives; once: point, active flags, the compact Jacobians' column lists, per-filter rows of a ragged visit,
+    // and the hybrid visit's apply mask (hv_ekf_visual_track_hybrid_dev: the filters whose track still takes updateVisualTrack,
+    // written by ekf_hybrid_insert_kernel and read by the update behind it; nothing else uses it)
     struct VisitBufs {
         DevBuf<double> H, v; int cap_rows = 0;
-        DevBuf<double> pf; DevBuf<unsigned char> active; DevBuf<int> acol, rec_rows;
+        DevBuf<double> pf; DevBuf<unsigned char> active, apply; DevBuf<int> acol, rec_rows;
         int ensure(const Ekf &e, int rows)
         {
             if (cap_rows >= rows) return HV_OK;
             const size_t n = e.n, B = e.batch;
             cap_rows = 0;
             if (const int rc = grow_buffers(e.c, {e.c->stream}, {{H, rows * n * B}, {v, rows * B}})) return rc;
-            if (pf.alloc_once(3 * B) || active.alloc_once(B) || acol.alloc_once(n * B) || rec_rows.alloc_once(B)) return HV_ERR_NOMEM;
+            if (pf.alloc_once(3 * B) || active.alloc_once(B) || apply.alloc_once(B) || acol.alloc_once(n * B) || rec_rows.alloc_once(B)) return HV_ERR_NOMEM;
             cap_rows = rows;
             return HV_OK;
         }

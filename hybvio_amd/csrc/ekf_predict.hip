@@ -715,16 +715,22 @@ static int predict_common(Ekf *e, const double *dt_dev, const double *gyro_dev, 
     return HV_OK;
 }
 
+// the samples of every filter staged in the context's arena: dt [n_samples x batch], gyro and acc [n_samples x batch][3]
+static int predict_staged(Ekf *e, int n_samples, const double *dt, const double *gyro, const double *acc)
+{
+    const size_t nB = (size_t)n_samples * e->batch;
+    hv::Stage s(e->c);
+    const auto o_dt = s.in(dt, nB), o_g = s.in(gyro, 3 * nB), o_a = s.in(acc, 3 * nB);
+    if (const int rc = s.upload()) return rc;
+    return predict_common(e, s.at(o_dt), s.at(o_g), s.at(o_a), 0.0, nullptr, nullptr, n_samples);
+}
+
 int hv_ekf_predict(hv_ekf *h, const double *dt, const double *gyro, const double *acc)
 {
     if (!h || !dt || !gyro || !acc) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
+    Ekf *e = &h->e;
     if (e->batch == 1) return predict_common(e, nullptr, nullptr, nullptr, dt[0], gyro, acc);   // immediates, no copy
-    const size_t B = e->batch;
-    HV_HIP(c, hipMemcpyAsync(e->fixed.simu, dt, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(e->fixed.simu + B, gyro, sizeof(double) * 3 * B, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(e->fixed.simu + 4 * B, acc, sizeof(double) * 3 * B, hipMemcpyHostToDevice, c->stream));
-    return predict_common(e, e->fixed.simu, e->fixed.simu + B, e->fixed.simu + 4 * B, 0.0, nullptr, nullptr);
+    return predict_staged(e, 1, dt, gyro, acc);
 }
 
 int hv_ekf_predict_dev(hv_ekf *h, const double *dt_dev, const double *gyro_dev, const double *acc_dev)
@@ -736,14 +742,9 @@ int hv_ekf_predict_dev(hv_ekf *h, const double *dt_dev, const double *gyro_dev, 
 int hv_ekf_predict_n(hv_ekf *h, int n_samples, const double *dt, const double *gyro, const double *acc)
 {
     if (!h || n_samples < 1 || n_samples > HV_EKF_MAX_PREDICT_SAMPLES || !dt || !gyro || !acc) return HV_ERR_INVALID;
-    Ekf *e = &h->e; Ctx *c = e->c;
+    Ekf *e = &h->e;
     if (n_samples == 1 && e->batch == 1) return predict_common(e, nullptr, nullptr, nullptr, dt[0], gyro, acc);
-    const size_t nB = (size_t)n_samples * e->batch;
-    double *d_dt = e->fixed.simu, *d_g = e->fixed.simu + nB, *d_a = e->fixed.simu + 4 * nB;
-    HV_HIP(c, hipMemcpyAsync(d_dt, dt, sizeof(double) * nB, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_g, gyro, sizeof(double) * 3 * nB, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_a, acc, sizeof(double) * 3 * nB, hipMemcpyHostToDevice, c->stream));
-    return predict_common(e, d_dt, d_g, d_a, 0.0, nullptr, nullptr, n_samples);
+    return predict_staged(e, n_samples, dt, gyro, acc);
 }
 
 int hv_ekf_predict_n_dev(hv_ekf *h, int n_samples, const double *dt_dev, const double *gyro_dev, const double *acc_dev)

@@ -230,9 +230,9 @@ int hv_ekf_visual_track_hybrid_dev(hv_ekf *h, const hv_vu_params *p, int np, con
     rc = hv::ekf_launch_update(e, hv::gate_request(rows, e->n, e->visit.H, e->visit.v, r_gate * r_gate * ns, chi2_dev, gate_status_dev, e->visit.active));
     if (rc != HV_OK) return rc;
     hipLaunchKernelGGL(hv::ekf_hybrid_insert_kernel, dim3(e->batch), dim3(256), 0, c->stream, e->n, e->n - e->map_dim, e->fixed.m, e->fixed.P, e->visit.active,
-                       gate_status_dev, map_update_dev, map_offer_dev, pf, e->fixed.sactive);
+                       gate_status_dev, map_update_dev, map_offer_dev, pf, e->visit.apply);
     HV_HIP(c, hipGetLastError());
-    return hv::ekf_launch_update(e, hv::inlier_update_request(rows, e->n, e->visit.H, e->visit.v, r_update * r_update * ns, e->fixed.sactive, gate_status_dev));
+    return hv::ekf_launch_update(e, hv::inlier_update_request(rows, e->n, e->visit.H, e->visit.v, r_update * r_update * ns, e->visit.apply, gate_status_dev));
 }
 
 // What the launch sequences of one visit share (visual_track_dev_impl): the shape, the thresholds, the compaction lists, the outputs.
@@ -765,57 +765,29 @@ int hv_ekf_visual_frame_batch_dev(hv_ekf *h, const hv_vu_params *p, int n_tracks
     return HV_OK;
 }
 
-// Device staging of the host-pointer entries in the context's arena (hv::Stage): the eight shared sections
-//     idx | features | velocities | y | status | gate | chi2 | pf
-// for B records of np poses, behind whatever sections of its own the entry took from `stage` before upload(); the four inputs are
-// uploaded here, the four outputs come back through download()
-struct TrackStage {
-    hv::Stage stage;
-    size_t B = 0;
-    int *idx = nullptr, *st = nullptr, *gs = nullptr;
-    double *feat = nullptr, *vel = nullptr, *y = nullptr, *chi = nullptr, *pf = nullptr;
-    explicit TrackStage(Ctx *c) : stage(c) {}
-
-    int upload(size_t B_, int np, bool stereo, const int *h_idx, const double *h_feat, const double *h_vel, const double *h_y)
-    {
-        Ctx *c = stage.c;
-        B = B_;
-        const size_t nt = (size_t)np * (stereo ? 2 : 1);
-        const auto o_idx = stage.take<int>(B * np), o_st = stage.take<int>(B * 2), o_gs = stage.take<int>(B);
-        const auto o_feat = stage.take<double>(B * nt * 2), o_vel = stage.take<double>(B * nt * 2), o_y = stage.take<double>(B * nt * 2);
-        const auto o_chi = stage.take<double>(B), o_pf = stage.take<double>(B * 3);
-        if (const int rc = stage.reserve()) return rc;
-        idx = stage.at(o_idx); st = stage.at(o_st); gs = stage.at(o_gs);
-        feat = stage.at(o_feat); vel = stage.at(o_vel); y = stage.at(o_y); chi = stage.at(o_chi); pf = stage.at(o_pf);
-        HV_HIP(c, hipMemcpyAsync(idx, h_idx, B * np * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(feat, h_feat, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(vel, h_vel, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(y, h_y, B * nt * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        return HV_OK;
-    }
-    // ... then the entry's own counters (n_cnt ints at d_cnt, optional) and the synchronise
-    int download(int *status, int *gate_status, double *chi2, double *h_pf, int *counts = nullptr, const int *d_cnt = nullptr, size_t n_cnt = 0) const
-    {
-        Ctx *c = stage.c;
-        HV_HIP(c, hipMemcpyAsync(status, st, B * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HV_HIP(c, hipMemcpyAsync(gate_status, gs, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        if (chi2) HV_HIP(c, hipMemcpyAsync(chi2, chi, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (h_pf) HV_HIP(c, hipMemcpyAsync(h_pf, pf, B * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (counts) HV_HIP(c, hipMemcpyAsync(counts, d_cnt, n_cnt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HV_HIP(c, hipStreamSynchronize(c->stream));
-        return HV_OK;
-    }
+// Staging of the host-pointer track entries (hv::Stage): the eight sections they share, for B records of np poses,
+//     idx | status | gate | features | velocities | y | chi2 | pf
+// four inputs and four outputs; an entry declares its own sections behind them, then upload() ... download()
+namespace {
+struct TrackStage : hv::Stage {
+    hv::StageSection<int> idx, st, gs;
+    hv::StageSection<double> feat, vel, y, chi, pf;
+    TrackStage(Ctx *c, size_t B, int np, bool stereo, const int *h_idx, const double *h_feat, const double *h_vel, const double *h_y,
+               int *status, int *gate_status, double *chi2, double *h_pf)
+        : hv::Stage(c), idx(in(h_idx, B * np)), st(out(status, B * 2)), gs(out(gate_status, B)), feat(in(h_feat, B * np * (stereo ? 4 : 2))),
+          vel(in(h_vel, B * np * (stereo ? 4 : 2))), y(in(h_y, B * np * (stereo ? 4 : 2))), chi(out(chi2, B)), pf(out(h_pf, B * 3)) {}
 };
+}  // namespace
 
 int hv_ekf_visual_track(hv_ekf *h, const hv_vu_params *p, int np, const int *idx, const double *feat, const double *vel,
                         const double *y, double r_gate, double r_update, int *status, int *gate_status, double *chi2, double *pf)
 {
     if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2) return HV_ERR_INVALID;
     Ekf *e = &h->e;
-    TrackStage s(e->c);
-    int rc = s.upload((size_t)e->batch, np, p->useStereo != 0, idx, feat, vel, y);
-    if (rc == HV_OK) rc = hv_ekf_visual_track_dev(h, p, np, s.idx, s.feat, s.vel, s.y, r_gate, r_update, s.st, s.gs, s.chi, s.pf);
-    return rc != HV_OK ? rc : s.download(status, gate_status, chi2, pf);
+    TrackStage t(e->c, (size_t)e->batch, np, p->useStereo != 0, idx, feat, vel, y, status, gate_status, chi2, pf);
+    int rc = t.upload();
+    if (rc == HV_OK) rc = hv_ekf_visual_track_dev(h, p, np, t.at(t.idx), t.at(t.feat), t.at(t.vel), t.at(t.y), r_gate, r_update, t.at(t.st), t.at(t.gs), t.at(t.chi), t.at(t.pf));
+    return rc != HV_OK ? rc : t.download();
 }
 
 // batch_rows: 0 = the sequential visit loop (visual_frame_dev_impl); != 0 = the batchVisualUpdate loop with this max_update_rows (< 0: the
@@ -828,17 +800,17 @@ static int visual_frame_host_impl(hv_ekf *h, const hv_vu_params *p, int n_tracks
     if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2 || n_tracks < 1) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
     const size_t B = (size_t)e->batch * n_tracks;
-    TrackStage s(c);                                               // own sections: success counts [batch] | pose counts [B]
-    const auto o_cnt = s.stage.take<int>(e->batch), o_np = s.stage.take<int>(B);
-    int rc = s.upload(B, np, p->useStereo != 0, idx, feat, vel, y);
+    TrackStage t(c, B, np, p->useStereo != 0, idx, feat, vel, y, status, gate_status, chi2, pf);
+    const auto o_cnt = t.out(success_count, (size_t)e->batch);   // own sections: success counts [batch] | pose counts [B]
+    const auto o_np = t.in(n_poses, B);
+    int rc = t.upload();
     if (rc != HV_OK) return rc;
-    int *d_cnt = s.stage.at(o_cnt), *d_np = n_poses ? s.stage.at(o_np) : nullptr;
-    if (n_poses) HV_HIP(c, hipMemcpyAsync(d_np, n_poses, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
     rc = batch_rows == 0
-        ? visual_frame_dev_impl(h, p, n_tracks, np, d_np, s.idx, s.feat, s.vel, s.y, r_gate, r_update, s.st, s.gs, s.chi, s.pf, d_cnt, max_successful)
-        : hv_ekf_visual_frame_batch_dev(h, p, n_tracks, np, d_np, s.idx, s.feat, s.vel, s.y, r_gate, r_update, s.st, s.gs, s.chi, s.pf, d_cnt, max_successful,
-                                        batch_rows < 0 ? 0 : batch_rows);
-    if (rc == HV_OK) rc = s.download(status, gate_status, chi2, pf, success_count, d_cnt, (size_t)e->batch);
+        ? visual_frame_dev_impl(h, p, n_tracks, np, t.at_or_null(o_np), t.at(t.idx), t.at(t.feat), t.at(t.vel), t.at(t.y), r_gate, r_update, t.at(t.st), t.at(t.gs), t.at(t.chi),
+                                t.at(t.pf), t.at(o_cnt), max_successful)
+        : hv_ekf_visual_frame_batch_dev(h, p, n_tracks, np, t.at_or_null(o_np), t.at(t.idx), t.at(t.feat), t.at(t.vel), t.at(t.y), r_gate, r_update, t.at(t.st), t.at(t.gs),
+                                        t.at(t.chi), t.at(t.pf), t.at(o_cnt), max_successful, batch_rows < 0 ? 0 : batch_rows);
+    if (rc == HV_OK) rc = t.download();
     if (rc != HV_OK) return rc;
     int flags = 0;
     const int rc2 = hv_ekf_frame_error(h, &flags);                // the hand-shake form of the speculative pass never fails silently
@@ -879,15 +851,13 @@ int hv_ekf_visual_track_hybrid(hv_ekf *h, const hv_vu_params *p, int np, const i
     if (!h || !p || !idx || !feat || !vel || !y || !status || !gate_status || np < 2) return HV_ERR_INVALID;
     Ekf *e = &h->e; Ctx *c = e->c;
     const size_t B = (size_t)e->batch;
-    TrackStage s(c);                                               // own sections: map_update [B] | map_offer [B]
-    const auto o_mu = s.stage.take<int>(B), o_mo = s.stage.take<int>(B);
-    int rc = s.upload(B, np, p->useStereo != 0, idx, feat, vel, y);
+    TrackStage t(c, B, np, p->useStereo != 0, idx, feat, vel, y, status, gate_status, chi2, pf);
+    const auto o_mu = t.in(map_update, B), o_mo = t.in(map_offer, B);       // own sections: map_update [B] | map_offer [B]
+    int rc = t.upload();
     if (rc != HV_OK) return rc;
-    int *d_mu = map_update ? s.stage.at(o_mu) : nullptr, *d_mo = map_offer ? s.stage.at(o_mo) : nullptr;
-    if (map_update) HV_HIP(c, hipMemcpyAsync(d_mu, map_update, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    if (map_offer) HV_HIP(c, hipMemcpyAsync(d_mo, map_offer, B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    rc = hv_ekf_visual_track_hybrid_dev(h, p, np, s.idx, s.feat, s.vel, s.y, d_mu, d_mo, r_gate, r_update, s.st, s.gs, s.chi, s.pf);
-    return rc != HV_OK ? rc : s.download(status, gate_status, chi2, pf);
+    rc = hv_ekf_visual_track_hybrid_dev(h, p, np, t.at(t.idx), t.at(t.feat), t.at(t.vel), t.at(t.y), t.at_or_null(o_mu), t.at_or_null(o_mo), r_gate, r_update, t.at(t.st),
+                                        t.at(t.gs), t.at(t.chi), t.at(t.pf));
+    return rc != HV_OK ? rc : t.download();
 }
 
 }  // extern "C"

@@ -638,15 +638,14 @@ int hv_gftt_detect(hv_ctx *ctx, const hv_gftt_params *p, int slot, const float *
     if (capacity < 2 * nk) return HV_ERR_INVALID;
     *n_out = 0;
     if (nk == 0) return HV_OK;
+    std::vector<float> kp(3 * (size_t)nk);
     hv::Stage s(c);
-    const auto o_kp = s.take<float>(3 * (size_t)nk);
-    int rc = s.reserve();
+    const auto o_kp = s.out(kp.data(), kp.size());
+    int rc = s.upload();
     if (rc != HV_OK) return rc;
     rc = hv::launch(c, 1, nullptr, slot, hv_gftt_block_size(p), p->gfttMinResponse, p->gfttBlockSize, s.at(o_kp));
+    if (rc == HV_OK) rc = s.download();
     if (rc != HV_OK) return rc;
-    std::vector<float> kp(3 * (size_t)nk);
-    HV_HIP(c, hipMemcpyAsync(kp.data(), s.at(o_kp), sizeof(float) * 3 * nk, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
     // detect(): stable sort by descending response, then corners.resize(n) + push_back (n zero points first)
     std::vector<int> order(nk);
     for (int i = 0; i < nk; ++i) order[i] = i;

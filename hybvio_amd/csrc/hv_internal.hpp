@@ -8,6 +8,7 @@
 
 #include "../../include/hybvio_hip.h"
 #include "dev_buf.hpp"
+#include "hv_stage.hpp"
 
 namespace hv {
 
@@ -90,7 +91,7 @@ struct CtxBuffers {
     DevBuf<const uint8_t *> d_l0_ptr;     // [pool_size]
     DevBuf<int> d_l0_stride;              // [pool_size]
     DevBuf<int> d_slots;                  // [4] slot numbers written by set_ints_kernel: [0] the slot of a one-slot pyramid build, [2] / [3] the pair of hv_klt_track
-    // device staging of every synchronous host-pointer entry point: one block (count() = its bytes), carved per call through Stage (below)
+    // device staging of every synchronous host-pointer entry point: one block (count() = its bytes), carved per call through Stage (hv_stage.hpp)
     DevBuf<unsigned char> d_stage;
     // ingest (f2): per-camera remap tables
     DevBuf<uint32_t> d_map_xy[HV_INGEST_CAMERAS];
@@ -134,31 +135,6 @@ inline int grow_buffers(Ctx *c, std::initializer_list<hipStream_t> drain, std::i
 {
     return grow_buffers([&]() -> int { for (hipStream_t s : drain) HV_HIP(c, hipStreamSynchronize(s)); return HV_OK; }, slots);
 }
-
-// Staging of one host-pointer call in the context's arena (Ctx::d_stage): take() every section, reserve() once, then at() for the
-// device pointers. Sections are 16-byte aligned and never overlap; the arena at least doubles when it grows.
-// Invariant: every user copies into, launches on and reads back from the arena on c->stream only, so successive calls are ordered by
-// that stream (hv_ingest_build, which returns before its kernel has read the arena, included); growth drains c->stream before it
-// frees, and hv_set_stream drains the old stream before it swaps. A forked visit (ekf_visit.hip) reads uploaded sections on
-// aux_stream, but joins c->stream again inside the visit, in front of the entry's download and synchronise.
-template <class T> struct StageSection { size_t off; };
-struct Stage {
-    Ctx *c; size_t total = 0;
-    explicit Stage(Ctx *ctx) : c(ctx) {}
-    template <class T> StageSection<T> take(size_t count)
-    {
-        const StageSection<T> s{total};
-        total += (count * sizeof(T) + 15) & ~(size_t)15;
-        return s;
-    }
-    int reserve()
-    {
-        const size_t have = c->d_stage.count();
-        if (total <= have) return HV_OK;
-        return grow_buffers(c, {c->stream}, {{c->d_stage, total > 2 * have ? total : 2 * have}});
-    }
-    template <class T> T *at(StageSection<T> s) const { return reinterpret_cast<T *>(c->d_stage + s.off); }
-};
 
 // RAII-ish per-launch timing helper (no-op unless profiling is on).
 struct ScopedKernelTime {

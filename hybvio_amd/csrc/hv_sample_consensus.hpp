@@ -296,32 +296,18 @@ int staged_entry(hv_ctx *h, const ScParams &p, int iters_limit, int n, const flo
         return HV_ERR_INVALID;
     const int mp = std::max(n, 1);
     const size_t nd = SAMPLE * (size_t)p.max_iters;
+    const bool any = n > 0;                                       // (n == 0: one-point sections, nothing of the caller's arrays read or written)
     Stage s(c);
-    const auto o_pl = s.take<float>(2 * (size_t)mp), o_pr = s.take<float>(2 * (size_t)mp), o_cl = s.take<float>(2 * (size_t)mp);
-    const auto o_n = s.take<int>(1), o_st = s.take<int>(mp), o_sum = s.take<int>(4);
-    const auto o_dr = s.take<uint32_t>(nd);
-    const auto o_model = s.take<double>(12), o_extra = s.take<double>(n_extra);
-    int rc = s.reserve();
+    const auto o_pl = s.in(any ? prev_left_xy : nullptr, 2 * (size_t)mp), o_pr = s.in(any ? prev_right_xy : nullptr, 2 * (size_t)mp);
+    const auto o_cl = s.in(any ? cur_left_xy : nullptr, 2 * (size_t)mp);
+    const auto o_n = s.in(&n, 1);
+    const auto o_st = s.inout(any ? status : nullptr, mp);
+    const auto o_sum = s.out(summary, 4);
+    const auto o_dr = s.in(draws, nd);
+    const auto o_model = s.out(model, 12);
+    const auto o_extra = s.in(extra, n_extra);
+    int rc = s.upload();
     if (rc != HV_OK) return rc;
-    const StagedSet d{mp, s.at(o_n), s.at(o_st), s.at(o_sum), s.at(o_pl), s.at(o_pr), s.at(o_cl), s.at(o_dr), s.at(o_model), s.at(o_extra)};
-    if (n > 0) {
-        HV_HIP(c, hipMemcpyAsync(d.pl, prev_left_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d.pr, prev_right_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d.cl, cur_left_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d.status, status, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    }
-    HV_HIP(c, hipMemcpyAsync(d.draws, draws, sizeof(uint32_t) * nd, hipMemcpyHostToDevice, c->stream));
-    if (n_extra) HV_HIP(c, hipMemcpyAsync(d.extra, extra, sizeof(double) * n_extra, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d.n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    rc = batch(d);
-    if (rc != HV_OK) return rc;
-    int sm[4];
-    double ps[12];
-    if (n > 0) HV_HIP(c, hipMemcpyAsync(status, d.status, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(ps, d.model, sizeof(ps), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(sm, d.summary, sizeof(sm), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    if (model) for (int i = 0; i < 12; ++i) model[i] = ps[i];
-    if (summary) for (int i = 0; i < 4; ++i) summary[i] = sm[i];
-    return HV_OK;
+    rc = batch(StagedSet{mp, s.at(o_n), s.at(o_st), s.at(o_sum), s.at(o_pl), s.at(o_pr), s.at(o_cl), s.at(o_dr), s.at(o_model), s.at(o_extra)});
+    return rc != HV_OK ? rc : s.download();
 }

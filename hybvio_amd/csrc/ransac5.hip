@@ -777,31 +777,16 @@ int hv_ransac5(hv_ctx *h, const hv_ransac5_params *p, int n, const float *c1, co
     Ctx *c = hv::ctx_of(h);
     if (!c || (n > 0 && (!c1 || !c2 || !status)) || !cam1 || !cam2) return HV_ERR_INVALID;
     const int mp = std::max(n, 1);
+    const bool any = n > 0;                                       // (n == 0: one-point sections, nothing of the caller's arrays read or written)
     hv::Stage s(c);
-    const auto o_c1 = s.take<float>(2 * (size_t)mp), o_c2 = s.take<float>(2 * (size_t)mp);
-    const auto o_n = s.take<int>(1), o_st = s.take<int>(mp), o_sum = s.take<int>(4);
-    const auto o_E = s.take<double>(9);
-    int rc = s.reserve();
+    const auto o_c1 = s.in(any ? c1 : nullptr, 2 * (size_t)mp), o_c2 = s.in(any ? c2 : nullptr, 2 * (size_t)mp);
+    const auto o_n = s.in(&n, 1);
+    const auto o_st = s.out(any ? status : nullptr, mp), o_sum = s.out(summary, 4);
+    const auto o_E = s.out(E, 9);
+    int rc = s.upload();
     if (rc != HV_OK) return rc;
-    float *d_c1 = s.at(o_c1), *d_c2 = s.at(o_c2);
-    int *d_n = s.at(o_n), *d_st = s.at(o_st), *d_sum = s.at(o_sum);
-    double *d_E = s.at(o_E);
-    if (n > 0) {
-        HV_HIP(c, hipMemcpyAsync(d_c1, c1, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d_c2, c2, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    }
-    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    rc = hv_ransac5_batch_dev(h, p, 1, mp, d_n, d_c1, d_c2, cam1, cam2, d_st, d_E, d_sum);
-    if (rc != HV_OK) return rc;
-    int sm[4];
-    if (n > 0) HV_HIP(c, hipMemcpyAsync(status, d_st, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    double e[9];
-    HV_HIP(c, hipMemcpyAsync(e, d_E, sizeof(e), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(sm, d_sum, sizeof(sm), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    if (E) for (int i = 0; i < 9; ++i) E[i] = e[i];
-    if (summary) for (int i = 0; i < 4; ++i) summary[i] = sm[i];
-    return HV_OK;
+    rc = hv_ransac5_batch_dev(h, p, 1, mp, s.at(o_n), s.at(o_c1), s.at(o_c2), cam1, cam2, s.at(o_st), s.at(o_E), s.at(o_sum));
+    return rc != HV_OK ? rc : s.download();
 }
 
 }  // extern "C"

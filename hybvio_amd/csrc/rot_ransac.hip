@@ -448,24 +448,17 @@ int hv_rot_ransac(hv_ctx *h, int n, const float *c1, const float *c2, const hv_c
 {
     Ctx *c = hv::ctx_of(h);
     if (!c || n < 2 || n > hv::MAX_PTS || !c1 || !c2 || !pairs || !status || !cam1 || !cam2) return HV_ERR_INVALID;
-    hv::Stage s(c);
-    const auto o_c1 = s.take<float>(2 * (size_t)n), o_c2 = s.take<float>(2 * (size_t)n), o_R = s.take<float>(9);
-    const auto o_pairs = s.take<int>(2 * hv::HYP), o_n = s.take<int>(1), o_st = s.take<int>(n), o_sum = s.take<int>(2);
-    int rc = s.reserve();
-    if (rc != HV_OK) return rc;
-    float *d_c1 = s.at(o_c1), *d_c2 = s.at(o_c2), *d_R = s.at(o_R);
-    int *d_pairs = s.at(o_pairs), *d_n = s.at(o_n), *d_st = s.at(o_st), *d_sum = s.at(o_sum);
-    HV_HIP(c, hipMemcpyAsync(d_c1, c1, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_c2, c2, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_pairs, pairs, sizeof(int) * 2 * hv::HYP, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    rc = hv_rot_ransac_batch_dev(h, 1, n, d_n, d_c1, d_c2, cam1, cam2, d_pairs, threshold_pow2, d_st, d_R, d_sum);
-    if (rc != HV_OK) return rc;
     int summary[2] = {0, 0};
-    HV_HIP(c, hipMemcpyAsync(status, d_st, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    if (R) HV_HIP(c, hipMemcpyAsync(R, d_R, sizeof(float) * 9, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipMemcpyAsync(summary, d_sum, sizeof(summary), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
+    hv::Stage s(c);
+    const auto o_c1 = s.in(c1, 2 * (size_t)n), o_c2 = s.in(c2, 2 * (size_t)n);
+    const auto o_R = s.out(R, 9);
+    const auto o_pairs = s.in(pairs, 2 * hv::HYP), o_n = s.in(&n, 1);
+    const auto o_st = s.out(status, n), o_sum = s.out(summary, 2);
+    int rc = s.upload();
+    if (rc != HV_OK) return rc;
+    rc = hv_rot_ransac_batch_dev(h, 1, n, s.at(o_n), s.at(o_c1), s.at(o_c2), cam1, cam2, s.at(o_pairs), threshold_pow2, s.at(o_st), s.at(o_R), s.at(o_sum));
+    if (rc == HV_OK) rc = s.download();
+    if (rc != HV_OK) return rc;
     if (best_inlier_count) *best_inlier_count = summary[0];
     if (hypotheses_visited) *hypotheses_visited = summary[1];
     return HV_OK;

@@ -304,32 +304,17 @@ int hv_track_gate(hv_ctx *h, const hv_stereo_gate_params *p, int n, const float 
     Ctx *c = hv::ctx_of(h);
     if (!c) return HV_ERR_INVALID;
     if (n == 0) return HV_OK;
-    const bool stereo = second_corners != nullptr;
-    const size_t xy = sizeof(float) * 2 * (size_t)n, st = sizeof(int32_t) * (size_t)n;
+    const size_t N = (size_t)n;
     hv::Stage s(c);
-    const auto o_n = s.take<int>(1);
-    const auto o_c = s.take<float>(2 * (size_t)n), o_s = s.take<float>(2 * (size_t)n);
-    const auto o_ss = s.take<int32_t>(n), o_ts = s.take<int32_t>(n);
-    const auto o_bl = s.take<uint8_t>(n);
-    int rc = s.reserve();
+    const auto o_n = s.in(&n, 1);
+    const auto o_c = s.in(corners, 2 * N), o_s = s.in(second_corners, 2 * N);
+    const auto o_ss = s.in(stereo_status, N), o_ts = s.inout(track_status, N);
+    const auto o_bl = s.in(blacklist, N);
+    int rc = s.upload();
     if (rc != HV_OK) return rc;
-    int *d_n = s.at(o_n);
-    float *d_c = s.at(o_c), *d_s = stereo ? s.at(o_s) : nullptr;
-    int32_t *d_ss = stereo ? s.at(o_ss) : nullptr, *d_ts = s.at(o_ts);
-    uint8_t *d_bl = blacklist ? s.at(o_bl) : nullptr;
-    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_c, corners, xy, hipMemcpyHostToDevice, c->stream));
-    if (stereo) {
-        HV_HIP(c, hipMemcpyAsync(d_s, second_corners, xy, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d_ss, stereo_status, st, hipMemcpyHostToDevice, c->stream));
-    }
-    if (blacklist) HV_HIP(c, hipMemcpyAsync(d_bl, blacklist, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_ts, track_status, st, hipMemcpyHostToDevice, c->stream));
-    rc = hv_track_gate_batch_dev(h, p, 1, n, d_n, d_c, d_s, d_ss, d_bl, camera0, camera1, d_ts, nullptr);
-    if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(track_status, d_ts, st, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    return HV_OK;
+    rc = hv_track_gate_batch_dev(h, p, 1, n, s.at(o_n), s.at(o_c), s.at_or_null(o_s), s.at_or_null(o_ss), s.at_or_null(o_bl), camera0, camera1,
+                                 s.at(o_ts), nullptr);
+    return rc != HV_OK ? rc : s.download();
 }
 
 int hv_detection_filter(hv_ctx *h, const hv_stereo_gate_params *p, int n, const float *corners, const float *second_corners,
@@ -343,35 +328,29 @@ int hv_detection_filter(hv_ctx *h, const hv_stereo_gate_params *p, int n, const 
     if (!c) return HV_ERR_INVALID;
     if (n == 0) { *n_out = 0; return HV_OK; }
     const bool stereo = second_corners != nullptr;
-    const size_t xy = sizeof(float) * 2 * (size_t)n, st = sizeof(int32_t) * (size_t)n;
+    const size_t N = (size_t)n;
     hv::Stage s(c);
-    const auto o_n = s.take<int>(1), o_no = s.take<int>(1);
-    const auto o_c = s.take<float>(2 * (size_t)n), o_s = s.take<float>(2 * (size_t)n);
-    const auto o_oc = s.take<float>(2 * (size_t)n), o_os = s.take<float>(2 * (size_t)n);
-    const auto o_ss = s.take<int32_t>(n), o_st = s.take<int32_t>(n);
-    int rc = s.reserve();
+    const auto o_n = s.in(&n, 1), o_no = s.take<int>(1);
+    const auto o_c = s.in(corners, 2 * N), o_s = s.in(second_corners, 2 * N);
+    const auto o_oc = s.take<float>(2 * N), o_os = s.take<float>(2 * N);      // (downloaded below, once the count is known)
+    const auto o_ss = s.in(stereo_status, N), o_st = s.out(status, N);
+    int rc = s.upload();
     if (rc != HV_OK) return rc;
-    int *d_n = s.at(o_n), *d_no = s.at(o_no);
-    float *d_c = s.at(o_c), *d_s = stereo ? s.at(o_s) : nullptr, *d_oc = s.at(o_oc), *d_os = stereo ? s.at(o_os) : nullptr;
-    int32_t *d_ss = stereo ? s.at(o_ss) : nullptr, *d_st = s.at(o_st);
-    HV_HIP(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HV_HIP(c, hipMemcpyAsync(d_c, corners, xy, hipMemcpyHostToDevice, c->stream));
-    if (stereo) {
-        HV_HIP(c, hipMemcpyAsync(d_s, second_corners, xy, hipMemcpyHostToDevice, c->stream));
-        HV_HIP(c, hipMemcpyAsync(d_ss, stereo_status, st, hipMemcpyHostToDevice, c->stream));
-    }
-    rc = hv_detection_filter_batch_dev(h, p, 1, n, d_n, d_c, d_s, d_ss, camera0, camera1, d_st, d_oc, d_os, d_no);
+    rc = hv_detection_filter_batch_dev(h, p, 1, n, s.at(o_n), s.at(o_c), s.at_or_null(o_s), s.at_or_null(o_ss), camera0, camera1, s.at(o_st),
+                                       s.at(o_oc), stereo ? s.at(o_os) : nullptr, s.at(o_no));
     if (rc != HV_OK) return rc;
     int cnt = 0;
-    HV_HIP(c, hipMemcpyAsync(&cnt, d_no, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
+    rc = s.fetch(&cnt, o_no, 1);
+    if (rc == HV_OK) rc = s.sync();
+    if (rc != HV_OK) return rc;
     if (cnt < 0 || cnt > n) return HV_ERR_HIP;
     if (cnt > 0) {
-        HV_HIP(c, hipMemcpyAsync(out_corners, d_oc, sizeof(float) * 2 * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
-        if (stereo) HV_HIP(c, hipMemcpyAsync(out_second, d_os, sizeof(float) * 2 * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        rc = s.fetch(out_corners, o_oc, 2 * (size_t)cnt);
+        if (rc == HV_OK && stereo) rc = s.fetch(out_second, o_os, 2 * (size_t)cnt);
+        if (rc != HV_OK) return rc;
     }
-    if (status) HV_HIP(c, hipMemcpyAsync(status, d_st, st, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
+    rc = s.download();
+    if (rc != HV_OK) return rc;
     *n_out = cnt;
     return HV_OK;
 }

@@ -241,19 +241,12 @@ int hv_corner_subpix(hv_ctx *ctx, const hv_subpix_params *p, int slot, int n, fl
     if (rc != HV_OK) return rc;
     if (n == 0) return HV_OK;
     hv::Stage s(c);
-    const auto o_xy = s.take<float>(2 * (size_t)n);
-    const auto o_it = s.take<int>(n);
-    rc = s.reserve();
+    const auto o_xy = s.inout(xy, 2 * (size_t)n);
+    const auto o_it = s.out(iters, n);
+    rc = s.upload();
     if (rc != HV_OK) return rc;
-    float *d_xy = s.at(o_xy);
-    int *d_it = s.at(o_it);
-    HV_HIP(c, hipMemcpyAsync(d_xy, xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    rc = hv::launch(c, p, 1, nullptr, slot, n, nullptr, n, d_xy, d_it);
-    if (rc != HV_OK) return rc;
-    HV_HIP(c, hipMemcpyAsync(xy, d_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (iters) HV_HIP(c, hipMemcpyAsync(iters, d_it, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HV_HIP(c, hipStreamSynchronize(c->stream));
-    return HV_OK;
+    rc = hv::launch(c, p, 1, nullptr, slot, n, nullptr, n, s.at(o_xy), s.at(o_it));
+    return rc != HV_OK ? rc : s.download();
 }
 
 int hv_corner_subpix_batch_dev(hv_ctx *ctx, const hv_subpix_params *p, int n_sets, const int *slots_dev, int max_points,
