@@ -74,6 +74,10 @@ class GfttParams(C.Structure):
                 ("maxTracks", C.c_int)]
 
 
+class FastParams(C.Structure):
+    _fields_ = [("threshold", C.c_int), ("maxTracks", C.c_int)]
+
+
 class SubpixParams(C.Structure):
     _fields_ = [("subPixWindowSize", C.c_int), ("subPixMaxIter", C.c_int), ("subPixEpsilon", C.c_double)]
 
@@ -312,6 +316,16 @@ PROTOTYPES = {
     "hv_gftt_detect_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(GfttParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hv_apply_min_distance": (None, [f32p, C.POINTER(C.c_int), f32p, C.c_int, C.c_int, C.c_int]),
+    "hv_fast_default_params": (None, [C.POINTER(FastParams)]),
+    "hv_fast_tile_size": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hv_fast_keypoint_bound": (C.c_int, [C.c_void_p]),
+    "hv_fast_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "hv_fast_keypoints_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(FastParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p]),
+    "hv_fast_detect_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(FastParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hv_fast_detect": (C.c_int, [C.c_void_p, C.POINTER(FastParams), C.c_int, f32p, C.c_int, C.c_int, f32p, C.c_int,
+                                 C.POINTER(C.c_int)]),
     "hv_subpix_default_params": (None, [C.POINTER(SubpixParams)]),
     "hv_corner_subpix": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_int, f32p, i32p]),
     "hv_corner_subpix_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -916,6 +930,41 @@ class Context:
         fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int]
         self._chk(fn(self._h, C.c_void_p(x_dev), C.c_void_p(y_dev), int(n), int(bool(wide))), "hv_debug_gftt_sqrt")
 
+    # -- FAST feature detector --
+    def fast_keypoint_bound(self) -> int:
+        """hv_fast_keypoint_bound: a max_keypoints no image of this context can exceed."""
+        return int(lib().hv_fast_keypoint_bound(self._h))
+
+    def fast_work_bytes(self, n_images: int) -> int:
+        return int(lib().hv_fast_work_bytes(self._h, int(n_images)))
+
+    def fast_detect(self, slot: int, prev=(), mask_radius: int = 1, params: "FastParams" = None):
+        """FeatureDetector::detect of the FAST detector on the level-0 image of a built pyramid slot -> corners [n, 2]."""
+        fp = params if params is not None else fast_default_params()
+        cap = max(min(fp.maxTracks, self.fast_keypoint_bound()), 0)
+        out = np.zeros((max(cap, 1), 2), np.float32)
+        pv = np.ascontiguousarray(prev, np.float32).reshape(-1, 2)
+        n = C.c_int(0)
+        self._chk(lib().hv_fast_detect(self._h, C.byref(fp), slot, _p(pv, f32p) if len(pv) else None, len(pv), int(mask_radius),
+                                       _p(out, f32p), cap, C.byref(n)), "hv_fast_detect")
+        return out[:n.value].copy()
+
+    def fast_keypoints_batch_dev(self, n_images, slots_dev, work_dev, max_keypoints, kp_dev, n_kp_dev, params: "FastParams" = None):
+        """hv_fast_keypoints_batch_dev: kp_dev [n_images][max_keypoints][3] = (x, y, score) in row-major order, counts in n_kp_dev."""
+        fp = params if params is not None else fast_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_fast_keypoints_batch_dev(self._h, C.byref(fp), n_images, p(slots_dev), p(work_dev), max_keypoints, p(kp_dev),
+                                                    p(n_kp_dev)), "hv_fast_keypoints_batch_dev")
+
+    def fast_detect_batch_dev(self, n_images, slots_dev, work_dev, max_keypoints, kp_dev, n_kp_dev, max_prev, n_prev_dev, prev_dev,
+                              mask_radius_dev, max_corners, corners_dev, n_out_dev, params: "FastParams" = None):
+        """hv_fast_detect_batch_dev: score map, track mask, stable sort by score and the min-distance walk on the context stream."""
+        fp = params if params is not None else fast_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_fast_detect_batch_dev(self._h, C.byref(fp), n_images, p(slots_dev), p(work_dev), max_keypoints, p(kp_dev),
+                                                 p(n_kp_dev), max_prev, p(n_prev_dev), p(prev_dev), p(mask_radius_dev), max_corners,
+                                                 p(corners_dev), p(n_out_dev)), "hv_fast_detect_batch_dev")
+
     # -- sub-pixel corner refinement --
     def corner_subpix(self, slot: int, xy, params: "SubpixParams" = None):
         """SubPixelAdjuster::adjust on the level-0 image of a built pyramid slot -> (refined xy [n, 2], position updates [n])."""
@@ -1097,6 +1146,21 @@ def intensity_default_params(**over) -> IntensityParams:
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def fast_default_params(**over) -> FastParams:
+    p = FastParams()
+    lib().hv_fast_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def fast_tile_size() -> tuple:
+    """(width, height) of the FAST score kernel's tile, as the library was built (hv_fast_tile_size)."""
+    w, h = C.c_int(), C.c_int()
+    lib().hv_fast_tile_size(C.byref(w), C.byref(h))
+    return w.value, h.value
 
 
 def subpix_default_params(**over) -> SubpixParams:

@@ -24,8 +24,9 @@
 // detect_tail_kernel<false> (hv_apply_min_distance_batch_dev): steps 3 and 4 on a caller's list, in place (an accepted corner is
 // written at an index not above its own, and the chunk it belongs to is in registers by then).
 // The distance test is the reference's binary32 expression, two rounded products and one rounded sum, strict `<` against
-// (float)(r * r): the library is built with -ffp-contract=off and the function below also switches contraction off itself.
+// (float)(r * r): the library is built with -ffp-contract=off and the function (hv_min_distance.hpp) also switches contraction off itself.
 #include "hv_internal.hpp"
+#include "hv_min_distance.hpp"
 
 #include <algorithm>
 
@@ -49,21 +50,7 @@ struct TailArgs {
     int *n_out;                  // [sets]
 };
 
-__device__ __forceinline__ bool within(float ax, float ay, float bx, float by, float r2)
-{
-#pragma clang fp contract(off)
-    const float dx = ax - bx, dy = ay - by;
-    const float xx = dx * dx, yy = dy * dy;
-    return xx + yy < r2;
-}
-
-// orders the LDS accesses of one wavefront (the hardware runs them in issue order; this keeps the compiler from moving them)
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
+// within() (the distance test, shared with fast.hip) and wave_sync(): hv_min_distance.hpp
 
 // descending response, ties (-0.0 == +0.0 included) equal
 __device__ __forceinline__ uint32_t response_key(float r)

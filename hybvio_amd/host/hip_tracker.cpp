@@ -59,7 +59,7 @@ void FeatureDetector::applyMinDistance(std::vector<Feature::Point> &corners, con
     int n = (int)corners.size();
     hv_apply_min_distance(reinterpret_cast<float *>(corners.data()), &n,
                           reinterpret_cast<const float *>(prevCorners.data()), (int)prevCorners.size(),
-                          minDistance, parameters.maxTracks);
+                          minDistance, maxTracks);
     corners.resize((size_t)n);
 }
 
@@ -196,6 +196,27 @@ public:
         session.check(hv_gftt_detect(session.ctx(), &parameters, imagePyramid.deviceSlot(),
                                       reinterpret_cast<const float *>(prevCorners.data()), (int)prevCorners.size(),
                                       maskRadius, reinterpret_cast<float *>(corners.data()), 2 * nk, &n), "hv_gftt_detect");
+        corners.resize((size_t)n);
+    }
+};
+
+// Counterpart of the legacy FAST detector (src/tracker/feature_detector_legacy.cpp:141-174 behind MaskedFeatureDetector, :20-83, and
+// the tail of FeatureDetector::detect): segment test, suppression, track mask, stable sort and applyMinDistance inside hv_fast_detect.
+class HipFastFeatureDetector : public FeatureDetector {
+    Session &session;
+    const hv_fast_params fast;
+public:
+    HipFastFeatureDetector(Session &s, const hv_fast_params &p) : FeatureDetector(p.maxTracks), session(s), fast(p) {}
+    void detect(ImagePyramid &imagePyramid, std::vector<Feature::Point> &corners,
+                const std::vector<Feature::Point> &prevCorners, int maskRadius) final {
+        const int bound = hv_fast_keypoint_bound(session.ctx());
+        assert(bound >= 0 && maskRadius >= 1);                             // feature_detector_legacy.cpp:72
+        const int cap = std::min(fast.maxTracks, bound);
+        corners.assign((size_t)std::max(cap, 0), Feature::Point{0.f, 0.f});
+        int n = 0;
+        session.check(hv_fast_detect(session.ctx(), &fast, imagePyramid.deviceSlot(),
+                                      reinterpret_cast<const float *>(prevCorners.data()), (int)prevCorners.size(),
+                                      maskRadius, reinterpret_cast<float *>(corners.data()), cap, &n), "hv_fast_detect");
         corners.resize((size_t)n);
     }
 };
@@ -539,6 +560,11 @@ std::unique_ptr<Undistorter> Undistorter::buildRectifiedHip(Session &s, int came
 std::unique_ptr<FeatureDetector> FeatureDetector::buildHip(Session &s, const hv_gftt_params &p)
 {
     return std::unique_ptr<FeatureDetector>(new HipFeatureDetector(s, p));
+}
+
+std::unique_ptr<FeatureDetector> FeatureDetector::buildHipFast(Session &s, const hv_fast_params &p)
+{
+    return std::unique_ptr<FeatureDetector>(new HipFastFeatureDetector(s, p));
 }
 
 std::unique_ptr<SubPixelAdjuster> SubPixelAdjuster::buildHip(Session &s, const hv_subpix_params &p)

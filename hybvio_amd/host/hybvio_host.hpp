@@ -181,6 +181,10 @@ struct OpticalFlow {         // src/tracker/optical_flow.hpp:20-40
 class FeatureDetector {
 public:
     static std::unique_ptr<FeatureDetector> buildHip(Session &session, const hv_gftt_params &parameters);   // sibling of build()
+    // featureDetector "FAST" (feature_detector.cpp:659-680, feature_detector_legacy.cpp:141-174): cv::FastFeatureDetector behind the
+    // track mask, stable sort by response and applyMinDistance, all inside hv_fast_detect; supportsAsync() is false, as the legacy
+    // detector's is
+    static std::unique_ptr<FeatureDetector> buildHipFast(Session &session, const hv_fast_params &parameters);
     virtual ~FeatureDetector();
     virtual void detect(
         ImagePyramid &imagePyramid,
@@ -195,8 +199,10 @@ public:
         int minDistance) const;
 
 protected:
-    explicit FeatureDetector(const hv_gftt_params &parameters) : parameters(parameters) {}
+    explicit FeatureDetector(const hv_gftt_params &parameters) : parameters(parameters), maxTracks(parameters.maxTracks) {}
+    explicit FeatureDetector(int maxTracks) : parameters{}, maxTracks(maxTracks) {}   // a detector with parameters of its own
     const hv_gftt_params parameters;
+    const int maxTracks;                    // where applyMinDistance stops, whichever parameter struct it came from
 };
 
 // tracker::SubPixelAdjuster (src/tracker/subpixel_adjuster.hpp:10-15): cv::cornerSubPix on the detected corners, refined

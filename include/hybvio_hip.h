@@ -477,6 +477,56 @@ int hv_gftt_detect_batch_dev(hv_ctx *ctx, const hv_gftt_params *p, int n_images,
                              int max_prev, const int *n_prev_dev, const float *prev_dev, const int *mask_radius_dev,
                              int max_corners, float *corners_dev, int *n_out_dev);
 
+/* ---- FAST feature detector: segment test, score, non-max suppression, track mask, detect() tail (added within ABI 4) ------
+ * Replaces tracker::FeatureDetector with featureDetector "FAST" (src/tracker/feature_detector.cpp:659-680 FeatureDetector::build;
+ * src/tracker/feature_detector_legacy.cpp:141-174 CustomFastFeatureDetector = cv::FastFeatureDetector, FAST-9 on the 16-pixel
+ * circle with non-max suppression; :20-51, :70-83 MaskedFeatureDetector::detect / setMask / drawMask; :177-213 applyMinDistance;
+ * codegen/parameter_definitions.c:310-311) on the level-0 image of pyramid slots. The rules, restated in
+ * tests/fast_restatement.py (written from the algorithm; not pinned against an OpenCV build):
+ *   corner   a pixel v, 3 <= x <= w - 4, 3 <= y <= h - 4, with 9 consecutive circle pixels all > v + threshold or all < v - threshold;
+ *   score    the largest threshold at which it still is one (threshold .. 254); kept when strictly above its 8 neighbours' scores;
+ *   mask     every live track (px, py) with 0 < px < w and 0 < py < h (binary32; NaN draws nothing) removes the key points in
+ *            columns [max(ix - r, 0), min(ix + r, w - 1)) and the like rows, ix = (int)px: the upper end is exclusive;
+ *   tail     std::stable_sort by descending score (equal scores keep row-major order; no zero prefix, that is GPU-GFTT's alone),
+ *            then applyMinDistance(corners, {}, maskRadius) stopped at maxTracks, the distance test of the section above.
+ * Everything is asynchronous on the context stream with no allocation or synchronisation inside (capturable in a HIP graph),
+ * two launches per call, timed under HV_K_GFTT (score map) and HV_K_DETECT_TAIL (mask, counting sort, walk).
+ * Checks made before the context is looked at: HV_ERR_INVALID for NULL required pointers, negative sizes, maxTracks < 1,
+ * threshold outside 0 .. 255 or max_corners < min(maxTracks, max_keypoints) (hv_fast_detect also for mask_radius < 1); then
+ * HV_ERR_UNSUPPORTED for n_images > 65535, max_prev > HV_DETECT_TAIL_MAX_PREV or maxTracks > HV_DETECT_TAIL_MAX_TRACKS.
+ * Counts read from device memory are clamped to their capacity. The radius is device data: a set with mask_radius_dev[s] < 1
+ * (where the reference asserts) writes no row and reports n_kp_dev[s] = n_out_dev[s] = -1. An image with more key points than
+ * max_keypoints, or whose slot is no valid slot (or holds no image), reports n_kp_dev[s] = -1 and n_out_dev[s] = -1 and writes
+ * no row either: it is never truncated, because the sort would then pick other corners. max_keypoints =
+ * hv_fast_keypoint_bound() cannot overflow. With the context: HV_ERR_UNSUPPORTED for images of more than about 2^27 pixels
+ * ((w + 259) * h > 2^27; the select kernel's packed indices). A context that runs both detectors reads the sums of both under
+ * HV_K_GFTT and HV_K_DETECT_TAIL. */
+#define HV_FAST_TILE_W 64   /* the score kernel's tile (one workgroup); tests place their cases across its seams */
+#define HV_FAST_TILE_H 16
+typedef struct hv_fast_params {
+    int threshold;   /* 10: cv::FastFeatureDetector::create() */
+    int maxTracks;   /* 200: applyMinDistance stops after this many corners (parameter_definitions.c:262) */
+} hv_fast_params;
+void hv_fast_default_params(hv_fast_params *p);
+void hv_fast_tile_size(int *tile_w, int *tile_h);      /* HV_FAST_TILE_W, HV_FAST_TILE_H as the library was built */
+int hv_fast_keypoint_bound(hv_ctx *ctx);               /* ceil((w-6)/2) * ceil((h-6)/2): suppressed key points are never 8-adjacent */
+size_t hv_fast_work_bytes(hv_ctx *ctx, int n_images);  /* the score maps, one byte per pixel (the histograms stay in LDS) */
+/* cv::FastFeatureDetector::detect without a mask: kp_dev [n_images][max_keypoints][3] = (x, y, score) in row-major order (y, then
+ * x, ascending), n_kp_dev [n_images]; work_dev: hv_fast_work_bytes(ctx, n_images) bytes, 16-byte aligned. */
+int hv_fast_keypoints_batch_dev(hv_ctx *ctx, const hv_fast_params *p, int n_images, const int *slots_dev, void *work_dev,
+                                int max_keypoints, float *kp_dev, int *n_kp_dev);
+/* FeatureDetector::detect of the FAST detector, no host step. kp_dev / n_kp_dev: by-product, the key points that survived the
+ * mask, in sorted order. prev_dev [n_images][max_prev][2] with n_prev_dev [n_images] (both NULL allowed when max_prev == 0),
+ * mask_radius_dev [n_images], corners_dev [n_images][max_corners][2], n_out_dev [n_images]. */
+int hv_fast_detect_batch_dev(hv_ctx *ctx, const hv_fast_params *p, int n_images, const int *slots_dev, void *work_dev,
+                             int max_keypoints, float *kp_dev, int *n_kp_dev, int max_prev, const int *n_prev_dev,
+                             const float *prev_dev, const int *mask_radius_dev, int max_corners, float *corners_dev,
+                             int *n_out_dev);
+/* One image, host pointers, synchronous (staged through the context's arena, hv_stage.hpp): capacity >= min(maxTracks,
+ * hv_fast_keypoint_bound()) corners (HV_ERR_INVALID below it); HV_ERR_POOL for a slot that is not in use or holds no image. */
+int hv_fast_detect(hv_ctx *ctx, const hv_fast_params *p, int slot, const float *prev_xy, int n_prev, int mask_radius,
+                   float *corners_xy, int capacity, int *n_out);
+
 /* ---- sub-pixel corner refinement (added within ABI 4) ----------------------------------------
  * Replaces tracker::SubPixelAdjuster::adjust (src/tracker/subpixel_adjuster.cpp:18-42): cv::cornerSubPix(image, corners,
  * Size(win, win), Size(-1, -1), TermCriteria(COUNT | EPS, maxIter, epsilon)) on the level-0 image of a pyramid slot, then
