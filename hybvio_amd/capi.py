@@ -78,6 +78,10 @@ class FastParams(C.Structure):
     _fields_ = [("threshold", C.c_int), ("maxTracks", C.c_int)]
 
 
+class GfttLegacyParams(C.Structure):
+    _fields_ = [("gfttBlockSize", C.c_int), ("gfttQualityLevel", C.c_double), ("gfttMinDistance", C.c_double), ("maxTracks", C.c_int)]
+
+
 class SubpixParams(C.Structure):
     _fields_ = [("subPixWindowSize", C.c_int), ("subPixMaxIter", C.c_int), ("subPixEpsilon", C.c_double)]
 
@@ -326,6 +330,18 @@ PROTOTYPES = {
                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hv_fast_detect": (C.c_int, [C.c_void_p, C.POINTER(FastParams), C.c_int, f32p, C.c_int, C.c_int, f32p, C.c_int,
                                  C.POINTER(C.c_int)]),
+    "hv_gftt_legacy_default_params": (None, [C.POINTER(GfttLegacyParams)]),
+    "hv_gftt_legacy_tile_size": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hv_gftt_legacy_min_distance": (C.c_double, [C.c_void_p, C.POINTER(GfttLegacyParams)]),
+    "hv_gftt_legacy_keypoint_bound": (C.c_int, [C.c_void_p]),
+    "hv_gftt_legacy_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "hv_gftt_legacy_keypoints_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(GfttLegacyParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hv_gftt_legacy_detect_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(GfttLegacyParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    "hv_gftt_legacy_detect": (C.c_int, [C.c_void_p, C.POINTER(GfttLegacyParams), C.c_int, f32p, C.c_int, C.c_int, f32p, C.c_int,
+                                        C.POINTER(C.c_int)]),
     "hv_subpix_default_params": (None, [C.POINTER(SubpixParams)]),
     "hv_corner_subpix": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_int, f32p, i32p]),
     "hv_corner_subpix_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -965,6 +981,49 @@ class Context:
                                                  p(n_kp_dev), max_prev, p(n_prev_dev), p(prev_dev), p(mask_radius_dev), max_corners,
                                                  p(corners_dev), p(n_out_dev)), "hv_fast_detect_batch_dev")
 
+    # -- legacy GFTT feature detector (cv::goodFeaturesToTrack behind the track mask) --
+    def gftt_legacy_min_distance(self, params: "GfttLegacyParams" = None) -> float:
+        """hv_gftt_legacy_min_distance: gfttMinDistance * (min(w, h) / 720.0), binary64."""
+        gp = params if params is not None else gftt_legacy_default_params()
+        return float(lib().hv_gftt_legacy_min_distance(self._h, C.byref(gp)))
+
+    def gftt_legacy_keypoint_bound(self) -> int:
+        """hv_gftt_legacy_keypoint_bound: a max_keypoints no image of this context can exceed."""
+        return int(lib().hv_gftt_legacy_keypoint_bound(self._h))
+
+    def gftt_legacy_work_bytes(self, n_images: int, max_keypoints: int) -> int:
+        return int(lib().hv_gftt_legacy_work_bytes(self._h, int(n_images), int(max_keypoints)))
+
+    def gftt_legacy_detect(self, slot: int, prev=(), mask_radius: int = 1, params: "GfttLegacyParams" = None):
+        """MaskedFeatureDetector::detect of the GFTT detector on the level-0 image of a built pyramid slot -> corners [n, 2]."""
+        gp = params if params is not None else gftt_legacy_default_params()
+        cap = max(min(gp.maxTracks, self.gftt_legacy_keypoint_bound()), 0)
+        out = np.zeros((max(cap, 1), 2), np.float32)
+        pv = np.ascontiguousarray(prev, np.float32).reshape(-1, 2)
+        n = C.c_int(0)
+        self._chk(lib().hv_gftt_legacy_detect(self._h, C.byref(gp), slot, _p(pv, f32p) if len(pv) else None, len(pv), int(mask_radius),
+                                              _p(out, f32p), cap, C.byref(n)), "hv_gftt_legacy_detect")
+        return out[:n.value].copy()
+
+    def gftt_legacy_keypoints_batch_dev(self, n_images, slots_dev, work_dev, max_keypoints, n_cand_dev, max_corners, corners_dev,
+                                        resp_dev, n_out_dev, params: "GfttLegacyParams" = None):
+        """hv_gftt_legacy_keypoints_batch_dev: cv::goodFeaturesToTrack with no mask on the context stream."""
+        gp = params if params is not None else gftt_legacy_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_gftt_legacy_keypoints_batch_dev(self._h, C.byref(gp), n_images, p(slots_dev), p(work_dev), max_keypoints,
+                                                           p(n_cand_dev), max_corners, p(corners_dev), p(resp_dev), p(n_out_dev)),
+                  "hv_gftt_legacy_keypoints_batch_dev")
+
+    def gftt_legacy_detect_batch_dev(self, n_images, slots_dev, work_dev, max_keypoints, n_cand_dev, max_prev, n_prev_dev, prev_dev,
+                                     mask_radius_dev, max_corners, corners_dev, resp_dev, n_out_dev, params: "GfttLegacyParams" = None):
+        """hv_gftt_legacy_detect_batch_dev: track mask, response, masked maximum, candidates, order and the min-distance walk."""
+        gp = params if params is not None else gftt_legacy_default_params()
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_gftt_legacy_detect_batch_dev(self._h, C.byref(gp), n_images, p(slots_dev), p(work_dev), max_keypoints,
+                                                        p(n_cand_dev), max_prev, p(n_prev_dev), p(prev_dev), p(mask_radius_dev),
+                                                        max_corners, p(corners_dev), p(resp_dev), p(n_out_dev)),
+                  "hv_gftt_legacy_detect_batch_dev")
+
     # -- sub-pixel corner refinement --
     def corner_subpix(self, slot: int, xy, params: "SubpixParams" = None):
         """SubPixelAdjuster::adjust on the level-0 image of a built pyramid slot -> (refined xy [n, 2], position updates [n])."""
@@ -1160,6 +1219,21 @@ def fast_tile_size() -> tuple:
     """(width, height) of the FAST score kernel's tile, as the library was built (hv_fast_tile_size)."""
     w, h = C.c_int(), C.c_int()
     lib().hv_fast_tile_size(C.byref(w), C.byref(h))
+    return w.value, h.value
+
+
+def gftt_legacy_default_params(**over) -> GfttLegacyParams:
+    p = GfttLegacyParams()
+    lib().hv_gftt_legacy_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def gftt_legacy_tile_size() -> tuple:
+    """(width, height) of the legacy GFTT kernels' tile, as the library was built (hv_gftt_legacy_tile_size)."""
+    w, h = C.c_int(), C.c_int()
+    lib().hv_gftt_legacy_tile_size(C.byref(w), C.byref(h))
     return w.value, h.value
 
 

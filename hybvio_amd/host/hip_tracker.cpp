@@ -221,6 +221,27 @@ public:
     }
 };
 
+// Counterpart of the legacy GFTT detector (src/tracker/feature_detector_legacy.cpp:53-139 behind MaskedFeatureDetector, :20-51):
+// track mask, cv::goodFeaturesToTrack's response, threshold, local maxima, order and minimum-distance walk inside hv_gftt_legacy_detect.
+class HipGfttLegacyFeatureDetector : public FeatureDetector {
+    Session &session;
+    const hv_gftt_legacy_params gftt;
+public:
+    HipGfttLegacyFeatureDetector(Session &s, const hv_gftt_legacy_params &p) : FeatureDetector(p.maxTracks), session(s), gftt(p) {}
+    void detect(ImagePyramid &imagePyramid, std::vector<Feature::Point> &corners,
+                const std::vector<Feature::Point> &prevCorners, int maskRadius) final {
+        const int bound = hv_gftt_legacy_keypoint_bound(session.ctx());
+        assert(bound >= 0 && maskRadius >= 1);                             // feature_detector_legacy.cpp:36
+        const int cap = std::min(gftt.maxTracks, bound);
+        corners.assign((size_t)std::max(cap, 0), Feature::Point{0.f, 0.f});
+        int n = 0;
+        session.check(hv_gftt_legacy_detect(session.ctx(), &gftt, imagePyramid.deviceSlot(),
+                                             reinterpret_cast<const float *>(prevCorners.data()), (int)prevCorners.size(),
+                                             maskRadius, reinterpret_cast<float *>(corners.data()), cap, &n), "hv_gftt_legacy_detect");
+        corners.resize((size_t)n);
+    }
+};
+
 // Counterpart of SubPixelAdjusterImplementation (src/tracker/subpixel_adjuster.cpp:9-42): cornerSubPix and the revert of
 // points outside the image both run inside hv_corner_subpix, on level 0 of the frame's pyramid.
 class HipSubPixelAdjuster : public SubPixelAdjuster {
@@ -565,6 +586,11 @@ std::unique_ptr<FeatureDetector> FeatureDetector::buildHip(Session &s, const hv_
 std::unique_ptr<FeatureDetector> FeatureDetector::buildHipFast(Session &s, const hv_fast_params &p)
 {
     return std::unique_ptr<FeatureDetector>(new HipFastFeatureDetector(s, p));
+}
+
+std::unique_ptr<FeatureDetector> FeatureDetector::buildHipGftt(Session &s, const hv_gftt_legacy_params &p)
+{
+    return std::unique_ptr<FeatureDetector>(new HipGfttLegacyFeatureDetector(s, p));
 }
 
 std::unique_ptr<SubPixelAdjuster> SubPixelAdjuster::buildHip(Session &s, const hv_subpix_params &p)

@@ -185,6 +185,9 @@ public:
     // track mask, stable sort by response and applyMinDistance, all inside hv_fast_detect; supportsAsync() is false, as the legacy
     // detector's is
     static std::unique_ptr<FeatureDetector> buildHipFast(Session &session, const hv_fast_params &parameters);
+    // featureDetector "GFTT" (feature_detector.cpp:659-680, feature_detector_legacy.cpp:53-139): cv::goodFeaturesToTrack behind the
+    // track mask, all inside hv_gftt_legacy_detect; no applyMinDistance behind it; supportsAsync() is false
+    static std::unique_ptr<FeatureDetector> buildHipGftt(Session &session, const hv_gftt_legacy_params &parameters);
     virtual ~FeatureDetector();
     virtual void detect(
         ImagePyramid &imagePyramid,

@@ -527,6 +527,70 @@ int hv_fast_detect_batch_dev(hv_ctx *ctx, const hv_fast_params *p, int n_images,
 int hv_fast_detect(hv_ctx *ctx, const hv_fast_params *p, int slot, const float *prev_xy, int n_prev, int mask_radius,
                    float *corners_xy, int capacity, int *n_out);
 
+/* ---- legacy GFTT feature detector: cv::goodFeaturesToTrack behind the track mask (added within ABI 4) ---------------------
+ * Replaces tracker::FeatureDetector with featureDetector "GFTT" (src/tracker/feature_detector.cpp:659-680 FeatureDetector::build;
+ * src/tracker/feature_detector_legacy.cpp:53-139 GFTTFeatureDetector = cv::GFTTDetector, i.e. cv::goodFeaturesToTrack(gray,
+ * corners, maxTracks, gfttQualityLevel, minDistance, mask, gfttBlockSize, 3, false); :20-51 MaskedFeatureDetector::detect /
+ * setMask / drawMask; codegen/parameter_definitions.c:310-311) on the level-0 image of pyramid slots. The rules, restated in
+ * tests/gftt_legacy_restatement.py (written from the algorithm of OpenCV 4.x; not pinned against an OpenCV build):
+ *   mask        every live track (px, py) with 0 < px < w and 0 < py < h (binary32; NaN draws nothing) masks columns
+ *               [max(ix - r, 0), min(ix + r, w - 1)) and the like rows, ix = (int)px: the upper end is exclusive;
+ *   response    eig = cv::cornerMinEigenVal(gray, gfttBlockSize, 3), binary32, the operation order of oracle/gftt_oracle.c;
+ *   threshold   maxVal = the maximum of eig over the unmasked pixels of the whole image (0 when there is none),
+ *               t = (float)((double)maxVal * gfttQualityLevel), eig[p] = eig[p] > t ? eig[p] : 0 at every pixel, masked or not;
+ *   candidates  (x, y), 1 <= x <= w - 2, 1 <= y <= h - 2, unmasked, whose thresholded value v is not 0 and equals the maximum of
+ *               the thresholded values of its 3 x 3 neighbourhood (masked neighbours suppress; equal neighbours are both candidates);
+ *   order       descending v; among equal v the larger raster index y * w + x first (OpenCV 4.x's greaterThanPtr);
+ *   walk        minDistance = gfttMinDistance * (min(w, h) / 720.0) in binary64. minDistance >= 1: a candidate is accepted unless
+ *               an accepted corner lies at dx dx + dy dy < minDistance^2 (integer coordinates); minDistance < 1: every candidate is
+ *               accepted; either way the walk stops at maxTracks corners. The corners are (float)x, (float)y in acceptance order:
+ *               no applyMinDistance and no zero prefix behind it.
+ * Everything is asynchronous on the context stream with no allocation or synchronisation inside (capturable in a HIP graph): one
+ * memset and three launches per call, timed under HV_K_GFTT (mask, response, candidates) and HV_K_DETECT_TAIL (order and walk).
+ * The result is deterministic: the order in which candidates are appended to the work memory is not, and the select kernel sorts.
+ * Checks made before the context is looked at: HV_ERR_INVALID for NULL required pointers, negative sizes, maxTracks < 1,
+ * gfttQualityLevel <= 0, gfttMinDistance < 0 or max_corners < min(maxTracks, max_keypoints) (hv_gftt_legacy_detect also for
+ * mask_radius < 1); then HV_ERR_UNSUPPORTED for a gfttBlockSize other than 3, 5 and 7, n_images > 65535, max_prev >
+ * HV_DETECT_TAIL_MAX_PREV or maxTracks > HV_DETECT_TAIL_MAX_TRACKS. With the context: HV_ERR_UNSUPPORTED for an image edge below
+ * 8 (one reflection serves every halo) or above 32767 (the walk's squared distances are 32-bit integers). Counts read from device
+ * memory are clamped to their capacity. The radius is device data: a set with mask_radius_dev[s] < 1 (where the reference
+ * asserts), a set whose slot is no valid slot or holds no image, and a set with more candidates than max_keypoints write no row
+ * and report n_cand_dev[s] = n_out_dev[s] = -1: never truncated, because the order would then pick other corners.
+ * max_keypoints = hv_gftt_legacy_keypoint_bound() cannot overflow. The select kernel itself has no limit below that: it takes
+ * the keys from the top in groups of at most 4096, and a group of equal responses larger than that is split by raster index. */
+#define HV_GFTT_LEGACY_TILE_W 64   /* the tile of the response and candidate kernels (one workgroup); tests place their cases across its seams */
+#define HV_GFTT_LEGACY_TILE_H 16
+typedef struct hv_gftt_legacy_params {
+    int    gfttBlockSize;      /* 3: the box of cv::cornerMinEigenVal; 3, 5 and 7 are built (parameter_definitions.c)          */
+    double gfttQualityLevel;   /* 0.01: candidates lie above this share of the masked maximum                                   */
+    double gfttMinDistance;    /* 50: pixels at 720p, scaled by min(w, h) / 720 (feature_detector_legacy.cpp:53-68)             */
+    int    maxTracks;          /* 200: maxCorners of cv::goodFeaturesToTrack                                                    */
+} hv_gftt_legacy_params;
+void hv_gftt_legacy_default_params(hv_gftt_legacy_params *p);
+void hv_gftt_legacy_tile_size(int *tile_w, int *tile_h);   /* HV_GFTT_LEGACY_TILE_W, HV_GFTT_LEGACY_TILE_H as the library was built */
+double hv_gftt_legacy_min_distance(hv_ctx *ctx, const hv_gftt_legacy_params *p);   /* the scaled binary64 distance (-1: NULL argument) */
+int hv_gftt_legacy_keypoint_bound(hv_ctx *ctx);             /* (w - 2)(h - 2): candidates lie inside the 1-pixel border */
+/* header, max_keypoints 64-bit keys, the response map (4 bytes per pixel) and the mask (1 byte per pixel) per image */
+size_t hv_gftt_legacy_work_bytes(hv_ctx *ctx, int n_images, int max_keypoints);
+/* MaskedFeatureDetector::detect of the GFTT detector (feature_detector_legacy.cpp:20-51, :53-139), no host step. work_dev:
+ * hv_gftt_legacy_work_bytes(ctx, n_images, max_keypoints) bytes, 16-byte aligned. prev_dev [n_images][max_prev][2] with
+ * n_prev_dev [n_images] (both NULL allowed when max_prev == 0), mask_radius_dev [n_images], corners_dev
+ * [n_images][max_corners][2], resp_dev [n_images][max_corners] or NULL (the responses of the accepted corners, OpenCV's
+ * cornersQuality), n_cand_dev [n_images] (the candidate count before the walk), n_out_dev [n_images]. */
+int hv_gftt_legacy_detect_batch_dev(hv_ctx *ctx, const hv_gftt_legacy_params *p, int n_images, const int *slots_dev, void *work_dev,
+                                    int max_keypoints, int *n_cand_dev, int max_prev, const int *n_prev_dev, const float *prev_dev,
+                                    const int *mask_radius_dev, int max_corners, float *corners_dev, float *resp_dev,
+                                    int *n_out_dev);
+/* The same without live tracks: cv::goodFeaturesToTrack with no mask (feature_detector_legacy.cpp:53-139). */
+int hv_gftt_legacy_keypoints_batch_dev(hv_ctx *ctx, const hv_gftt_legacy_params *p, int n_images, const int *slots_dev,
+                                       void *work_dev, int max_keypoints, int *n_cand_dev, int max_corners, float *corners_dev,
+                                       float *resp_dev, int *n_out_dev);
+/* One image, host pointers, synchronous (staged through the context's arena, hv_stage.hpp; feature_detector_legacy.cpp:20-51,
+ * :53-139): capacity >= min(maxTracks, hv_gftt_legacy_keypoint_bound()) corners (HV_ERR_INVALID below it); HV_ERR_POOL for a
+ * slot that is not in use or holds no image. */
+int hv_gftt_legacy_detect(hv_ctx *ctx, const hv_gftt_legacy_params *p, int slot, const float *prev_xy, int n_prev, int mask_radius,
+                          float *corners_xy, int capacity, int *n_out);
+
 /* ---- sub-pixel corner refinement (added within ABI 4) ----------------------------------------
  * Replaces tracker::SubPixelAdjuster::adjust (src/tracker/subpixel_adjuster.cpp:18-42): cv::cornerSubPix(image, corners,
  * Size(win, win), Size(-1, -1), TermCriteria(COUNT | EPS, maxIter, epsilon)) on the level-0 image of a pyramid slot, then
