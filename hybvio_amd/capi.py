@@ -1780,3 +1780,168 @@ class EkfBatch:
         self._chk(lib().hv_ekf_transform(self._h, b, _p(_f(pC), f64p), _p(_f(qC), f64p), _p(_f(tr), f64p)),
                   "hv_ekf_transform")
         self.ctx.synchronize()
+
+
+# ---- resident VIO engine (hv_vio_*): one object, one call per frame -------------------------------------------------------
+DETECTOR_GPU_GFTT, DETECTOR_FAST, DETECTOR_GFTT = 0, 1, 2
+TRACKING_INIT, TRACKING_TRACKING, TRACKING_LOST = 0, 1, 2
+
+
+class VioParams(C.Structure):
+    """hv_vio_params: one member per owned entry, the two cameras and the session's scalars."""
+    _fields_ = [("ekf", EkfParams), ("gftt", GfttParams), ("subpix", SubpixParams), ("gate", StereoGateParams), ("ransac3", Ransac3Params),
+                ("tracks", TrackTableParams), ("trail", TrailIndexParams), ("flow", FlowPredictParams), ("vu", VuParams),
+                ("control", EkfControlParams), ("session", SessionParams), ("output", OutputParams), ("camera0", CameraModel),
+                ("camera1", CameraModel), ("ransac2Threshold", C.c_double), ("trackChiTestOutlierR", C.c_double), ("visualR", C.c_double),
+                ("ransacRngSeed", C.c_int), ("odometryRngSeed", C.c_int), ("imu_samples_max", C.c_int), ("featureDetector", C.c_int),
+                ("useRansac3", C.c_int), ("predictOpticalFlow", C.c_int), ("batchVisualUpdate", C.c_int)]
+
+
+class VioView(C.Structure):
+    """hv_vio_view: the owned objects and the device pointers of the frame's stage outputs."""
+    _fields_ = [("ekf", C.c_void_p), ("table", TrackTable), ("trail", TrailIndexTable), ("session", SessionState), ("control", EkfControlTable),
+                ("rng_pipeline", RngState), ("rng_ransac3", RngState), ("rng_odometry", RngState), ("record", OutputTable)] + [
+        (k, C.c_void_p) for k in ("frame_num", "has_previous", "full_update", "keyframe", "keyframe_out", "good_frame", "reset_kind",
+                                  "tracking_status", "n_candidates", "cand_id", "status", "gate_status", "slot_prev_left", "slot_cur_left",
+                                  "slot_right")]
+
+
+PROTOTYPES.update({
+    "hv_vio_default_params": (None, [C.POINTER(VioParams)]),
+    "hv_vio_create": (C.c_int, [C.c_void_p, C.POINTER(VioParams), C.c_int, C.POINTER(C.c_void_p)]),
+    "hv_vio_destroy": (None, [C.c_void_p]),
+    "hv_vio_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hv_vio_view_get": (C.c_int, [C.c_void_p, C.POINTER(VioView)]),
+    "hv_vio_replay_period": (C.c_int, [C.c_void_p]),
+    "hv_vio_sets": (C.c_int, [C.c_void_p]),
+})
+
+
+def vio_default_params(**over) -> VioParams:
+    """hv_vio_default_params; an override names a member (ransac2Threshold=3.0) or, with a double underscore, a member of a member
+    (tracks__maxTracks=120); matrices take 16 values."""
+    p = VioParams()
+    lib().hv_vio_default_params(C.byref(p))
+    for k, v in over.items():
+        obj, names = p, k.split("__")
+        for name in names[:-1]:
+            obj = getattr(obj, name)
+        if isinstance(getattr(obj, names[-1]), C.Array):
+            getattr(obj, names[-1])[:] = list(np.asarray(v, np.float64).reshape(-1))
+        else:
+            setattr(obj, names[-1], v)
+    return p
+
+
+class _Wrapped:
+    """A device array the engine owns, as the interface torch.as_tensor reads (no copy)."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2)
+
+
+def _wrap(ptr, shape, typestr):
+    return torch.as_tensor(_Wrapped(ptr, shape, typestr), device="cuda")
+
+
+class VioEngine:
+    """hv_vio: the default stereo session of n_sets resident sequences on one Context; frame() is one frame of every set."""
+
+    def __init__(self, ctx: Context, params: VioParams | None = None, n_sets: int = 1):
+        self.ctx, self.n_sets = ctx, n_sets
+        self.params = params if params is not None else vio_default_params()
+        self._h = C.c_void_p()
+        rc = lib().hv_vio_create(ctx._h, C.byref(self.params), n_sets, C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            ctx._chk(rc, "hv_vio_create")
+        if not hasattr(ctx, "_children"):
+            ctx._children = []
+        ctx._children.append(self)
+
+    @classmethod
+    def create(cls, ctx: Context, params: VioParams | None = None, n_sets: int = 1) -> "VioEngine":
+        return cls(ctx, params, n_sets)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().hv_vio_destroy(self._h)
+            self._h = None
+            if self in getattr(self.ctx, "_children", []):
+                self.ctx._children.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                             # interpreter shutdown: module globals may be gone already
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def frame(self, left_dev, right_dev, image_stride, row_stride, n_samples, t_dev, gyro_dev, acc_dev):
+        p = lambda x: C.c_void_p(x) if x else None
+        self.ctx._chk(lib().hv_vio_frame(self._h, p(left_dev), p(right_dev), image_stride, row_stride, n_samples, p(t_dev), p(gyro_dev),
+                                         p(acc_dev)), "hv_vio_frame")
+
+    def replay_period(self) -> int:
+        return lib().hv_vio_replay_period(self._h)
+
+    def raw_view(self) -> VioView:
+        v = VioView()
+        self.ctx._chk(lib().hv_vio_view_get(self._h, C.byref(v)), "hv_vio_view_get")
+        return v
+
+    def view(self) -> dict:
+        """The engine's arrays as torch tensors over its own device memory (nothing is copied): 'table', 'trail', 'session',
+        'control', 'record' and the three 'rng_*' are dicts by member name, the stage outputs are tensors, 'ekf_handle' is the
+        engine's hv_ekf (not owned; state() reads its mean and covariance back)."""
+        raw, p, S = self.raw_view(), self.params, self.n_sets
+        M, K, V, T = p.tracks.maxTracks, p.trail.cameraTrailLength + 1, p.trail.maxVisualUpdates, p.output.cameraTrailLength
+        W = session_window(p.session)
+        i4, f4, f8, u1 = "<i4", "<f4", "<f8", "|u1"
+        spec = dict(
+            table=dict(n_tracks=((S,), i4), ids=((S, M), i4), xy=((S, M, 2), f4), second_xy=((S, M, 2), f4), status=((S, M), i4),
+                       blacklist=((S, M), u1), kf_xy=((S, M, 2), f4), kf_valid=((S, M), u1), frame_num=((S,), i4), mask_steps=((S,), i4),
+                       mask_radius=((S,), i4), frame_flags=((S,), u1)),
+            trail=dict(n_keyframes=((S,), i4), frame_counter=((S,), i4), kf_row=((S, K), i4), frame_number=((S, K), i4),
+                       timestamp=((S, K), f8), col_id=((S, M), i4), col_len=((S, M), i4), image_point=((S, K, M, 2, 2), f4),
+                       norm_point=((S, K, M, 2, 2), f8), norm_velocity=((S, K, M, 2, 2), f8), used=((S, K, M), u1), n_blacklist=((S,), i4),
+                       blacklist_ids=((S, M), i4), n_order=((S,), i4), n_skipped=((S,), i4), skipped_pos=((S, M), i4),
+                       skipped_id=((S, M), i4), cand_pos=((S, V), i4), cand_col=((S, V), i4)),
+            session=dict(good_ring=((S, W), f4), ring_head=((S,), i4), ring_entries=((S,), i4), tracking_status=((S,), i4),
+                         control_status=((S,), i4), last_reset_time=((S,), f8), first_sample=((S,), u1), first_sample_t=((S,), f8),
+                         prev_sample_t=((S,), f8), time=((S,), f8), initialized_orientation=((S,), u1)),
+            control=dict(zupt_time=((S,), f8), init_zupt_time=((S,), f8), was_stationary=((S,), i4), frames_since_keyframe=((S,), i4)),
+            record=dict(t=((S,), f8), tracking_status=((S,), i4), stationary_visual=((S,), u1), inertial_mean=((S, 20), f8),
+                        inertial_cov_diag=((S, 20), f8), position_cov=((S, 3, 3), f8), velocity_cov=((S, 3, 3), f8), n_trail=((S,), i4),
+                        trail_time=((S, T), f8), trail_pose=((S, T, 7), f8), api_pose=((S, 7), f8), api_trail_pose=((S, T, 7), f8),
+                        n_points=((S,), i4), point_id=((S, V), i4), point_status=((S, V), i4), point_first_pixel=((S, V, 2), f4),
+                        point_xyz=((S, V, 3), f8)))
+        rng = dict(mt=((S, RNG_STATE_WORDS), i4), pos=((S,), i4))
+        out = {}
+        for name, members in list(spec.items()) + [(k, rng) for k in ("rng_pipeline", "rng_ransac3", "rng_odometry")]:
+            struct = getattr(raw, name)
+            out[name] = {k: _wrap(getattr(struct, k), shape, ts) for k, (shape, ts) in members.items()}
+        stage = dict(frame_num=((S,), i4), has_previous=((S,), u1), full_update=((S,), u1), keyframe=((S,), i4), keyframe_out=((S,), i4),
+                     good_frame=((S,), u1), reset_kind=((S,), i4), tracking_status=((S,), i4), n_candidates=((S,), i4), cand_id=((V, S), i4),
+                     status=((V, S, 2), i4), gate_status=((V, S), i4), slot_prev_left=((S,), i4), slot_cur_left=((S,), i4),
+                     slot_right=((S,), i4))
+        for k, (shape, ts) in stage.items():
+            out[k] = _wrap(getattr(raw, k), shape, ts)
+        out["ekf_handle"] = C.c_void_p(raw.ekf)
+        out["state_dim"] = lib().hv_ekf_state_dim(out["ekf_handle"])
+        return out
+
+    def state(self):
+        """Means [n_sets][n] and covariances [n_sets][n][n] (column-major per filter) read back from the engine's filter."""
+        raw = self.raw_view()
+        h = C.c_void_p(raw.ekf)
+        n = lib().hv_ekf_state_dim(h)
+        ms, Ps = np.zeros((self.n_sets, n)), np.zeros((self.n_sets, n, n))
+        for b in range(self.n_sets):
+            self.ctx._chk(lib().hv_ekf_get_state(h, b, _p(ms[b], f64p), _p(Ps[b], f64p)), "hv_ekf_get_state")
+        return ms, Ps

@@ -1616,6 +1616,109 @@ int hv_match_intensities_batch_dev(hv_ctx *ctx, const hv_intensity_params *param
 int hv_match_intensities(hv_ctx *ctx, int width, int height, const uint8_t *l_host, int l_stride_bytes, uint8_t *r_host,
                          int r_stride_bytes, double weight);
 
+/* ---- resident VIO engine: one object, one call per frame (added within ABI 4) ------------------------------------------
+ * The default stereo session of n_sets resident sequences as ONE owned object: Session::process (src/odometry/backend.cpp:716-860)
+ * with Tracker::add in front of it, assembled from the _dev entries above in the order INTEGRATION.md states ("The whole frame on
+ * the device", "Between the table and the filter", "Around the frame"; "One call per frame" lists the calls of hv_vio_frame). The
+ * engine adds no arithmetic of its own: every stage is the entry documented above, with the engine's buffers as its arguments.
+ * What it adds is the ownership of those buffers and the per-frame state a caller of the long chains keeps on the host, here in
+ * device memory (csrc/vio_engine.hip): the frame number of every set (frame->num = ++frameCount, src/odometry/sample_sync.cpp:138: the
+ * first frame is 1, and a reset does not restart it), the rule fullVisualUpdate = frame->num %
+ * visualUpdateForEveryNFrame == 0 || !canPopKeyframe() (backend.cpp:765, ekf_state_index.hpp:109), the zeroing of the per-frame
+ * counters, the "has a previous frame" flag, and the roles of the three pyramid slots of a set.
+ * hv_vio_params: one member per owned entry, each with that entry's own defaults (hv_vio_default_params calls their default
+ * functions), the two cameras, and the scalars the reference derives per session:
+ *   ransac2Threshold (4.0)        threshold_pow2 = (float)pow(ransac2Threshold * (min(w, h) / 720.0), 2), ransac_pipeline.cpp:87-88;
+ *   trackChiTestOutlierR (1.5), visualR (0.05)   both divided by the focal length (fx + fy) / 2 of camera0, backend.cpp:996-997
+ *                                 (a vu.trackRmseThreshold >= 0 likewise, :995);
+ *   ransacRngSeed (4649), odometryRngSeed (0)    the seeds of the two tracker generators and of the odometry generator;
+ *   imu_samples_max               the most IMU samples a frame may bring, 1 .. HV_EKF_MAX_PREDICT_SAMPLES (default: that limit);
+ *   featureDetector, useRansac3, predictOpticalFlow, batchVisualUpdate   the reference's switches whose other settings the engine
+ *                                 refuses (defaults HV_DETECTOR_GPU_GFTT, 1, 1, 0).
+ * second_to_first of RANSAC3 is flow.imuToCamera * flow.secondCameraToImu; gate.cam0ToCam1 and the four matrices of `flow` are
+ * the caller's, as for the entries themselves.
+ * hv_vio_create decides, before the device is touched and in this order: HV_ERR_INVALID for a NULL params or out, n_sets < 1,
+ * imu_samples_max outside 1 .. HV_EKF_MAX_PREDICT_SAMPLES, tracks.maxTracks != trail.maxTracks (or != gftt.maxTracks /
+ * output.maxTracks), a cameraTrailLength, maxVisualUpdates or maxSuccessfulVisualUpdates that differs between ekf, trail and
+ * output, trail.useStereo and output.useStereo disagreeing (vu.useStereo is not read: the engine's copy of vu takes
+ * trail.useStereo, because hv_vu_default_params leaves it 0); then HV_ERR_UNSUPPORTED for everything outside the default
+ * stereo session: mono (useStereo 0), featureDetector != HV_DETECTOR_GPU_GFTT, useRansac3 0 (hybrid RANSAC5, upright 2-point),
+ * gate.independentStereoOpticalFlow, predictOpticalFlow 0, batchVisualUpdate, trail.fullPointCloud, ekf.hybridMapSize > 0, n_sets >
+ * 65535, 3 * ransac3.ransac3MaxIterations > HV_RNG_MAX_DRAWS; then HV_ERR_INVALID for a NULL context, a context whose max_tracks is below
+ * maxTracks or whose pool has fewer than 3 * n_sets free slots (the pool is never grown here: the caller sizes it). Whatever the
+ * owned entries themselves refuse comes back from hv_vio_create (the init entries and the filter) or from the first hv_vio_frame.
+ * hv_vio_create allocates everything the frame needs through the library's owning buffer type (one block for the engine's
+ * arrays; the filter's lazily grown visit buffers are grown here by one visit loop over empty candidate lists), runs every *_init*
+ * entry and the three seeds, and synchronises once. An hv_vio must be destroyed before its context.
+ * hv_vio_frame is one frame of every set: left_dev / right_dev are 8-bit gray images, set s at s * image_stride_bytes, rows
+ * row_stride_bytes apart (base and strides multiples of 4 bytes: the images are copied into the engine's pyramid slots by
+ * hv_ingest_build_batch_dev and may be overwritten as soon as the call has run on the stream); t_dev [n_samples][n_sets], gyro_dev /
+ * acc_dev [n_samples][n_sets][3] as hv_session_imu_dev and hv_ekf_predict_n_dev take them, 1 <= n_samples <= imu_samples_max. A
+ * set with fewer samples repeats its last time stamp: dt = 0 is skipped (ekf.cpp:367). Intensity matching and a rectifying ingest
+ * work on the caller's buffers in front of the call. The call allocates nothing, copies nothing to the host and synchronises
+ * nothing; no per-frame state is kept on the host, so it can be captured (hipStreamBeginCapture, torch.cuda.graph) and replayed.
+ * The first frame of a set after create or after a reset has no previous image: its table is empty and "has a previous frame" is
+ * 0 in device memory, so the temporal and stereo LK, the gate and the RANSAC filters see zero points and the frame is the
+ * detection-only frame of a fresh tracker.
+ * hv_vio_replay_period: the number of consecutive frames that form the unit a graph may hold. It is 1: a frame issues
+ * hv_ekf_undo_augment_dev and hv_ekf_symmetrize_augment_dev exactly once each, unconditionally (their masks are device data),
+ * and each swaps the two covariance buffers (hv_ekf_device_pointers above), so every frame starts on the buffer it found; the slot
+ * roles and the frame number are device arrays that vio_frame_end_kernel rotates and advances.
+ * hv_vio_view hands out the owned objects and the device pointers of the frame's stage outputs; nothing is copied, the pointers
+ * stay valid until hv_vio_destroy. */
+enum { HV_DETECTOR_GPU_GFTT = 0, HV_DETECTOR_FAST = 1, HV_DETECTOR_GFTT = 2 };   /* tracker.featureDetector */
+typedef struct hv_vio_params {
+    hv_ekf_params ekf;                   /* (the LK parameters are hv_params of the context the engine is built on) */
+    hv_gftt_params gftt;
+    hv_subpix_params subpix;
+    hv_stereo_gate_params gate;
+    hv_ransac3_params ransac3;
+    hv_track_table_params tracks;
+    hv_trail_index_params trail;
+    hv_flow_predict_params flow;
+    hv_vu_params vu;
+    hv_ekf_control_params control;
+    hv_session_params session;
+    hv_output_params output;
+    hv_camera_model camera0, camera1;
+    double ransac2Threshold;
+    double trackChiTestOutlierR, visualR;
+    int ransacRngSeed, odometryRngSeed;
+    int imu_samples_max;
+    int featureDetector, useRansac3, predictOpticalFlow, batchVisualUpdate;
+} hv_vio_params;
+void hv_vio_default_params(hv_vio_params *p);
+typedef struct hv_vio hv_vio;
+typedef struct hv_vio_view {              /* device memory unless noted; V = trail.maxVisualUpdates */
+    hv_ekf *ekf;                          /* host handle of the filter batch (batch = n_sets) */
+    hv_track_table table;
+    hv_trail_index trail;
+    hv_session session;
+    hv_ekf_control control;
+    hv_rng rng_pipeline, rng_ransac3, rng_odometry;
+    hv_output record;
+    const int32_t *frame_num;             /* [n_sets] the number of the NEXT frame of every set */
+    const uint8_t *has_previous;          /* [n_sets] as the last frame's begin kernel read it */
+    const uint8_t *full_update;           /* [n_sets] */
+    const int32_t *keyframe;              /* [n_sets] keyframe_dev of hv_tracks_update_batch_dev */
+    const int32_t *keyframe_out;          /* [n_sets] keyframe_out_dev of hv_ekf_frame_control_dev */
+    const uint8_t *good_frame;            /* [n_sets] hv_trail_finish_batch_dev */
+    const int32_t *reset_kind;            /* [n_sets] hv_session_status_dev */
+    const int32_t *tracking_status;       /* [n_sets] status_dev of hv_session_status_dev */
+    const int32_t *n_candidates;          /* [n_sets] hv_trail_select_batch_dev */
+    const int32_t *cand_id;               /* [V][n_sets] */
+    const int32_t *status;                /* [V][n_sets][2] hv_ekf_visual_frame_ragged_dev */
+    const int32_t *gate_status;           /* [V][n_sets] */
+    const int32_t *slot_prev_left, *slot_cur_left, *slot_right;   /* [n_sets] the slot roles of the NEXT frame */
+} hv_vio_view;
+int hv_vio_create(hv_ctx *ctx, const hv_vio_params *p, int n_sets, hv_vio **out);
+void hv_vio_destroy(hv_vio *vio);
+int hv_vio_frame(hv_vio *vio, const uint8_t *left_dev, const uint8_t *right_dev, long long image_stride_bytes,
+                 int row_stride_bytes, int n_samples, const double *t_dev, const double *gyro_dev, const double *acc_dev);
+int hv_vio_view_get(hv_vio *vio, hv_vio_view *out);
+int hv_vio_replay_period(const hv_vio *vio);
+int hv_vio_sets(const hv_vio *vio);
+
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
        HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
@@ -1626,7 +1729,7 @@ enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_
        HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3*, hv_upright2p* */,
-       HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev, hv_session_*_dev, hv_output_dev */,
+       HV_K_EKF_CONTROL = 18 /* added within ABI 4: hv_ekf_block_update_dev, hv_ekf_pseudo_velocity_dev, hv_ekf_imu_control_dev, hv_ekf_frame_control_dev, hv_session_*_dev, hv_output_dev, the two kernels of hv_vio_frame */,
        HV_K_TRAIL_INDEX = 19 /* added within ABI 4: hv_trail_*_batch_dev, hv_flow_predict_batch_dev, the index kernel of hv_full_point_cloud_dev, hv_rng_*_batch_dev */,
        HV_K_COUNT = 20 };
 int hv_profile_enable(hv_ctx *ctx, int on);
