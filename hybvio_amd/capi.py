@@ -82,6 +82,11 @@ class GfttLegacyParams(C.Structure):
     _fields_ = [("gfttBlockSize", C.c_int), ("gfttQualityLevel", C.c_double), ("gfttMinDistance", C.c_double), ("maxTracks", C.c_int)]
 
 
+class StereoBmParams(C.Structure):
+    _fields_ = [("numDisparities", C.c_int), ("blockSize", C.c_int), ("preFilterCap", C.c_int), ("textureThreshold", C.c_int),
+                ("uniquenessRatio", C.c_int), ("speckleWindowSize", C.c_int), ("speckleRange", C.c_int)]
+
+
 class SubpixParams(C.Structure):
     _fields_ = [("subPixWindowSize", C.c_int), ("subPixMaxIter", C.c_int), ("subPixEpsilon", C.c_double)]
 
@@ -341,6 +346,23 @@ PROTOTYPES = {
                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]),
     "hv_gftt_legacy_detect": (C.c_int, [C.c_void_p, C.POINTER(GfttLegacyParams), C.c_int, f32p, C.c_int, C.c_int, f32p, C.c_int,
+                                        C.POINTER(C.c_int)]),
+    "hv_stereo_num_disparities": (C.c_int, [C.c_int]),
+    "hv_stereo_bm_default_params": (None, [C.POINTER(StereoBmParams), C.c_int]),
+    "hv_stereo_work_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(StereoBmParams), C.c_int]),
+    "hv_filter_speckles_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "hv_stereo_cloud_bound": (C.c_int, [C.c_void_p, C.c_int]),
+    "hv_stereo_disparity_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(StereoBmParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_longlong, C.c_void_p]),
+    "hv_filter_speckles_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
+                                               C.c_int, C.c_void_p]),
+    "hv_stereo_track_depth_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                                  C.POINTER(C.c_double), C.c_void_p]),
+    "hv_stereo_point_cloud_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_double), C.c_int,
+                                                  C.c_int, C.c_void_p, C.c_void_p]),
+    "hv_stereo_disparity": (C.c_int, [C.c_void_p, C.POINTER(StereoBmParams), C.c_int, C.c_int, C.c_void_p, C.c_longlong]),
+    "hv_stereo_track_depth": (C.c_int, [C.c_void_p, C.c_int, f32p, C.c_void_p, C.c_longlong, C.POINTER(C.c_double), f32p]),
+    "hv_stereo_point_cloud": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_double), C.c_int, f32p, C.c_int,
                                         C.POINTER(C.c_int)]),
     "hv_subpix_default_params": (None, [C.POINTER(SubpixParams)]),
     "hv_corner_subpix": (C.c_int, [C.c_void_p, C.POINTER(SubpixParams), C.c_int, C.c_int, f32p, i32p]),
@@ -1024,6 +1046,77 @@ class Context:
                                                         max_corners, p(corners_dev), p(resp_dev), p(n_out_dev)),
                   "hv_gftt_legacy_detect_batch_dev")
 
+    # -- dense stereo depth --
+    def stereo_work_bytes(self, n_sets: int, params: "StereoBmParams" = None) -> int:
+        sp = params if params is not None else stereo_bm_default_params(self.params.width)
+        return int(lib().hv_stereo_work_bytes(self._h, C.byref(sp), int(n_sets)))
+
+    def stereo_cloud_bound(self, cloud_stride: int = 5) -> int:
+        """hv_stereo_cloud_bound: a max_points no cloud of this context can exceed."""
+        return self._chk_count(lib().hv_stereo_cloud_bound(self._h, int(cloud_stride)), "hv_stereo_cloud_bound")
+
+    def _chk_count(self, rc, what):
+        if rc < 0:
+            self._chk(rc, what)
+        return int(rc)
+
+    def stereo_disparity(self, left_slot: int, right_slot: int, params: "StereoBmParams" = None):
+        """OpenCvStereoDisparity::computeDisparity on the level-0 images of two built slots -> int16 [h, w] (disparity x 16)."""
+        sp = params if params is not None else stereo_bm_default_params(self.params.width)
+        out = np.zeros((self.params.height, self.params.width), np.int16)
+        self._chk(lib().hv_stereo_disparity(self._h, C.byref(sp), int(left_slot), int(right_slot), out.ctypes.data_as(C.c_void_p),
+                                            self.params.width), "hv_stereo_disparity")
+        return out
+
+    def stereo_track_depth(self, disp, xy, q):
+        """getDepth of every point on a host disparity image [h, w] int16 -> float32 [n]."""
+        disp = np.ascontiguousarray(disp, np.int16)
+        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.zeros(max(len(pts), 1), np.float32)
+        qa = (C.c_double * 16)(*np.asarray(q, np.float64).reshape(16))
+        self._chk(lib().hv_stereo_track_depth(self._h, len(pts), _p(pts, f32p) if len(pts) else None, disp.ctypes.data_as(C.c_void_p),
+                                              disp.shape[1], qa, _p(out, f32p)), "hv_stereo_track_depth")
+        return out[:len(pts)].copy()
+
+    def stereo_point_cloud(self, disp, q, cloud_stride: int = 5):
+        """computePointCloud on a host disparity image -> float32 [n, 3] in row-major visiting order."""
+        disp = np.ascontiguousarray(disp, np.int16)
+        cap = self.stereo_cloud_bound(cloud_stride)
+        out = np.zeros((max(cap, 1), 3), np.float32)
+        n = C.c_int(0)
+        qa = (C.c_double * 16)(*np.asarray(q, np.float64).reshape(16))
+        self._chk(lib().hv_stereo_point_cloud(self._h, disp.ctypes.data_as(C.c_void_p), disp.shape[1], qa, int(cloud_stride),
+                                              _p(out, f32p), cap, C.byref(n)), "hv_stereo_point_cloud")
+        return out[:n.value].copy()
+
+    def stereo_disparity_batch_dev(self, n_sets, left_slots_dev, right_slots_dev, work_dev, disp_dev, disp_set_stride, n_valid_dev=0,
+                                   params: "StereoBmParams" = None):
+        """hv_stereo_disparity_batch_dev: prefilter, block matching and the speckle filter on the context stream."""
+        sp = params if params is not None else stereo_bm_default_params(self.params.width)
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_stereo_disparity_batch_dev(self._h, C.byref(sp), n_sets, p(left_slots_dev), p(right_slots_dev), p(work_dev),
+                                                      p(disp_dev), int(disp_set_stride), p(n_valid_dev)), "hv_stereo_disparity_batch_dev")
+
+    def filter_speckles_batch_dev(self, n_sets, width, height, disp_dev, set_stride, new_val, max_size, max_diff, work_dev):
+        """hv_filter_speckles_batch_dev: cv::filterSpeckles in place on int16 maps of any size."""
+        p = lambda x: C.c_void_p(x or None)
+        self._chk(lib().hv_filter_speckles_batch_dev(self._h, n_sets, width, height, p(disp_dev), int(set_stride), int(new_val),
+                                                     int(max_size), int(max_diff), p(work_dev)), "hv_filter_speckles_batch_dev")
+
+    def stereo_track_depth_batch_dev(self, n_sets, max_points, n_points_dev, xy_dev, disp_dev, stride, q, depth_dev):
+        """hv_stereo_track_depth_batch_dev: getDepth of every track; q: disparityToDepthQ, 16 row-major doubles."""
+        p = lambda x: C.c_void_p(x or None)
+        qa = (C.c_double * 16)(*np.asarray(q, np.float64).reshape(16))
+        self._chk(lib().hv_stereo_track_depth_batch_dev(self._h, n_sets, max_points, p(n_points_dev), p(xy_dev), p(disp_dev), int(stride),
+                                                        qa, p(depth_dev)), "hv_stereo_track_depth_batch_dev")
+
+    def stereo_point_cloud_batch_dev(self, n_sets, disp_dev, stride, q, cloud_stride, max_points, xyz_dev, n_points_dev):
+        """hv_stereo_point_cloud_batch_dev: computePointCloud in row-major order; -1 for a set that does not fit."""
+        p = lambda x: C.c_void_p(x or None)
+        qa = (C.c_double * 16)(*np.asarray(q, np.float64).reshape(16))
+        self._chk(lib().hv_stereo_point_cloud_batch_dev(self._h, n_sets, p(disp_dev), int(stride), qa, int(cloud_stride), max_points,
+                                                        p(xyz_dev), p(n_points_dev)), "hv_stereo_point_cloud_batch_dev")
+
     # -- sub-pixel corner refinement --
     def corner_subpix(self, slot: int, xy, params: "SubpixParams" = None):
         """SubPixelAdjuster::adjust on the level-0 image of a built pyramid slot -> (refined xy [n, 2], position updates [n])."""
@@ -1235,6 +1328,25 @@ def gftt_legacy_tile_size() -> tuple:
     w, h = C.c_int(), C.c_int()
     lib().hv_gftt_legacy_tile_size(C.byref(w), C.byref(h))
     return w.value, h.value
+
+
+def stereo_num_disparities(width: int) -> int:
+    return int(lib().hv_stereo_num_disparities(int(width)))
+
+
+def stereo_bm_default_params(width: int, **over) -> StereoBmParams:
+    p = StereoBmParams()
+    lib().hv_stereo_bm_default_params(C.byref(p), int(width))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def filter_speckles_work_bytes(width: int, height: int, n_sets: int) -> int:
+    return int(lib().hv_filter_speckles_work_bytes(int(width), int(height), int(n_sets)))
+
+
+STEREO_FILTERED = -16
 
 
 def subpix_default_params(**over) -> SubpixParams:

@@ -328,6 +328,7 @@ static int init_ctx(Ctx *c, int high_priority)
     if (rc == HV_OK) rc = hv::upright2p_init(c);
     if (rc == HV_OK) rc = hv::detect_tail_init(c);
     if (rc == HV_OK) rc = hv::fast_init(c);
+    if (rc == HV_OK) rc = hv::stereo_bm_init(c);
     if (rc == HV_OK) rc = hv::gftt_legacy_init(c);
     if (rc == HV_OK) rc = hv::ekf_kernels_init(c);
     if (rc == HV_OK) rc = hv::vu_prepare_init(c);

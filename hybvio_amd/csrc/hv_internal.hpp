@@ -231,6 +231,7 @@ int upright2p_init(Ctx *c);            // upright2p.hip: likewise
 int detect_tail_init(Ctx *c);         // detect_tail.hip: likewise
 int fast_init(Ctx *c) __attribute__((visibility("hidden")));   // fast.hip: likewise
 int gftt_legacy_init(Ctx *c) __attribute__((visibility("hidden")));   // gftt_legacy.hip: likewise
+int stereo_bm_init(Ctx *c) __attribute__((visibility("hidden")));     // stereo_bm.hip: likewise
 int pyramid_init(Ctx *c);             // pyramid.hip: likewise
 int ekf_kernels_init(Ctx *c);         // ekf.hip: likewise, every EKF kernel that carves dynamic LDS (lds_layout.hpp), through ...
 int ekf_update_init(Ctx *c) __attribute__((visibility("hidden")));    // ... ekf_update.hip,

@@ -51,6 +51,7 @@ Undistorter::~Undistorter() = default;
 rot_ransac::RotRansac::~RotRansac() = default;
 RansacPipeline::~RansacPipeline() = default;
 StereoGate::~StereoGate() = default;
+StereoDisparity::~StereoDisparity() = default;
 
 void FeatureDetector::applyMinDistance(std::vector<Feature::Point> &corners, const std::vector<Feature::Point> &prevCorners,
                                        int minDistance) const
@@ -570,6 +571,55 @@ std::unique_ptr<StereoGate> StereoGate::buildHip(Session &s, int width, int heig
     if (width != s.params().width || height != s.params().height)
         throw std::invalid_argument("StereoGate::buildHip: width / height differ from the session's image size");
     return std::unique_ptr<StereoGate>(new HipStereoGate(s, p, cam0ToCam1));
+}
+
+// Counterpart of OpenCvStereoDisparity (src/tracker/stereo_disparity.cpp:21-138): every method is one synchronous C-ABI call.
+class HipStereoDisparity : public StereoDisparity {
+    Session &session;
+    const int width, height, cloudStride;
+    const hv_stereo_bm_params params;
+public:
+    HipStereoDisparity(Session &s, int w, int h, const hv_stereo_bm_params &p, int stride)
+        : session(s), width(w), height(h), cloudStride(stride), params(p) {}
+    DisparityImage buildDisparityImage() const final { return DisparityImage((size_t)width * height, (std::int16_t)HV_STEREO_FILTERED); }
+    void computeDisparity(ImagePyramid &first, ImagePyramid &second, DisparityImage &out) final {
+        out.resize((size_t)width * height);
+        session.check(hv_stereo_disparity(session.ctx(), &params, first.deviceSlot(), second.deviceSlot(), out.data(), width),
+                      "hv_stereo_disparity");
+    }
+    float getDepth(const std::array<double, 16> &Q, const DisparityImage &disparity, const Feature::Point &pixCoords) const final {
+        assert(disparity.size() == (size_t)width * height);
+        float depth = -1;
+        session.check(hv_stereo_track_depth(session.ctx(), 1, &pixCoords.x, disparity.data(), width, Q.data(), &depth),
+                      "hv_stereo_track_depth");
+        return depth;
+    }
+    void getDepths(const std::array<double, 16> &Q, const DisparityImage &disparity, const std::vector<Feature::Point> &pixCoords,
+                   std::vector<float> &depths) const final {
+        assert(disparity.size() == (size_t)width * height);
+        depths.assign(pixCoords.size(), -1.f);
+        session.check(hv_stereo_track_depth(session.ctx(), (int)pixCoords.size(), reinterpret_cast<const float *>(pixCoords.data()),
+                                            disparity.data(), width, Q.data(), depths.data()), "hv_stereo_track_depth");
+    }
+    void computePointCloud(const std::array<double, 16> &Q, const DisparityImage &disparity, PointCloud &out) final {
+        assert(disparity.size() == (size_t)width * height);
+        const int bound = hv_stereo_cloud_bound(session.ctx(), cloudStride);
+        if (bound < 0) session.check(bound, "hv_stereo_cloud_bound");
+        out.resize((size_t)std::max(bound, 0));
+        int n = 0;
+        session.check(hv_stereo_point_cloud(session.ctx(), disparity.data(), width, Q.data(), cloudStride,
+                                            reinterpret_cast<float *>(out.data()), bound, &n), "hv_stereo_point_cloud");
+        out.resize((size_t)n);
+    }
+};
+
+std::unique_ptr<StereoDisparity> StereoDisparity::buildHip(Session &s, int width, int height, const hv_stereo_bm_params &p,
+                                                           int stereoPointCloudStride)
+{
+    if (width != s.params().width || height != s.params().height)
+        throw std::invalid_argument("StereoDisparity::buildHip: width / height differ from the session's image size");
+    if (stereoPointCloudStride < 1) throw std::invalid_argument("StereoDisparity::buildHip: stereoPointCloudStride < 1");
+    return std::unique_ptr<StereoDisparity>(new HipStereoDisparity(s, width, height, p, stereoPointCloudStride));
 }
 
 std::unique_ptr<Undistorter> Undistorter::buildRectifiedHip(Session &s, int cameraIndex, std::shared_ptr<const Camera> rectified)

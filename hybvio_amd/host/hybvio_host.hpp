@@ -335,6 +335,29 @@ public:
                                   const hv_camera_model &camera1) = 0;
 };
 
+// tracker::StereoDisparity (src/tracker/stereo_disparity.hpp:13-31; stereo_disparity.cpp): cv::StereoBM with the speckle filter, the
+// per-track depth and the strided point cloud of tracker.computeDenseStereoDepth (tracker.cpp:532, :784-796), through
+// hv_stereo_disparity, hv_stereo_track_depth and hv_stereo_point_cloud. The rectified pair is read where the ingest left it: level
+// 0 of the two frames' device pyramids. accelerated::Image becomes a row-major int16 vector (disparity x 16, width * height), and
+// Q = disparityToDepthQ 16 row-major doubles, formed by the caller as stereo_rectifier.cpp:64-93 does. The visualisations stay with
+// the caller. width / height must be the session's; buildHip throws std::invalid_argument otherwise. Not pinned against an OpenCV
+// build: tests/stereo_bm_restatement.py states the rules and lists the doubts.
+class StereoDisparity {
+public:
+    using DisparityImage = std::vector<std::int16_t>;
+    using PointCloud = std::vector<std::array<float, 3>>;
+    static std::unique_ptr<StereoDisparity> buildHip(Session &session, int width, int height, const hv_stereo_bm_params &parameters,
+                                                     int stereoPointCloudStride = 5);        // sibling of build()
+    virtual ~StereoDisparity();
+    virtual DisparityImage buildDisparityImage() const = 0;
+    virtual void computeDisparity(ImagePyramid &rectifiedFirst, ImagePyramid &rectifiedSecond, DisparityImage &out) = 0;
+    virtual float getDepth(const std::array<double, 16> &Q, const DisparityImage &disparity, const Feature::Point &pixCoords) const = 0;
+    // getDepth for many tracks in one call (the loop of tracker.cpp:790-795)
+    virtual void getDepths(const std::array<double, 16> &Q, const DisparityImage &disparity, const std::vector<Feature::Point> &pixCoords,
+                           std::vector<float> &depths) const = 0;
+    virtual void computePointCloud(const std::array<double, 16> &Q, const DisparityImage &disparity, PointCloud &out) = 0;
+};
+
 // tracker::util::matchIntensities (src/tracker/util.hpp, util.cpp:173-179), the call of main.cpp:767,776: the mean and standard
 // deviation of r's intensities are moved towards l's (weight 1: onto them). l is read, r's pixels are rewritten in place -- r.data
 // must point at writable memory although GrayImage carries a pointer to const -- and a constant r stays as it is (the reference

@@ -591,6 +591,81 @@ int hv_gftt_legacy_keypoints_batch_dev(hv_ctx *ctx, const hv_gftt_legacy_params 
 int hv_gftt_legacy_detect(hv_ctx *ctx, const hv_gftt_legacy_params *p, int slot, const float *prev_xy, int n_prev, int mask_radius,
                           float *corners_xy, int capacity, int *n_out);
 
+/* ---- dense stereo depth: StereoBM block matching, speckle filter, track depth, point cloud (added within ABI 4) --------------
+ * Replaces tracker.computeDenseStereoDepth (src/tracker/tracker.cpp:532 and :784-796 computeDenseStereoDepth; src/tracker/image.cpp:
+ * 108-139, whose line 115 notes "Currently only supported on the CPU, even if rectification was done on the GPU"; all of
+ * src/tracker/stereo_disparity.cpp: cv::StereoBM::create(nd) with speckle window 500 and range 10, getDepth :66-77,
+ * computePointCloud :79-94; the cloud is what backend.cpp:1328 hands out) on the level-0 images of pyramid slots, the rectified pair
+ * the ingest wrote there. The rules, restated in tests/stereo_bm_restatement.py (written from the algorithm; NOT pinned against an
+ * OpenCV build -- the doubts: the prefilter's edge rows, the tie order of a SIMD path, the unscaled speckle range, the left edge of
+ * the valid rectangle, Eigen's summation order; DESIGN.md lists them under "not pinned"):
+ *   prefilter  XSOBEL, out = clamp(S, -c, c) + c; rows mirror without repeating the edge row; columns 0 and W - 1, and the last row
+ *              of an odd height, are c;
+ *   rectangle  nd - 1 + 10 <= x < W - 10, 10 <= y < H - 10; everything else is FILTERED = -16; output int16 = disparity x 16;
+ *   pixel      sad[d] over the 21 x 21 window, textsum < textureThreshold -> FILTERED; the first strictly smallest sad in OpenCV's
+ *              index k = nd - 1 - d (a tie goes to the larger disparity); a rival further than 1 away with sad <= m + m * ratio / 100
+ *              -> FILTERED; the sub-pixel step ((nd - mink - 1) * 256 + (dd ? (p - n) * 256 / dd : 0) + 15) >> 4;
+ *   speckles   4-neighbour components of the pixels != FILTERED joined where |a - b| <= speckleRange (unscaled); a component of
+ *              <= speckleWindowSize pixels becomes FILTERED;
+ *   getDepth / computePointCloud  binary32: Qf . (x, y, v / 16, 1) summed left to right, IEEE division, sqrt((x^2 + y^2) + z^2).
+ * blockSize 21 is the one size served: other odd sizes >= 5 return HV_ERR_UNSUPPORTED, as do numDisparities > 256,
+ * uniquenessRatio > 100 and textureThreshold > 65535. Everything `_dev` is asynchronous on the context stream with no allocation or
+ * synchronisation inside (capturable in a HIP graph). The image kernels (prefilter, matching, speckles, count) are timed under
+ * HV_K_INGEST, the depth and cloud kernels under HV_K_STEREO_GATE. The matching kernel keeps no cost volume in global memory.
+ * Checks made before the context is looked at: HV_ERR_INVALID for NULL required pointers, negative sizes, numDisparities not a
+ * positive multiple of 16, blockSize even or < 5, preFilterCap outside 1 .. 63, negative textureThreshold / uniquenessRatio,
+ * cloud_stride < 1; then HV_ERR_UNSUPPORTED for the limits above and n_sets > 32767 (65535 for the other entries). With the
+ * context: HV_ERR_INVALID for a set stride below width * height. */
+typedef struct hv_stereo_bm_params {
+    int numDisparities;     /* std::ceil(width * 0.1f / 32) * 32 (stereo_disparity.cpp:39): hv_stereo_num_disparities(width) */
+    int blockSize;          /* 21 */
+    int preFilterCap;       /* 31 */
+    int textureThreshold;   /* 10 */
+    int uniquenessRatio;    /* 15 */
+    int speckleWindowSize;  /* 500 (stereo_disparity.cpp:19); <= 0: no speckle filter */
+    int speckleRange;       /* 10 (stereo_disparity.cpp:18); < 0: no speckle filter */
+} hv_stereo_bm_params;
+#define HV_STEREO_FILTERED (-16)
+int hv_stereo_num_disparities(int width);                                      /* 752 -> 96, 1280 -> 128, 320 -> 32, 160 -> 32 */
+void hv_stereo_bm_default_params(hv_stereo_bm_params *p, int width);
+/* work_dev of hv_stereo_disparity_batch_dev (16-byte aligned): two prefiltered byte planes and the int32 labels and counters of the
+ * speckle filter per set; 0 for a NULL context or refused parameters */
+size_t hv_stereo_work_bytes(hv_ctx *ctx, const hv_stereo_bm_params *p, int n_sets);
+size_t hv_filter_speckles_work_bytes(int width, int height, int n_sets);       /* work_dev of hv_filter_speckles_batch_dev */
+int hv_stereo_cloud_bound(hv_ctx *ctx, int cloud_stride);                      /* ceil(W / s) * ceil(H / s): a max_points that cannot overflow */
+/* OpenCvStereoDisparity::computeDisparity for n_sets pairs: the level-0 images of left_slots_dev[s] / right_slots_dev[s] ->
+ * disp_dev [n_sets][H][W] int16 (set s at disp_dev + s * disp_set_stride elements, rows W apart). The speckle filter runs when
+ * speckleWindowSize > 0 && speckleRange >= 0. n_valid_dev (NULL allowed) [n_sets]: the pixels != FILTERED. A set whose slot is no
+ * valid slot or holds no image reports -1 and writes nothing. */
+int hv_stereo_disparity_batch_dev(hv_ctx *ctx, const hv_stereo_bm_params *p, int n_sets, const int *left_slots_dev,
+                                  const int *right_slots_dev, void *work_dev, int16_t *disp_dev, long long disp_set_stride,
+                                  int *n_valid_dev);
+/* cv::filterSpeckles(disp, new_val, max_size, max_diff) in place on n_sets int16 maps of width x height (any size, not the
+ * context's); work_dev: hv_filter_speckles_work_bytes(width, height, n_sets) bytes, 16-byte aligned. */
+int hv_filter_speckles_batch_dev(hv_ctx *ctx, int n_sets, int width, int height, int16_t *disp_dev, long long set_stride, int new_val,
+                                 int max_size, int max_diff, void *work_dev);
+/* getDepth for every track: xy_dev [n_sets][max_points][2], n_points_dev [n_sets] (clamped to 0 .. max_points), depth_dev
+ * [n_sets][max_points] binary32, -1 where the reference returns -1 and for a non-finite coordinate or one beyond int range (the
+ * reference's cast is undefined there). Q: disparityToDepthQ, 16 row-major doubles on the host, formed by the caller as
+ * stereo_rectifier.cpp:64-93 does; it is rounded to binary32 as Q.cast<float>() does. disp_dev / stride: as written above. */
+int hv_stereo_track_depth_batch_dev(hv_ctx *ctx, int n_sets, int max_points, const int *n_points_dev, const float *xy_dev,
+                                    const int16_t *disp_dev, long long stride, const double *Q, float *depth_dev);
+/* computePointCloud: y, then x, in steps of cloud_stride (stereoPointCloudStride, 5); xyz_dev [n_sets][max_points][3] in that
+ * row-major order, n_points_dev [n_sets]. A set with more points than max_points reports -1 and writes nothing: never truncated. */
+int hv_stereo_point_cloud_batch_dev(hv_ctx *ctx, int n_sets, const int16_t *disp_dev, long long stride, const double *Q,
+                                    int cloud_stride, int max_points, float *xyz_dev, int *n_points_dev);
+/* One pair, host pointers, synchronous (staged through the context's arena, hv_stage.hpp): disp_host rows `stride` elements apart
+ * (>= width); HV_ERR_POOL for a slot that is not in use or holds no image. */
+int hv_stereo_disparity(hv_ctx *ctx, const hv_stereo_bm_params *p, int left_slot, int right_slot, int16_t *disp_host,
+                        long long stride);
+/* getDepth / computePointCloud on a disparity image the caller holds on the host (rows `stride` == width elements apart), one set,
+ * synchronous, the image staged through the arena with the points: what the C++ adapter calls. hv_stereo_point_cloud: capacity >=
+ * the number of points (hv_stereo_cloud_bound() always is), HV_ERR_INVALID when they do not fit. */
+int hv_stereo_track_depth(hv_ctx *ctx, int n_points, const float *xy_host, const int16_t *disp_host, long long stride, const double *Q,
+                          float *depth_host);
+int hv_stereo_point_cloud(hv_ctx *ctx, const int16_t *disp_host, long long stride, const double *Q, int cloud_stride, float *xyz_host,
+                          int capacity, int *n_out);
+
 /* ---- sub-pixel corner refinement (added within ABI 4) ----------------------------------------
  * Replaces tracker::SubPixelAdjuster::adjust (src/tracker/subpixel_adjuster.cpp:18-42): cv::cornerSubPix(image, corners,
  * Size(win, win), Size(-1, -1), TermCriteria(COUNT | EPS, maxIter, epsilon)) on the level-0 image of a pyramid slot, then
@@ -1721,11 +1796,11 @@ int hv_vio_sets(const hv_vio *vio);
 
 /* ---- per-kernel timing (hipEvents on the context stream) ---------------------------------- */
 enum { HV_K_PYR_L0 = 0, HV_K_PYR_LN = 1, HV_K_KLT = 2, HV_K_EKF_PREDICT = 3, HV_K_EKF_UPDATE = 4,
-       HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
+       HV_K_EKF_AUGMENT = 5, HV_K_GFTT = 6, HV_K_INGEST = 7 /* also the image kernels of hv_stereo_disparity*, hv_filter_speckles_batch_dev */, HV_K_VU_PREPARE = 8, HV_K_ROT_RANSAC = 9, HV_K_EKF_GATE = 10,
        HV_K_VU_TRI = 11 /* r06: the triangulation front of the split form (vu_tri_kernel); HV_K_VU_PREPARE then times the record-fed gates; also the tail kernel of hv_full_point_cloud_dev */,
        HV_K_SUBPIX = 12 /* added within ABI 4: hv_corner_subpix* */,
        HV_K_RANSAC5 = 13 /* added within ABI 4: hv_ransac5*, hv_hybrid_ransac_lk_batch_dev */,
-       HV_K_STEREO_GATE = 14 /* added within ABI 4: hv_flow_status_batch_dev, hv_track_gate*, hv_detection_filter* */,
+       HV_K_STEREO_GATE = 14 /* added within ABI 4: hv_flow_status_batch_dev, hv_track_gate*, hv_detection_filter*, hv_stereo_track_depth_batch_dev, hv_stereo_point_cloud_batch_dev */,
        HV_K_DETECT_TAIL = 15 /* added within ABI 4: hv_apply_min_distance_batch_dev, hv_gftt_corners_batch_dev, hv_gftt_detect_batch_dev */,
        HV_K_TRACK_TABLE = 16 /* added within ABI 4: hv_tracks_*_batch_dev */,
        HV_K_RANSAC3 = 17 /* added within ABI 4: hv_ransac3*, hv_upright2p* */,
