@@ -1906,7 +1906,9 @@ class VioParams(C.Structure):
                 ("control", EkfControlParams), ("session", SessionParams), ("output", OutputParams), ("camera0", CameraModel),
                 ("camera1", CameraModel), ("ransac2Threshold", C.c_double), ("trackChiTestOutlierR", C.c_double), ("visualR", C.c_double),
                 ("ransacRngSeed", C.c_int), ("odometryRngSeed", C.c_int), ("imu_samples_max", C.c_int), ("featureDetector", C.c_int),
-                ("useRansac3", C.c_int), ("predictOpticalFlow", C.c_int), ("batchVisualUpdate", C.c_int)]
+                ("useRansac3", C.c_int), ("predictOpticalFlow", C.c_int), ("batchVisualUpdate", C.c_int),
+                ("ransac5", Ransac5Params), ("upright2p", Upright2pParams), ("fast", FastParams), ("gftt_legacy", GfttLegacyParams),
+                ("useStereoUpright2p", C.c_int), ("useHybridRansac", C.c_int)]
 
 
 class VioView(C.Structure):
@@ -1915,12 +1917,13 @@ class VioView(C.Structure):
                 ("rng_pipeline", RngState), ("rng_ransac3", RngState), ("rng_odometry", RngState), ("record", OutputTable)] + [
         (k, C.c_void_p) for k in ("frame_num", "has_previous", "full_update", "keyframe", "keyframe_out", "good_frame", "reset_kind",
                                   "tracking_status", "n_candidates", "cand_id", "status", "gate_status", "slot_prev_left", "slot_cur_left",
-                                  "slot_right")]
+                                  "slot_right", "ransac_result", "ransac_score", "r5_summary")]
 
 
 PROTOTYPES.update({
     "hv_vio_default_params": (None, [C.POINTER(VioParams)]),
     "hv_vio_create": (C.c_int, [C.c_void_p, C.POINTER(VioParams), C.c_int, C.POINTER(C.c_void_p)]),
+    "hv_vio_create_session": (C.c_int, [C.c_void_p, C.POINTER(VioParams), C.c_int, C.POINTER(C.c_void_p)]),
     "hv_vio_destroy": (None, [C.c_void_p]),
     "hv_vio_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hv_vio_view_get": (C.c_int, [C.c_void_p, C.POINTER(VioView)]),
@@ -1957,23 +1960,26 @@ def _wrap(ptr, shape, typestr):
 
 
 class VioEngine:
-    """hv_vio: the default stereo session of n_sets resident sequences on one Context; frame() is one frame of every set."""
+    """hv_vio: a session of n_sets resident sequences on one Context; frame() is one frame of every set. session=False is
+    hv_vio_create (the default stereo session, everything else refused); session=True is hv_vio_create_session (mono and stereo, every
+    track filter, every detector). A mono session's frame() takes right_dev = 0."""
 
-    def __init__(self, ctx: Context, params: VioParams | None = None, n_sets: int = 1):
+    def __init__(self, ctx: Context, params: VioParams | None = None, n_sets: int = 1, session: bool = False):
         self.ctx, self.n_sets = ctx, n_sets
         self.params = params if params is not None else vio_default_params()
         self._h = C.c_void_p()
-        rc = lib().hv_vio_create(ctx._h, C.byref(self.params), n_sets, C.byref(self._h))
+        name = "hv_vio_create_session" if session else "hv_vio_create"
+        rc = getattr(lib(), name)(ctx._h, C.byref(self.params), n_sets, C.byref(self._h))
         if rc != 0:
             self._h = None
-            ctx._chk(rc, "hv_vio_create")
+            ctx._chk(rc, name)
         if not hasattr(ctx, "_children"):
             ctx._children = []
         ctx._children.append(self)
 
     @classmethod
-    def create(cls, ctx: Context, params: VioParams | None = None, n_sets: int = 1) -> "VioEngine":
-        return cls(ctx, params, n_sets)
+    def create(cls, ctx: Context, params: VioParams | None = None, n_sets: int = 1, session: bool = False) -> "VioEngine":
+        return cls(ctx, params, n_sets, session)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -2010,18 +2016,20 @@ class VioEngine:
     def view(self) -> dict:
         """The engine's arrays as torch tensors over its own device memory (nothing is copied): 'table', 'trail', 'session',
         'control', 'record' and the three 'rng_*' are dicts by member name, the stage outputs are tensors, 'ekf_handle' is the
-        engine's hv_ekf (not owned; state() reads its mean and covariance back)."""
+        engine's hv_ekf (not owned; state() reads its mean and covariance back). An array the session does not have (a mono
+        session's table.second_xy and slot_right, r5_summary without the hybrid filter) is None."""
         raw, p, S = self.raw_view(), self.params, self.n_sets
         M, K, V, T = p.tracks.maxTracks, p.trail.cameraTrailLength + 1, p.trail.maxVisualUpdates, p.output.cameraTrailLength
         W = session_window(p.session)
+        Cn = 2 if p.trail.useStereo else 1
         i4, f4, f8, u1 = "<i4", "<f4", "<f8", "|u1"
         spec = dict(
             table=dict(n_tracks=((S,), i4), ids=((S, M), i4), xy=((S, M, 2), f4), second_xy=((S, M, 2), f4), status=((S, M), i4),
                        blacklist=((S, M), u1), kf_xy=((S, M, 2), f4), kf_valid=((S, M), u1), frame_num=((S,), i4), mask_steps=((S,), i4),
                        mask_radius=((S,), i4), frame_flags=((S,), u1)),
             trail=dict(n_keyframes=((S,), i4), frame_counter=((S,), i4), kf_row=((S, K), i4), frame_number=((S, K), i4),
-                       timestamp=((S, K), f8), col_id=((S, M), i4), col_len=((S, M), i4), image_point=((S, K, M, 2, 2), f4),
-                       norm_point=((S, K, M, 2, 2), f8), norm_velocity=((S, K, M, 2, 2), f8), used=((S, K, M), u1), n_blacklist=((S,), i4),
+                       timestamp=((S, K), f8), col_id=((S, M), i4), col_len=((S, M), i4), image_point=((S, K, M, Cn, 2), f4),
+                       norm_point=((S, K, M, Cn, 2), f8), norm_velocity=((S, K, M, Cn, 2), f8), used=((S, K, M), u1), n_blacklist=((S,), i4),
                        blacklist_ids=((S, M), i4), n_order=((S,), i4), n_skipped=((S,), i4), skipped_pos=((S, M), i4),
                        skipped_id=((S, M), i4), cand_pos=((S, V), i4), cand_col=((S, V), i4)),
             session=dict(good_ring=((S, W), f4), ring_head=((S,), i4), ring_entries=((S,), i4), tracking_status=((S,), i4),
@@ -2037,13 +2045,13 @@ class VioEngine:
         out = {}
         for name, members in list(spec.items()) + [(k, rng) for k in ("rng_pipeline", "rng_ransac3", "rng_odometry")]:
             struct = getattr(raw, name)
-            out[name] = {k: _wrap(getattr(struct, k), shape, ts) for k, (shape, ts) in members.items()}
+            out[name] = {k: _wrap(getattr(struct, k), shape, ts) if getattr(struct, k) else None for k, (shape, ts) in members.items()}
         stage = dict(frame_num=((S,), i4), has_previous=((S,), u1), full_update=((S,), u1), keyframe=((S,), i4), keyframe_out=((S,), i4),
                      good_frame=((S,), u1), reset_kind=((S,), i4), tracking_status=((S,), i4), n_candidates=((S,), i4), cand_id=((V, S), i4),
                      status=((V, S, 2), i4), gate_status=((V, S), i4), slot_prev_left=((S,), i4), slot_cur_left=((S,), i4),
-                     slot_right=((S,), i4))
+                     slot_right=((S,), i4), ransac_result=((S, 2), i4), ransac_score=((S,), f8), r5_summary=((S, 4), i4))
         for k, (shape, ts) in stage.items():
-            out[k] = _wrap(getattr(raw, k), shape, ts)
+            out[k] = _wrap(getattr(raw, k), shape, ts) if getattr(raw, k) else None
         out["ekf_handle"] = C.c_void_p(raw.ekf)
         out["state_dim"] = lib().hv_ekf_state_dim(out["ekf_handle"])
         return out

@@ -1709,7 +1709,10 @@ int hv_match_intensities(hv_ctx *ctx, int width, int height, const uint8_t *l_ho
  *   ransacRngSeed (4649), odometryRngSeed (0)    the seeds of the two tracker generators and of the odometry generator;
  *   imu_samples_max               the most IMU samples a frame may bring, 1 .. HV_EKF_MAX_PREDICT_SAMPLES (default: that limit);
  *   featureDetector, useRansac3, predictOpticalFlow, batchVisualUpdate   the reference's switches whose other settings the engine
- *                                 refuses (defaults HV_DETECTOR_GPU_GFTT, 1, 1, 0).
+ *                                 refuses (defaults HV_DETECTOR_GPU_GFTT, 1, 1, 0);
+ *   ransac5, upright2p, fast, gftt_legacy, useStereoUpright2p (0), useHybridRansac (1)   the entries and switches only
+ *                                 hv_vio_create_session reads (below), each struct with its own default function's values
+ *                                 (parameter_definitions.c:298, 268 for the switches).
  * second_to_first of RANSAC3 is flow.imuToCamera * flow.secondCameraToImu; gate.cam0ToCam1 and the four matrices of `flow` are
  * the caller's, as for the entries themselves.
  * hv_vio_create decides, before the device is touched and in this order: HV_ERR_INVALID for a NULL params or out, n_sets < 1,
@@ -1761,6 +1764,12 @@ typedef struct hv_vio_params {
     int ransacRngSeed, odometryRngSeed;
     int imu_samples_max;
     int featureDetector, useRansac3, predictOpticalFlow, batchVisualUpdate;
+    /* read by hv_vio_create_session alone (hv_vio_create ignores them) */
+    hv_ransac5_params ransac5;
+    hv_upright2p_params upright2p;
+    hv_fast_params fast;
+    hv_gftt_legacy_params gftt_legacy;
+    int useStereoUpright2p, useHybridRansac;
 } hv_vio_params;
 void hv_vio_default_params(hv_vio_params *p);
 typedef struct hv_vio hv_vio;
@@ -1784,9 +1793,47 @@ typedef struct hv_vio_view {              /* device memory unless noted; V = tra
     const int32_t *cand_id;               /* [V][n_sets] */
     const int32_t *status;                /* [V][n_sets][2] hv_ekf_visual_frame_ragged_dev */
     const int32_t *gate_status;           /* [V][n_sets] */
-    const int32_t *slot_prev_left, *slot_cur_left, *slot_right;   /* [n_sets] the slot roles of the NEXT frame */
+    const int32_t *slot_prev_left, *slot_cur_left, *slot_right;   /* [n_sets] the slot roles of the NEXT frame; slot_right NULL: mono */
+    const int32_t *ransac_result;         /* [n_sets][2] result_dev of the session's filter: {RansacResult type, inlierCount} */
+    const double *ransac_score;           /* [n_sets] its score_dev, the stationarity score hv_tracks_update_batch_dev read */
+    const int32_t *r5_summary;            /* [n_sets][4] r5_summary_dev of hv_hybrid_ransac_lk_batch_dev; NULL unless hybrid */
 } hv_vio_view;
 int hv_vio_create(hv_ctx *ctx, const hv_vio_params *p, int n_sets, hv_vio **out);
+/* Every session the reference's useStereo, useRansac3, useStereoUpright2p, useHybridRansac and featureDetector select, as the same
+ * object with the same call per frame. With default parameters it builds exactly the engine of hv_vio_create: the same buffers,
+ * the same launches, the same bits.
+ * Mono (trail.useStereo == output.useStereo == 0; tracker.useStereo is false by default, codegen/parameter_definitions.c:349): the
+ * mono path of TrackerImplementation::track and detectFeatures (src/tracker/tracker.cpp:378-559, 241-312). hv_vio_frame takes
+ * right_dev == NULL (a right image on a mono engine is HV_ERR_INVALID, as is none on a stereo engine); a set holds two pyramid
+ * slots, previous and current left; no stereo LK runs, hv_track_gate_batch_dev, hv_tracks_update_batch_dev,
+ * hv_detection_filter_batch_dev and hv_tracks_append_batch_dev run in their mono forms (every new corner starts TRACKED,
+ * tracker.cpp:291), the visual update runs with vu.useStereo 0. The stereo-only arrays do not exist: table.second_xy and slot_right
+ * of the view are NULL.
+ * The filter behind RANSAC2 (which always runs) is chosen once, on the host, as RansacPipeline::compute chooses it
+ * (src/tracker/ransac_pipeline.cpp:119-150):
+ *   useRansac3 and stereo                  hv_ransac3_lk_batch_dev, as in hv_vio_create (:121-123);
+ *   else useStereoUpright2p and stereo     hv_upright2p_lk_batch_dev (:124-127) behind the frame's predicts, fed from the second
+ *                                          tracker generator (rng_ransac3 of the view, seeded with ransacRngSeed as
+ *                                          src/tracker/stereo_upright_2p.cpp:101 seeds its own): 2 * MaxIterations draws, 2 *
+ *                                          iterations-run kept consumed;
+ *   else useHybridRansac                   hv_hybrid_ransac_lk_batch_dev (:128-133) with camera0 twice (tracker.cpp:482-487), in a
+ *                                          mono session and in a stereo one alike; it draws nothing;
+ *   else                                   no filter (:134-136): the statuses stay as the gate left them, ransac_result is {0, 0}
+ *                                          and the score is RANSAC2 inliers / TRACKED count without a guard, so no TRACKED feature
+ *                                          gives 0 / 0 = NaN, which the table's stationarity rule reads as "not stationary"
+ *                                          (score * ... > threshold is false). This is the engine's one piece of arithmetic.
+ * A mono session with useStereoUpright2p falls through to the hybrid filter (:124 asks for two cameras). The second tracker
+ * generator of a session whose filter draws nothing is seeded at creation and never touched again.
+ * featureDetector selects hv_gftt_detect_batch_dev, hv_fast_detect_batch_dev (params `fast`) or hv_gftt_legacy_detect_batch_dev
+ * (params `gftt_legacy`), each with the table's mask, radius and cap; hv_corner_subpix_batch_dev follows every one of them
+ * (src/tracker/image.cpp:69-85). The key point capacity of the last two is their own bound, so no image is refused for its count.
+ * The checks, in hv_vio_create's order: every HV_ERR_INVALID of hv_vio_create (gftt.maxTracks included, whatever the detector); the
+ * selected detector's maxTracks differing from tracks.maxTracks or an unknown featureDetector, HV_ERR_INVALID; then
+ * HV_ERR_UNSUPPORTED for gate.independentStereoOpticalFlow, predictOpticalFlow 0, batchVisualUpdate, trail.fullPointCloud,
+ * ekf.hybridMapSize > 0, n_sets > 65535 and a draw count of the selected filter below 1 or above HV_RNG_MAX_DRAWS; then the context
+ * checks, where a mono engine needs 2 * n_sets free pyramid slots and a stereo engine 3 * n_sets. hv_vio_replay_period is 1 for
+ * every session. */
+int hv_vio_create_session(hv_ctx *ctx, const hv_vio_params *p, int n_sets, hv_vio **out);
 void hv_vio_destroy(hv_vio *vio);
 int hv_vio_frame(hv_vio *vio, const uint8_t *left_dev, const uint8_t *right_dev, long long image_stride_bytes,
                  int row_stride_bytes, int n_samples, const double *t_dev, const double *gyro_dev, const double *acc_dev);
